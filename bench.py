@@ -19,6 +19,14 @@ into N blocks + the gather of c1/c2 (prove) and of the verdicts (verify).
 127.0.0.1); under an external launcher (RANK / WORLD_SIZE set) it checks WORLD_SIZE == N and
 exits with status 2 otherwise.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: inputs, ONE untimed prove (the
+proofs the verify steps consume), W warm-up and K timed verify steps, the line.  `prove.value` stays null there.  `--full`
+adds everything else the line reports: the timed prove leg, the other scaling mode at N > 1, the CPU baseline and oracle
+samples, the PCIe / host-API / zkp_multi legs and the other BASELINE.json configurations (`other_configs`).
+
+--dump-outputs DIR writes what the last timed verify step returned — the all-gathered verdict bytes, one per proof — as
+DIR/verdict.npy (float32).  The inputs are seeded: the same arguments give the same inputs on every run.
+
 Prints ONE JSON line on rank 0.  See DESIGN.md §6 for the definitions of roofline/cpu_baseline."""
 import argparse
 import glob
@@ -448,6 +456,11 @@ def parse_args(argv=None):
                     help="what a PROVE step exchanges: all = the c1 / c2 slabs are all-gathered onto every rank (north_star; 2 x 64 KiB per proof "
                          "at n = 2048: 4.3 GB received per rank per step at 8 x 4096 proofs); verdicts = nothing (each rank keeps its proofs)")
     ap.add_argument("--n-bits", type=int, default=2048)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: timed prove, the other scaling mode, CPU baseline, PCIe, host API, zkp_multi, "
+                         "other_configs (the --no-* / --*-batch / --cpu-sample options below shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed verify step to DIR/verdict.npy (float32)")
     ap.add_argument("--cpu-sample", type=int, default=64, help="proofs verified by the all-cores CPU baseline (0 = skip the CPU legs and the oracle samples)")
     ap.add_argument("--no-prove-leg", action="store_true")
     ap.add_argument("--no-host-api-leg", action="store_true", help="skip the C++ host-API leg (tests/cpp/host_bench.cpp; rank 0 at N = 1 only)")
@@ -614,9 +627,9 @@ def main():
     recv_bytes = gathered.pop("recv_bytes")
     phases = gathered.pop("phases")
 
-    # ---- prove leg (also produces the proofs the verify leg consumes)
+    # ---- prove leg (also produces the proofs the verify leg consumes): timed under --full only
     prove = None
-    if args.no_prove_leg:
+    if args.no_prove_leg or not args.full:
         engine.prove(pb, wt); sync()
     else:
         with ClockSampler(local_rank) as clk_p:
@@ -641,7 +654,10 @@ def main():
     ok = ok and bool(torch.equal(gathered["verdict"][my_lo:my_lo + B], expect)) and gathered["verdict"].shape[0] == B_total
     if "c1" in gathered:
         ok = ok and bool(torch.equal(gathered["c1"][my_lo:my_lo + B], pb.c1))
-    ok = ok and (("c1" in gathered) == (args.gather == "all" and not args.no_prove_leg))
+    ok = ok and (("c1" in gathered) == (args.gather == "all" and prove is not None))
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "verdict.npy"), gathered["verdict"].cpu().numpy().astype(np.float32))
     value = B_total * args.steps / dt
     bn_lanes, bn_ok = ctx.diag_basen_last()
     basen = bool(bn_lanes and bn_ok)
@@ -676,12 +692,12 @@ def main():
     other_mode = "strong" if args.scaling == "weak" else "weak"
     if world == 1:
         scaling_values[other_mode] = dict(this_mode, note="one GPU: the two modes are the same run")
-    elif not args.no_prove_leg:
+    elif args.full and not args.no_prove_leg:
         scaling_values[other_mode], same = scaling_leg(other_mode, args, engine, synth, shard, torch, dev, ctx, sync, timed, n, n_bits, world, rank)
         ok = ok and same
 
     cpu = pcie = other = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         if args.cpu_sample > 0:
             cpu, same = cpu_baseline(args, pb, wt, verdict, np)
@@ -690,11 +706,11 @@ def main():
             pcie, same = pcie_leg(ctx, pb, expect, np, B)
             ok = ok and same
     host_api = None
-    if rank == 0 and world == 1 and not args.no_host_api_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_host_api_leg:
         host_api, same = host_api_leg(B)
         ok = ok and same
     capi_multi = None
-    if not args.no_capi_multi_leg and not shared_gpu:
+    if args.full and not args.no_capi_multi_leg and not shared_gpu:
         barrier()
         if rank == 0:
             try:
@@ -703,7 +719,7 @@ def main():
             except Exception as e:                       # (a node whose devices this process may not open: the leg is reported as missing)
                 capi_multi = {"error": f"{type(e).__name__}: {e}"}
         barrier()
-    if not args.no_other_configs:
+    if args.full and not args.no_other_configs:
         env = dict(args=args, ctx=ctx, engine=engine, synth=synth, shard=shard, torch=torch, dist=dist, dev=dev, sync=sync, barrier=barrier,
                    timed_reps=timed_reps, enc_roofline=enc_roofline, lpl=lpl, np=np, world=world, rank=rank, pb=pb, wt=wt, local_rank=local_rank)
         other, same = other_configs(env)
@@ -723,7 +739,7 @@ def main():
     if rank == 0:
         per = "per GPU" if args.scaling == "weak" else f"in all, cut into {world} blocks"
         out = {"metric": f"RangeProofNi proofs/sec + verifies/sec, n=2048, batch={args.batch} {per} (value = verifies/sec; proofs/sec in prove.value)", "value": value, "unit": "verifies/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "full": args.full,
                "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u32 (29-bit limbs, u64 accumulate)",
                "data": "synthetic" + (" — FUNCTIONAL CHECK ONLY: all ranks share ONE GPU, collectives over gloo (ZKP_BENCH_SHARED_GPU=1); timings are meaningless" if shared_gpu else ""),
                "verdicts_ok": ok,

@@ -40,6 +40,7 @@ def test_pmc_lookup_reads_the_committed_profiles():
 def test_argument_defaults_are_the_baseline_sizes():
     a = bench.parse_args([])
     assert (a.gpus, a.batch, a.n_bits, a.big_batch, a.distinct_batch) == (1, 4096, 2048, 4096, 4096)
+    assert not a.full and a.dump_outputs is None             # a plain run: the headline legs only, nothing written
 
 
 def test_executed_work_figure_follows_the_kernel_script():

@@ -258,7 +258,7 @@ def test_bench_two_ranks_share_the_one_gpu(scaling):
     env = dict(os.environ, ZKP_BENCH_SHARED_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "2", "--scaling", scaling, "--batch", "66", "--steps", "1", "--warmup", "0", "--cpu-sample", "0",
+    cmd = [sys.executable, os.path.join(H.ROOT, "bench.py"), "--full", "--gpus", "2", "--scaling", scaling, "--batch", "66", "--steps", "1", "--warmup", "0", "--cpu-sample", "0",
            "--no-pcie-leg", "--big-batch", "9", "--distinct-batch", "34", "--ck-batch", "1025", "--interactive-batch", "33", "--other-reps", "1"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -271,6 +271,31 @@ def test_bench_two_ranks_share_the_one_gpu(scaling):
     assert ck["n_gpus"] == 2 and ck["keys_per_rank"] == 513 and ck["all_rejected_as_expected"]          # 1025 keys: blocks of 513 + 512
     assert big["n_gpus"] == 2 and big["batch_per_rank"] == 5 and big["verdicts_ok"]                       # 9 proofs: blocks of 5 + 4
     assert all(v.get("verdicts_ok", True) and v.get("all_accepted", True) for v in legs.values())
+
+
+def test_bench_plain_run_times_the_verify_steps_and_dumps_their_verdicts(tmp_path):
+    """a plain `bench.py` run: only the headline legs (no timed prove, no other legs), `--steps` timed steps, and with
+    --dump-outputs the verdicts of the last timed step — 1 for every honest proof, 0 for every 64th (tampered) one"""
+    import json
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ZKP_BENCH_SHARED_GPU"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--batch", "130", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["verdicts_ok"] and d["steps"] == 3 and d["warmup"] == 1 and not d["full"]
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "verifies/s" and d["higher_is_better"]
+    assert d["phases_rank0"]["verify"]["steps"] == 3
+    assert d["prove"] is None and all(d[k] is None for k in ("cpu_baseline", "pcie_inclusive", "host_api", "capi_multi", "other_configs"))
+    v = np.load(tmp_path / "out" / "verdict.npy")
+    expect = np.ones(130, np.float32)
+    expect[::64] = 0
+    assert v.dtype == np.float32 and np.array_equal(v, expect)
 
 
 def test_receive_buffers_of_an_8_rank_prove_step_fit_the_gpu():

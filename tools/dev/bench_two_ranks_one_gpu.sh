@@ -3,7 +3,7 @@
 # both ranks use cuda:0, the collectives run over gloo.  Timings are meaningless; rc and verdicts_ok are the result.
 export ZKP_BENCH_SHARED_GPU=1
 for scaling in weak strong; do
-  python bench.py --gpus 2 --scaling $scaling --batch 130 --steps 1 --warmup 0 --cpu-sample 0 --no-pcie-leg --big-batch 33 --distinct-batch 66 --ck-batch 2049 --interactive-batch 65 --other-reps 1 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --gpus 2 --scaling $scaling --batch 130 --steps 1 --warmup 0 --cpu-sample 0 --no-pcie-leg --big-batch 33 --distinct-batch 66 --ck-batch 2049 --interactive-batch 65 --other-reps 1 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.readline())
 print('$scaling', 'n_gpus', d['n_gpus'], 'ok', d['verdicts_ok'], 'value %.1f' % d['value'], d['config']['proofs_per_rank'], d['config']['proofs_total'])
 print('    rccl', d['rccl']['backend'], 'ranks_seen', d['rccl']['ranks_seen'], 'boards', d['rccl']['distinct_boards_seen'])
