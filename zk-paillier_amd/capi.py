@@ -346,11 +346,13 @@ class Context:
         return self.lib.zkp_diag_last_split(self.h)
 
     def set_fuse_hash(self, on: bool):
-        """the transcript hash of a one-proof verify as a workgroup of its Enc launch (include/zkp_hip_diag.h); on by default"""
+        """the transcript hashes of a verify as workgroups of its Enc launch (include/zkp_hip_diag.h): taken whenever the call has the
+        two-stream shape, fewer proofs than compute units, and its Enc launch on the latency engine's one-Enc-per-wavefront ladder, which
+        takes the hashes (1 ... 10 proofs at 128 rows under one 2048-bit key); on by default"""
         self.check(self.lib.zkp_diag_set_fuse_hash(self.h, 1 if on else 0))
 
     def last_fused_hash(self) -> bool:
-        """did the most recent verify call carry its transcript hash inside its Enc launch?"""
+        """did the most recent verify call carry its transcript hashes inside its Enc launch (the rule of set_fuse_hash)?"""
         return self.lib.zkp_diag_last_fused_hash(self.h) == 1
 
     def set_key_cache(self, on: bool):

@@ -165,7 +165,10 @@ static int32_t lat_forward_plain(zkp_ctx* c, int32_t st) {
 }
 
 // the items a verify's work list is expected to hold when the launch is sized for `bound` (2 per row: an Open row has two Enc checks, a Mask
-// row one, the challenge bits are fair): three quarters, + 3 % (5 proofs: 960 + 40 of 1280; the spread of 5 proofs is 13)
+// row one, the challenge bits are fair): three quarters, + 3 % (5 proofs: 960 + 40 of 1280; the spread of 5 proofs is 13).
+// A PERFORMANCE assumption only: the prover chooses the response kinds, and the kind-derived list of the two-stream shape holds up to the
+// whole bound — crafted all-Open proofs, about 1.33x the items planned here.  Every launch sized by it claims until the list is empty, so
+// such a verify is slower, its verdicts the same (tests/test_gpu_verify_crafted.py).
 static uint64_t expected_items(uint64_t bound) { return (3 * bound + 3) / 4 + bound / 32; }
 // which of the ctx's secondary engines has this many limbs per lane (-1: none; always -1 inside a secondary engine)
 static int engine_with(const zkp_ctx* c, int limbs_per_lane) {
@@ -1063,7 +1066,8 @@ extern "C" int32_t zkp_diag_set_r2l(zkp_ctx* c, int32_t mode) try {
 #endif
   return ZKP_OK;
 } ZKP_CATCH(c)
-// The transcript hashes of a verify of 1 ... 8 proofs as workgroups of its Enc launch (k_enc_basen_r2l5 / k_enc_basen_r2l; csrc/zkp_api_proofs.inc range_verify_impl): on / off;
+// The transcript hashes of a verify as workgroups of its Enc launch (k_enc_basen_r2l5 / k_enc_basen_r2l: the two-stream shape, fewer proofs than
+// compute units, the r2l launch taking the hashes — 1 ... 10 proofs at 128 rows; csrc/zkp_api_proofs.inc range_verify_impl): on / off;
 // did the most recent verify call of the ctx run that way?
 extern "C" int32_t zkp_diag_set_fuse_hash(zkp_ctx* c, int32_t on) try {
   if (!c) return ZKP_EINVAL;

@@ -383,6 +383,21 @@ extern "C" int32_t zkp_range_challenge_batch(zkp_ctx* c, const zkp_range_ni_proo
   return st ? st : fin;
 } ZKP_CATCH(c)
 
+// Names a verify's transcript hashes to the Enc launch for the length of it (c->fuse_hash points at a local of range_verify_impl): cleared
+// however the scope is left, so that no later call finds it dangling.  fuse_hash_taken outlives a normal exit (the caller and
+// zkp_diag_last_fused_hash read it); an exception out of the launch clears it too.
+struct FuseHashScope {
+  zkp_ctx* c;
+  int unwinding;
+  FuseHashScope(zkp_ctx* c_, const RangeHashArgs* h) : c(c_), unwinding(std::uncaught_exceptions()) { c->fuse_hash = h; c->fuse_hash_taken = false; }
+  ~FuseHashScope() {
+    c->fuse_hash = nullptr;
+    if (std::uncaught_exceptions() > unwinding) c->fuse_hash_taken = false;
+  }
+  FuseHashScope(const FuseHashScope&) = delete;
+  FuseHashScope& operator=(const FuseHashScope&) = delete;
+};
+
 template <int G>
 static int32_t range_verify_impl(zkp_ctx* c, const zkp_range_ni_proofs& p, uint8_t* verdict, const uint8_t* e_in = nullptr,
                                  const uint8_t* e_len_in = nullptr) {
@@ -464,10 +479,8 @@ static int32_t range_verify_impl(zkp_ctx* c, const zkp_range_ni_proofs& p, uint8
   if ((st = fresh_work_counter(c, &a.work_counter))) return st;
   {
     TimedRegion tr(c, 0);
-    c->fuse_hash = fuse ? &fused_hash : nullptr;
-    c->fuse_hash_taken = false;
+    FuseHashScope fh(c, fuse ? &fused_hash : nullptr);
     launch_k_enc<G>(c, blocks, a);
-    c->fuse_hash = nullptr;
   }
   HIPCHK(c, hipGetLastError());
   if (fuse) {
