@@ -340,6 +340,60 @@ pub fn range_ni_prove_batch(ek: &EncryptionKey, statements: &[RangeStatement]) -
     Some(out)
 }
 
+/// The same from what `RangeProofNi::prove` takes — statements and secrets only: a fresh 32-byte seed from the crate's RNG (`rand::random`,
+/// the source `generate_encrypted_pairs` draws its coins from) is expanded into (w1, w2, r1, r2) ON THE GPU by
+/// `zkp_range_ni_prove_seeded_batch` (the stream is published in include/zkp_hip.h).  No witness is sampled through GMP, flattened or
+/// uploaded, and none is left on the host; the seed — worth the whole witness — is overwritten before this returns and never reused.
+pub fn range_ni_prove_seeded_batch(ek: &EncryptionKey, statements: &[RangeStatement]) -> Option<Vec<RangeProofNi>> {
+    let n_bits = width_for(&ek.n)?;
+    let kw = (n_bits / 32) as usize;
+    let b = statements.len();
+    let ef = SECURITY_PARAMETER;
+    if b == 0 {
+        return Some(Vec::new());
+    }
+    let mut batch = RangeBatch::new(n_bits, b, ef);
+    if !put_limbs(&mut batch.n, &ek.n) {
+        return None;
+    }
+    let (mut x, mut r) = (vec![0u32; b * kw], vec![0u32; b * kw]);
+    for (k, st) in statements.iter().enumerate() {
+        if !put_limbs(&mut batch.range[k * kw..(k + 1) * kw], st.range)
+            || !put_limbs(&mut batch.ciphertext[k * 2 * kw..(k + 1) * 2 * kw], st.ciphertext)
+            || !put_limbs(&mut x[k * kw..(k + 1) * kw], st.secret_x)
+            || !put_limbs(&mut r[k * kw..(k + 1) * kw], st.secret_r)
+        {
+            return None;
+        }
+    }
+    let mut seed: [u8; 32] = random();
+    let mut status = vec![0u8; b];
+    let raw = batch.raw();
+    let done = with_ctx(|ctx| {
+        ok(unsafe { sys::zkp_range_ni_prove_seeded_batch(ctx, &raw, x.as_ptr(), r.as_ptr(), seed.as_ptr(), 0, ptr::null_mut(), ptr::null_mut(), status.as_mut_ptr(), 0) })
+    });
+    for byte in seed.iter_mut() {
+        unsafe { ptr::write_volatile(byte, 0) };
+    }
+    done?;
+    if status.iter().any(|s| *s != 0) {
+        return None; // an empty interval (range < 3) or a row the fixed width cannot carry: GMP decides
+    }
+    let mut out = Vec::with_capacity(b);
+    for (k, st) in statements.iter().enumerate() {
+        let (encrypted_pairs, proof) = batch.proof(k);
+        out.push(RangeProofNi {
+            ek: ek.clone(),
+            range: st.range.clone(),
+            ciphertext: st.ciphertext.clone(),
+            encrypted_pairs,
+            proof,
+            error_factor: SECURITY_PARAMETER,
+        });
+    }
+    Some(out)
+}
+
 /// `RangeProofNi::verify_self` (range_proof_ni.rs:109-128 -> range_proof.rs:254-355) for many proofs under one key.
 /// Entry k is `None` when proof k has to be decided by the GMP path (not canonical, see the module docs); the whole result is
 /// `None` when the key is not one the kernels carry or there is no GPU.
@@ -391,6 +445,14 @@ impl RangeProofNi {
     /// in the original GMP body) when the GPU cannot take the batch.
     pub fn prove_batch(ek: &EncryptionKey, statements: &[RangeStatement]) -> Vec<RangeProofNi> {
         match range_ni_prove_batch(ek, statements) {
+            Some(v) => v,
+            None => statements.iter().map(|s| RangeProofNi::prove(ek, s.range, s.ciphertext, s.secret_x, s.secret_r)).collect(),
+        }
+    }
+
+    /// `prove_batch` with the witness expanded on the GPU from a fresh seed (`range_ni_prove_seeded_batch`); the same fall-back.
+    pub fn prove_seeded(ek: &EncryptionKey, statements: &[RangeStatement]) -> Vec<RangeProofNi> {
+        match range_ni_prove_seeded_batch(ek, statements) {
             Some(v) => v,
             None => statements.iter().map(|s| RangeProofNi::prove(ek, s.range, s.ciphertext, s.secret_x, s.secret_r)).collect(),
         }

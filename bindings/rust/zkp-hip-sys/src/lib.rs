@@ -115,6 +115,8 @@ extern "C" {
     pub fn zkp_paillier_enc_batch(ctx: *mut zkp_ctx, n_bits: u32, count: u64, n: *const u32, n_stride: u64, m: *const u32, r: *const u32, out_c: *mut u32, flags: u32) -> i32;
     pub fn zkp_paillier_enc_check_batch(ctx: *mut zkp_ctx, n_bits: u32, count: u64, n: *const u32, n_stride: u64, m: *const u32, r: *const u32, mulc_a: *const u32, mulc_b: *const u32, expected: *const u32, out_ok: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_ni_prove_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, w: *const zkp_range_ni_witness, out_e: *mut u8, out_e_len: *mut u8, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_sample_witness_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, seed: *const u8, first_index: u64, out_w1: *mut u32, out_w2: *mut u32, out_r1: *mut u32, out_r2: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_ni_prove_seeded_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, x: *const u32, r: *const u32, seed: *const u8, first_index: u64, out_e: *mut u8, out_e_len: *mut u8, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_ni_verify_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_generate_encrypted_pairs_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, w: *const zkp_range_ni_witness, flags: u32) -> i32;
     pub fn zkp_range_challenge_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_e: *mut u8, out_e_len: *mut u8, flags: u32) -> i32;
@@ -151,6 +153,7 @@ extern "C" {
     pub fn zkp_multi_set_gather(m: *mut zkp_multi, mode: u32) -> i32;
     pub fn zkp_multi_gathered(m: *mut zkp_multi, device_index: u32, which: u32, out_device_ptr: *mut *mut c_void, out_block_stride_bytes: *mut u64, out_bytes: *mut u64) -> i32;
     pub fn zkp_multi_range_ni_prove_batch(m: *mut zkp_multi, p: *const zkp_range_ni_proofs, w: *const zkp_range_ni_witness, out_e: *mut u8, out_e_len: *mut u8, out_status: *mut u8) -> i32;
+    pub fn zkp_multi_range_ni_prove_seeded_batch(m: *mut zkp_multi, p: *const zkp_range_ni_proofs, x: *const u32, r: *const u32, seed: *const u8, first_index: u64, out_e: *mut u8, out_e_len: *mut u8, out_status: *mut u8) -> i32;
     pub fn zkp_multi_range_ni_verify_batch(m: *mut zkp_multi, p: *const zkp_range_ni_proofs, out_verdict: *mut u8) -> i32;
     pub fn zkp_multi_correct_key_ni_verify_batch(m: *mut zkp_multi, n_bits: u32, batch: u64, n: *const u32, sigma: *const u32, salt: *const u8, salt_len: u32, out_verdict: *mut u8) -> i32;
 }

@@ -177,6 +177,39 @@ int32_t zkp_range_ni_prove_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p,
                                  const zkp_range_ni_witness* w, uint8_t* out_e,
                                  uint8_t* out_e_len, uint8_t* out_status, uint32_t flags);
 
+/* ---- seeded proving: RangeProofNi::prove with what the reference's prove takes.
+ * The reference draws w1, w2, a coin, r1 and r2 per row itself (range_proof.rs:133-159).  Here a 32-byte seed is expanded ON THE DEVICE
+ * into that witness, by a published, deterministic function of (seed, proof index, row) — DESIGN.md section 4 has the definition,
+ * tests/seeded_model.py restates it — so sharded or chunked calls are identical to one call and the result can be checked bit for bit:
+ *   ChaCha20 block function of RFC 8439 (20 rounds, 32-bit block counter in state word 12); key = seed as 8 little-endian words;
+ *   nonce words (state 13, 14, 15) = (index & 0xffffffff, index >> 32, row << 2 | field), index = first_index + b for proof b of the
+ *   call, row < error_factor <= 256, field 0 = w, 1 = r1, 2 = r2, 3 = coin.
+ *   sample_below(u) for a field: bits = bit_length(u), nw = ceil(bits / 32), nb = ceil(nw / 16); attempt t = 0, 1, ... takes the first nw
+ *   keystream words of blocks [t nb, (t + 1) nb) as limbs 0 .. nw - 1, clears the bits of the top limb above `bits`, and is accepted when
+ *   the value is < u.  At most 128 attempts (each accepts with probability >= 1/2).
+ *   Per row: third = floor(range / 3); a = third + sample_below(third) (field 0); coin = bit 0 of word 0 of block 0 of field 3;
+ *   (w1, w2) = (a, a - third), swapped when coin = 1; r1 = sample_below(n) (field 1); r2 = sample_below(n) (field 2).
+ * OUR rule for an empty interval — third == 0 (range < 3), likewise n == 0 — and for 128 rejected attempts in a row: that proof's witness is
+ * all zero and its status is ZKP_VERDICT_MALFORMED; the other proofs of the batch are unaffected.  (The reference reaches curv's
+ * BigInt::sample_below(0) there; what that does is recalled as a panic, not pinned by any vector of this repository.)
+ *
+ * SECURITY CONTRACT.  The seed is worth the whole witness: whoever learns it learns x from any Mask response.  A (seed, index) pair must
+ * never be used for two different statements: under one key the commitments (c1, c2), and hence the challenge, repeat only if the
+ * statement does, and two Mask responses over the same w give away x - x'.  Callers draw a fresh seed per call from the operating system
+ * and wipe it afterwards.  `seed` is always a HOST pointer, also under ZKP_F_DEVICE_PTRS. */
+
+/* the witness of rows [0, p->error_factor) of proofs first_index .. first_index + p->batch - 1, expanded from seed[32]; reads p->n, p->range.
+ * Device-pointer calls: the four output arrays are 16-byte aligned. */
+int32_t zkp_range_sample_witness_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, const uint8_t* seed, uint64_t first_index,
+                                       uint32_t* out_w1, uint32_t* out_w2, uint32_t* out_r1, uint32_t* out_r2,   /* [B][EF][kw] */
+                                       uint8_t* out_status /* [B], nullable */, uint32_t flags);
+/* zkp_range_ni_prove_batch with that witness (ZKP_SECURITY_PARAMETER rows), which never leaves the device and is zeroed there — as are the
+ * staged copies of x and r of a host-pointer call — before the call's blocks are given back, on error returns too.  out_status: the status
+ * of zkp_range_ni_prove_batch, with the sampler's MALFORMED cases OR-ed in. */
+int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r,
+                                        const uint8_t* seed, uint64_t first_index,
+                                        uint8_t* out_e, uint8_t* out_e_len, uint8_t* out_status, uint32_t flags);
+
 /* RangeProofNi::verify_self / verify (range_proof_ni.rs:84-128 -> range_proof.rs:254-355).
  * out_verdict [B]: ZKP_VERDICT_*.  (verify()'s two assert_eq! on ek and ciphertext are the
  * host layer's job: here the statement is whatever `p` holds.) */
@@ -419,6 +452,11 @@ int32_t zkp_multi_gathered(zkp_multi* m, uint32_t device_index, uint32_t which, 
                            uint64_t* out_bytes);
 int32_t zkp_multi_range_ni_prove_batch(zkp_multi* m, const zkp_range_ni_proofs* p, const zkp_range_ni_witness* w,
                                        uint8_t* out_e, uint8_t* out_e_len, uint8_t* out_status);
+/* zkp_range_ni_prove_seeded_batch over the contexts: block i passes first_index + lo_i, so the result is byte-identical to one
+ * single-context call.  ZKP_GATHER_HOST only (ZKP_EINVAL in the device-resident gathering modes). */
+int32_t zkp_multi_range_ni_prove_seeded_batch(zkp_multi* m, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r,
+                                              const uint8_t* seed, uint64_t first_index,
+                                              uint8_t* out_e, uint8_t* out_e_len, uint8_t* out_status);
 int32_t zkp_multi_range_ni_verify_batch(zkp_multi* m, const zkp_range_ni_proofs* p, uint8_t* out_verdict);
 int32_t zkp_multi_correct_key_ni_verify_batch(zkp_multi* m, uint32_t n_bits, uint64_t batch, const uint32_t* n,
                                               const uint32_t* sigma, const uint8_t* salt, uint32_t salt_len,

@@ -98,6 +98,12 @@ int32_t zkp_diag_last_fused_hash(zkp_ctx* ctx);
 int32_t zkp_diag_set_key_cache(zkp_ctx* ctx, int32_t on);
 int32_t zkp_diag_key_cache_state(zkp_ctx* ctx, int32_t which, uint32_t* out);
 
+/* Non-zero 32-bit words left in the device blocks that held the secrets of the most recent zkp_range_ni_prove_seeded_batch /
+ * zkp_range_sample_witness_batch call of this ctx: the expanded witness, the seed, and the staged x / r of a host-pointer call.  The blocks
+ * stay in the ctx's staging cache after the call, so this reads memory the library still owns (ZKP_EINVAL once a later call or
+ * zkp_ctx_release_staging has freed them).  0 is the only good answer; 0 as well before the first seeded call. */
+int32_t zkp_diag_witness_residue(zkp_ctx* ctx, uint64_t* out_nonzero_words);
+
 #ifdef __cplusplus
 }
 #endif

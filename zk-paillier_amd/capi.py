@@ -59,6 +59,7 @@ DIAG_EXPORTS = {
     "zkp_diag_last_split": (C.c_int32, [C.c_void_p]),
     "zkp_diag_set_key_cache": (C.c_int32, [C.c_void_p, C.c_int32]),
     "zkp_diag_key_cache_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
+    "zkp_diag_witness_residue": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 ENC_FORM_AUTO, ENC_FORM_N2, ENC_FORM_SHARED, ENC_FORM_ALWAYS = 0, 1, 2, 3
 ENC_FORMS = {"auto": ENC_FORM_AUTO, "n2": ENC_FORM_N2, "shared": ENC_FORM_SHARED, "basen": ENC_FORM_ALWAYS, "always": ENC_FORM_ALWAYS}
@@ -86,6 +87,10 @@ EXPORTS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_range_ni_prove_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.POINTER(RangeNiWitness),
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_sample_witness_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_ni_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_range_ni_verify_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint32]),
     "zkp_range_generate_encrypted_pairs_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.POINTER(RangeNiWitness), C.c_uint32]),
     "zkp_range_challenge_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -134,6 +139,8 @@ EXPORTS = {
     "zkp_multi_set_gather": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "zkp_multi_gathered": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkp_multi_range_ni_prove_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.POINTER(RangeNiWitness), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkp_multi_range_ni_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkp_multi_range_ni_verify_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p]),
     "zkp_multi_correct_key_ni_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
 }
@@ -198,6 +205,16 @@ def ptr(a):
     raise TypeError(type(a))
 
 
+def _seed(seed):
+    """32 seed bytes, or None (the library refuses a null seed)"""
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    return seed
+
+
 class MultiContext:
     """zkp_multi: several device contexts behind one caller (host buffers only)."""
 
@@ -256,6 +273,11 @@ class MultiContext:
 
     def range_ni_prove(self, proofs, wit, out_e=None, out_e_len=None, out_status=None):
         self.check(self.lib.zkp_multi_range_ni_prove_batch(self.h, C.byref(proofs), C.byref(wit), ptr(out_e), ptr(out_e_len), ptr(out_status)))
+
+    def range_ni_prove_seeded(self, proofs, x, r, seed: bytes, first_index: int = 0, out_e=None, out_e_len=None, out_status=None):
+        """zkp_multi_range_ni_prove_seeded_batch: the witness is expanded from the 32-byte seed on each context's GPU"""
+        self.check(self.lib.zkp_multi_range_ni_prove_seeded_batch(self.h, C.byref(proofs), ptr(x), ptr(r), _seed(seed), first_index,
+                                                                  ptr(out_e), ptr(out_e_len), ptr(out_status)))
 
     def range_ni_verify(self, proofs, out_verdict):
         self.check(self.lib.zkp_multi_range_ni_verify_batch(self.h, C.byref(proofs), ptr(out_verdict)))
@@ -432,6 +454,23 @@ class Context:
     def range_ni_prove(self, proofs: RangeNiProofs, wit: RangeNiWitness, out_e, out_e_len, out_status, device: bool):
         self.check(self.lib.zkp_range_ni_prove_batch(self.h, C.byref(proofs), C.byref(wit), ptr(out_e), ptr(out_e_len),
                                                      ptr(out_status), ZKP_F_DEVICE_PTRS if device else 0))
+
+    def range_sample_witness(self, proofs: RangeNiProofs, seed: bytes, first_index: int, out_w1, out_w2, out_r1, out_r2, out_status, device: bool):
+        """zkp_range_sample_witness_batch: rows [0, proofs.error_factor) of the witness a seeded prove uses, expanded from the 32-byte seed
+        (always host bytes) for proofs first_index .. first_index + batch - 1"""
+        self.check(self.lib.zkp_range_sample_witness_batch(self.h, C.byref(proofs), _seed(seed), first_index, ptr(out_w1), ptr(out_w2), ptr(out_r1),
+                                                           ptr(out_r2), ptr(out_status), ZKP_F_DEVICE_PTRS if device else 0))
+
+    def range_ni_prove_seeded(self, proofs: RangeNiProofs, x, r, seed: bytes, first_index: int, out_e, out_e_len, out_status, device: bool):
+        """zkp_range_ni_prove_seeded_batch: RangeProofNi::prove from (statement, x, r) and a fresh 32-byte seed; the witness never leaves the GPU"""
+        self.check(self.lib.zkp_range_ni_prove_seeded_batch(self.h, C.byref(proofs), ptr(x), ptr(r), _seed(seed), first_index, ptr(out_e),
+                                                            ptr(out_e_len), ptr(out_status), ZKP_F_DEVICE_PTRS if device else 0))
+
+    def witness_residue(self) -> int:
+        """non-zero words left in the device blocks that held the last seeded call's secrets (zkp_diag_witness_residue); 0 is the only good answer"""
+        out = C.c_uint64()
+        self.check(self.lib.zkp_diag_witness_residue(self.h, C.byref(out)))
+        return out.value
 
     def range_ni_verify(self, proofs: RangeNiProofs, out_verdict, device: bool):
         self.check(self.lib.zkp_range_ni_verify_batch(self.h, C.byref(proofs), ptr(out_verdict),

@@ -1,0 +1,162 @@
+// kernels_sample.hpp — the witness of RangeProofNi::prove expanded on the device from a 32-byte seed (include/zkp_hip.h:
+// zkp_range_sample_witness_batch; the stream is defined in DESIGN.md section 4 and restated by tests/seeded_model.py).
+//
+// Per row the reference draws w1, w2, a coin, r1 and r2 (range_proof.rs:133-159).  Here every (proof, row, field) has a ChaCha20
+// stream of its own — key = the seed, nonce = (index lo, index hi, row << 2 | field) — and sample_below(u) reads WHOLE blocks per
+// attempt, so lanes compute blocks and attempts independently of one another.
+//
+// Geometry: a group of G = kw / 16 lanes per (proof, row, field); lane l of a group holds words [16 l, 16 l + 16) of the kw-word value,
+// i.e. the keystream block with counter attempt * nb + l.  Consecutive lanes hold consecutive 64-byte pieces of a row, so a group's
+// stores cover the row without gaps.  The comparison `< u` is decided by the most significant lane that differs (two ballots); the
+// carry of third + s crosses the lanes of a group the same way.  Every loop is bounded (max_attempts).
+// Tasks are numbered field-major, so the lanes of a wavefront nearly always work on one field.
+#pragma once
+#include "chacha_dev.hpp"
+
+namespace zkp {
+
+struct RangeSampleArgs {
+  const uint32_t* key;        // the seed as 8 little-endian words (device memory)
+  const uint32_t* n; uint64_t n_stride;
+  const uint32_t* range;      // [B][kw]
+  uint32_t* third;            // [B][kw]  floor(range / 3)         (written by k_range_sample_prep)
+  uint32_t* meta;             // [B][2]   bit_length(third), bit_length(n)
+  uint32_t* w1; uint32_t* w2; uint32_t* r1; uint32_t* r2;   // [B][EF][kw], 16-byte aligned
+  uint8_t* status;            // [B] 0 | ZKP_VERDICT_MALFORMED
+  uint64_t first_index, batch;
+  uint32_t kw, ef, max_attempts;
+};
+
+// one thread per proof: third = floor(range / 3), the bit lengths of both bounds, status = MALFORMED for an empty interval
+// (third == 0, i.e. range < 3 — or n == 0)
+__global__ void __launch_bounds__(256) k_range_sample_prep(RangeSampleArgs a) {
+  const uint64_t b = blockIdx.x * 256ull + threadIdx.x;
+  if (b >= a.batch) return;
+  const uint32_t* q = a.range + b * a.kw;
+  const uint32_t* n = a.n + b * a.n_stride;
+  uint32_t* t = a.third + b * a.kw;
+  uint32_t rem = 0, tbits = 0, nbits = 0;
+  for (int i = (int)a.kw - 1; i >= 0; i--) {
+    const uint64_t cur = ((uint64_t)rem << 32) | q[i];
+    const uint32_t d = (uint32_t)(cur / 3);
+    rem = (uint32_t)(cur - 3ull * d);
+    t[i] = d;
+    if (d && !tbits) tbits = 32u * (uint32_t)i + 32u - (uint32_t)__clz((int)d);
+    const uint32_t nv = n[i];
+    if (nv && !nbits) nbits = 32u * (uint32_t)i + 32u - (uint32_t)__clz((int)nv);
+  }
+  a.meta[2 * b] = tbits;
+  a.meta[2 * b + 1] = nbits;
+  a.status[b] = (tbits == 0 || nbits == 0) ? 2 : 0;
+}
+
+template <int G>
+__global__ void __launch_bounds__(256) k_range_sample(RangeSampleArgs a) {
+  static_assert(G == 2 || G == 4 || G == 8, "kw = 32, 64 or 128 words");
+  constexpr uint64_t GM = (1ull << G) - 1;
+  const uint64_t gid = blockIdx.x * 256ull + threadIdx.x;
+  const uint64_t task = gid / G, rows = a.batch * a.ef;
+  const uint32_t l = (uint32_t)(gid % G);
+  if (task >= 3 * rows) return;                                  // (whole groups leave together: 256 and 64 are multiples of G)
+  const uint32_t f = (uint32_t)(task / rows);                    // 0 = w, 1 = r1, 2 = r2
+  const uint64_t br = task - (uint64_t)f * rows, b = br / a.ef;
+  const uint32_t row = (uint32_t)(br - b * a.ef);
+  const uint32_t tbits = a.meta[2 * b], nbits = a.meta[2 * b + 1];
+  if (tbits == 0 || nbits == 0) return;                          // an empty interval: k_range_sample_fixup zeroes the proof's rows
+  const uint32_t g0 = (threadIdx.x & 63u) - l;                   // the group's first bit in a ballot
+  const uint32_t bits = f ? nbits : tbits, nw = (bits + 31) / 32, nb = (nw + 15) / 16;
+  const uint32_t topmask = (bits & 31u) ? (1u << (bits & 31u)) - 1u : 0xffffffffu;
+  const uint32_t* u = f ? a.n + b * a.n_stride : a.third + b * a.kw;
+  uint32_t uw[16], key[8], v[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) { const uint32_t wi = 16 * l + i; uw[i] = wi < nw ? u[wi] : 0u; v[i] = 0u; }
+#pragma unroll
+  for (int i = 0; i < 8; i++) key[i] = a.key[i];
+  const uint64_t index = a.first_index + b;
+  const uint32_t n0 = (uint32_t)index, n1 = (uint32_t)(index >> 32), n2 = (row << 2) | f;
+
+  bool active = true, ok = false;
+  for (uint32_t t = 0; t < a.max_attempts; t++) {
+    int c = 0;
+    if (active) {
+      if (l < nb) {
+        chacha20_block(key, t * nb + l, n0, n1, n2, v);
+#pragma unroll
+        for (int i = 0; i < 16; i++) { const uint32_t wi = 16 * l + i; if (wi >= nw) v[i] = 0u; else if (wi == nw - 1) v[i] &= topmask; }
+      }
+#pragma unroll
+      for (int i = 15; i >= 0; i--) if (c == 0 && v[i] != uw[i]) c = v[i] < uw[i] ? -1 : 1;
+    }
+    const uint64_t ne = __ballot(active && c != 0), lt = __ballot(active && c < 0);
+    if (active) {
+      const uint32_t m = (uint32_t)((ne >> g0) & GM);
+      if (m) ok = ((lt >> (g0 + (31u - (uint32_t)__clz((int)m)))) & 1ull) != 0;      // the most significant lane that differs decides
+      if (ok) active = false;
+    }
+    if (__ballot(active) == 0) break;
+  }
+  if (!ok) {                     // max_attempts rejections in a row (probability <= 2^-max_attempts): the whole proof is zeroed by k_range_sample_fixup
+    if (l == 0) a.status[b] = 2;
+    return;
+  }
+  const uint64_t off = br * a.kw + 16 * l;
+  if (f) {
+    uint4* o = (uint4*)((f == 1 ? a.r1 : a.r2) + off);
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+    return;
+  }
+  // field 0: a = third + s with s = v < third; the carry crosses the lanes of the group (generate / propagate masks, one addition)
+  uint32_t sum[16], carry = 0;
+  bool all_ones = true;
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const uint64_t x = (uint64_t)v[i] + uw[i] + carry;
+    sum[i] = (uint32_t)x; carry = (uint32_t)(x >> 32);
+    all_ones = all_ones && sum[i] == 0xffffffffu;
+  }
+  const uint64_t gen = (__ballot(carry != 0) >> g0) & GM, prop = (__ballot(all_ones) >> g0) & GM;
+  uint32_t cin = (uint32_t)(((((gen << 1) + prop) ^ prop) >> l) & 1ull);
+#pragma unroll
+  for (int i = 0; i < 16; i++) { sum[i] += cin; cin = (cin && sum[i] == 0u) ? 1u : 0u; }
+  uint32_t cs[16];
+  chacha20_block(key, 0u, n0, n1, (row << 2) | 3u, cs);
+  const bool coin = (cs[0] & 1u) != 0;                           // (w1, w2) = (a, a - third), swapped when the coin is 1
+  uint4* o1 = (uint4*)(a.w1 + off);
+  uint4* o2 = (uint4*)(a.w2 + off);
+  uint32_t first[16], second[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) { first[i] = coin ? v[i] : sum[i]; second[i] = coin ? sum[i] : v[i]; }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    o1[i] = make_uint4(first[4 * i], first[4 * i + 1], first[4 * i + 2], first[4 * i + 3]);
+    o2[i] = make_uint4(second[4 * i], second[4 * i + 1], second[4 * i + 2], second[4 * i + 3]);
+  }
+}
+
+// 16 words per thread: the four rows of every (proof, row) whose proof is MALFORMED become zero
+template <int G>
+__global__ void __launch_bounds__(256) k_range_sample_fixup(RangeSampleArgs a) {
+  const uint64_t gid = blockIdx.x * 256ull + threadIdx.x, br = gid / G;
+  if (br >= a.batch * a.ef || a.status[br / a.ef] == 0) return;
+  const uint64_t off = br * a.kw + 16 * (gid % G);
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  uint32_t* const arrays[4] = {a.w1, a.w2, a.r1, a.r2};
+  for (int k = 0; k < 4; k++)
+    for (int i = 0; i < 4; i++) ((uint4*)(arrays[k] + off))[i] = z;
+}
+
+// non-zero words of a device region (zkp_diag_witness_residue)
+__global__ void __launch_bounds__(256) k_count_nonzero(const uint32_t* p, uint64_t words, unsigned long long* out) {
+  unsigned long long mine = 0;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < words; i += (uint64_t)gridDim.x * 256ull) mine += p[i] != 0u;
+  if (mine) atomicAdd(out, mine);
+}
+
+// status[b] |= extra[b]
+__global__ void __launch_bounds__(256) k_or_bytes(uint8_t* status, const uint8_t* extra, uint64_t count) {
+  const uint64_t b = blockIdx.x * 256ull + threadIdx.x;
+  if (b < count && extra[b]) status[b] |= extra[b];
+}
+
+}  // namespace zkp

@@ -21,6 +21,7 @@
 #include "kernels_proofs.hpp"
 #include "kernels_inv.hpp"
 #include "kernels_serde.hpp"
+#include "kernels_sample.hpp"
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
 #include "kernels_basen.hpp"
@@ -51,6 +52,9 @@ struct StageBlock { void* p; size_t cap; };
 
 struct zkp_ctx {
   std::vector<StageBlock> stage_free;
+  // the regions of staging blocks that held the secrets of the most recent seeded prove / sample call (expanded witness, seed, staged x / r):
+  // zeroed on the stream before the blocks went back to the cache above (Stage::wipe_now); zkp_diag_witness_residue reads them
+  std::vector<std::pair<void*, size_t>> last_wiped;
   uint32_t* setup_flag = nullptr;      // device word: k_setup ORs the status of every modulus it rejects into it
   uint32_t* setup_flag_host = nullptr; // its pinned host mirror
   int device = 0;
@@ -304,6 +308,9 @@ struct Stage {
   std::vector<StageBlock> owned;
   struct Out { void* d; void* h; size_t n; };
   std::vector<Out> outs;
+  // regions of blocks of this call that hold secrets (zkp_range_ni_prove_seeded_batch): zeroed on the ctx stream behind the call's last
+  // kernel and copy, before the blocks return to the cache — on every path out of the call, the destructor's included
+  std::vector<std::pair<void*, size_t>> wipe;
   int32_t st = ZKP_OK;
   Stage(zkp_ctx* c_, uint32_t flags) : c(c_), dev((flags & ZKP_F_DEVICE_PTRS) != 0) {}
   Stage(const Stage&) = delete;
@@ -311,8 +318,16 @@ struct Stage {
   ~Stage() {                       // an error return that skipped finish(): nothing is copied back, the blocks go back to the ctx
     join_side();
     if (owned.empty()) return;
+    wipe_now();
     (void)hipStreamSynchronize(c->stream);
     give_back();
+  }
+  void secret(const void* p, size_t bytes) { if (p && bytes) wipe.push_back({(void*)p, bytes}); }
+  void wipe_now() {
+    if (wipe.empty()) return;
+    for (auto& w : wipe) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);
+    c->last_wiped.swap(wipe);
+    wipe.clear();
   }
   // An error return between the fork onto the ctx's second stream and the join: the kernels there may still read the staging
   // blocks and the ctx scratch that the next call reuses — wait for them before anything is handed back.
@@ -379,6 +394,7 @@ struct Stage {
     for (auto& o : outs)
       if (!st && hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "D2H copy"; }
     join_side();
+    wipe_now();
     if (!dev || st) { if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; } }
     give_back();
     outs.clear();
@@ -948,6 +964,7 @@ extern "C" int32_t zkp_ctx_release_staging(zkp_ctx* c) try {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (auto& b : c->stage_free) (void)hipFree(b.p);
   c->stage_free.clear();
+  c->last_wiped.clear();
   // the base-n form's per-launch areas (window tables of pairs: 1.4 GB under one key, 2.5 GB under per-proof keys; raw pairs; Mask-row
   // products) are sized by the largest launch so far and rebuilt on demand
   for (DevBuf* b : {&c->bn_table, &c->bn_raw, &c->bn_expected}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }

@@ -465,6 +465,26 @@ extern "C" int32_t zkp_multi_range_ni_prove_batch(zkp_multi* m, const zkp_range_
   });
 } ZKP_CATCH(nullptr)
 
+// zkp_range_ni_prove_seeded_batch over the contexts: block i expands the witness of ITS proof indices (first_index + lo), so the bytes are
+// those of one single-context call.  The per-GPU D2H reassembly only (ZKP_GATHER_HOST).
+extern "C" int32_t zkp_multi_range_ni_prove_seeded_batch(zkp_multi* m, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r,
+                                                         const uint8_t* seed, uint64_t first_index, uint8_t* out_e, uint8_t* out_e_len,
+                                                         uint8_t* out_status) try {
+  if (!m) return ZKP_EINVAL;
+  if (!p || !seed) { m->err = "zkp_multi_range_ni_prove_seeded_batch: invalid argument"; return ZKP_EINVAL; }
+  if (m->gather != ZKP_GATHER_HOST) { m->err = "zkp_multi_range_ni_prove_seeded_batch: ZKP_GATHER_HOST only"; return ZKP_EINVAL; }
+  if (p->batch == 0) return ZKP_OK;
+  const uint64_t kw = p->n_bits / 32, EF = ZKP_SECURITY_PARAMETER;
+  return multi_run(m, p->batch, [&](zkp_ctx* c, uint64_t lo, uint64_t hi) {
+    zkp_range_ni_proofs s = *p;
+    s.error_factor = (uint32_t)EF;            // prove always writes ZKP_SECURITY_PARAMETER rows: slice with that row count
+    s = range_slice(s, lo, hi);
+    s.error_factor = p->error_factor;
+    return zkp_range_ni_prove_seeded_batch(c, &s, x ? x + lo * kw : nullptr, r ? r + lo * kw : nullptr, seed, first_index + lo,
+                                           out_e ? out_e + lo * 32 : nullptr, out_e_len ? out_e_len + lo : nullptr, out_status ? out_status + lo : nullptr, 0);
+  });
+} ZKP_CATCH(nullptr)
+
 extern "C" int32_t zkp_multi_correct_key_ni_verify_batch(zkp_multi* m, uint32_t n_bits, uint64_t batch, const uint32_t* n, const uint32_t* sigma,
                                                          const uint8_t* salt, uint32_t salt_len, uint8_t* out_verdict) try {
   if (!m) return ZKP_EINVAL;

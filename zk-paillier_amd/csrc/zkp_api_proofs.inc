@@ -351,6 +351,139 @@ extern "C" int32_t zkp_range_ni_prove_batch(zkp_ctx* c, const zkp_range_ni_proof
   ZKP_ROUTE_ENC(c, p ? p->batch * 2 * ZKP_SECURITY_PARAMETER : 0, p ? 2 * p->n_bits : 0, p && p->n_stride == 0, zkp_range_ni_prove_batch, p, w, out_e, out_e_len, out_status, flags)
   return range_prove_entry(c, "zkp_range_ni_prove_batch", p, w, ZKP_SECURITY_PARAMETER, 3, nullptr, nullptr, out_e, out_e_len, out_status, flags);
 } ZKP_CATCH(c)
+// ---- seeded proving: the witness expanded on the device (kernels_sample.hpp) -----------------------------------------------------------
+enum { S_SAMPLE_THIRD = 44, S_SAMPLE_META = 45, S_SAMPLE_STATUS = 46, S_RESIDUE = 47 };
+enum { RANGE_SAMPLE_MAX_ATTEMPTS = 128 };
+
+// every pointer is device memory; `d` supplies n_bits, batch, n, n_stride and range; status is written for every proof
+static int32_t range_sample_launch(zkp_ctx* c, const zkp_range_ni_proofs& d, uint32_t ef, const uint32_t* key, uint64_t first_index,
+                                   uint32_t* w1, uint32_t* w2, uint32_t* r1, uint32_t* r2, uint8_t* status) {
+  const uint32_t kw = d.n_bits / 32;
+  const uint64_t B = d.batch, rows = B * ef;
+  int32_t st;
+  if ((st = ensure(c, c->scratch[S_SAMPLE_THIRD], B * kw * 4))) return st;
+  if ((st = ensure(c, c->scratch[S_SAMPLE_META], B * 8))) return st;
+  RangeSampleArgs a{};
+  a.key = key; a.n = d.n; a.n_stride = d.n_stride; a.range = d.range;
+  a.third = (uint32_t*)c->scratch[S_SAMPLE_THIRD].p; a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p;
+  a.w1 = w1; a.w2 = w2; a.r1 = r1; a.r2 = r2; a.status = status;
+  a.first_index = first_index; a.batch = B; a.kw = kw; a.ef = ef; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
+  hipLaunchKernelGGL(k_range_sample_prep, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (rows == 0) return ZKP_OK;
+  const uint64_t G = kw / 16;
+  const unsigned sample_blocks = (unsigned)((3 * rows * G + 255) / 256), fix_blocks = (unsigned)((rows * G + 255) / 256);
+  switch (G) {
+    case 2: hipLaunchKernelGGL(k_range_sample<2>, dim3(sample_blocks), dim3(256), 0, c->stream, a);
+            hipLaunchKernelGGL(k_range_sample_fixup<2>, dim3(fix_blocks), dim3(256), 0, c->stream, a); break;
+    case 4: hipLaunchKernelGGL(k_range_sample<4>, dim3(sample_blocks), dim3(256), 0, c->stream, a);
+            hipLaunchKernelGGL(k_range_sample_fixup<4>, dim3(fix_blocks), dim3(256), 0, c->stream, a); break;
+    default: hipLaunchKernelGGL(k_range_sample<8>, dim3(sample_blocks), dim3(256), 0, c->stream, a);
+             hipLaunchKernelGGL(k_range_sample_fixup<8>, dim3(fix_blocks), dim3(256), 0, c->stream, a); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+
+extern "C" int32_t zkp_range_sample_witness_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint8_t* seed, uint64_t first_index,
+                                                  uint32_t* out_w1, uint32_t* out_w2, uint32_t* out_r1, uint32_t* out_r2, uint8_t* out_status,
+                                                  uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (!range_args_ok(p, RA_RANGE) || !seed || (p->batch && p->error_factor && (!out_w1 || !out_w2 || !out_r1 || !out_r2))) {
+    c->err = "zkp_range_sample_witness_batch: invalid argument"; return ZKP_EINVAL;
+  }
+  if ((flags & ZKP_F_DEVICE_PTRS) && ((((uintptr_t)out_w1 | (uintptr_t)out_w2 | (uintptr_t)out_r1 | (uintptr_t)out_r2) & 15u) != 0)) {
+    c->err = "zkp_range_sample_witness_batch: device output arrays must be 16-byte aligned"; return ZKP_EINVAL;
+  }
+  if (p->batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = p->n_bits / 32, B = p->batch, rows = B * p->error_factor;
+  Stage s(c, flags);
+  zkp_range_ni_proofs d = *p;
+  d.n = s.in(p->n, p->n_stride ? B * kw : kw);
+  d.range = s.in(p->range, B * kw);
+  const uint32_t* key = (const uint32_t*)s.host_in(seed, 32);
+  s.secret(key, 32);
+  uint32_t* w[4] = {out_w1, out_w2, out_r1, out_r2};
+  for (auto& q : w) { q = s.out(q, rows * kw); if (!s.dev) s.secret(q, rows * kw * 4); }      // (host arrays: the staged copies are wiped behind the D2H)
+  uint8_t* ds = s.out(out_status, B);
+  int32_t st = s.st;
+  if (!st && !ds) { st = ensure(c, c->scratch[S_SAMPLE_STATUS], B); ds = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p; }
+  if (!st) st = range_sample_launch(c, d, p->error_factor, key, first_index, w[0], w[1], w[2], w[3], ds);
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r, const uint8_t* seed,
+                                                   uint64_t first_index, uint8_t* out_e, uint8_t* out_e_len, uint8_t* out_status, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (!range_args_ok(p, RA_PAIRS | RA_RANGE | RA_RESP) || !seed) { c->err = "zkp_range_ni_prove_seeded_batch: invalid argument"; return ZKP_EINVAL; }
+  if (p->batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = p->n_bits / 32, B = p->batch, EF = ZKP_SECURITY_PARAMETER, rows = B * EF;
+  // Everything is made device-resident HERE (a host-pointer call stages its statement, x, r and outputs in blocks of this ctx), the sampler
+  // fills four more blocks, and zkp_range_ni_prove_batch runs as the device-pointer call it already knows: routing, split plans, the key
+  // cache and the kernels are those of that entry point.  `s` wipes what is secret on every path out (Stage::secret).
+  Stage s(c, flags);
+  zkp_range_ni_proofs d = *p;
+  d.n = s.in(p->n, p->n_stride ? B * kw : kw);
+  d.range = s.in(p->range, B * kw);
+  if (!s.dev) d.ciphertext = nullptr;                  // (no prover function reads it)
+  d.c1 = s.out(p->c1, rows * 2 * kw); d.c2 = s.out(p->c2, rows * 2 * kw);
+  d.resp_kind = s.out(p->resp_kind, rows); d.resp_j = s.out(p->resp_j, rows);
+  d.resp_w1 = s.out(p->resp_w1, rows * kw); d.resp_r1 = s.out(p->resp_r1, rows * kw);
+  d.resp_w2 = s.out(p->resp_w2, rows * kw); d.resp_r2 = s.out(p->resp_r2, rows * kw);
+  const uint32_t* key = (const uint32_t*)s.host_in(seed, 32);
+  s.secret(key, 32);
+  zkp_range_ni_witness dw{};
+  uint32_t* wit[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (auto& q : wit) { q = s.st ? nullptr : (uint32_t*)s.take(rows * kw * 4); s.secret(q, rows * kw * 4); }
+  dw.w1 = wit[0]; dw.w2 = wit[1]; dw.r1 = wit[2]; dw.r2 = wit[3];
+  dw.x = s.in(x, B * kw); dw.r = s.in(r, B * kw);
+  if (!s.dev) { s.secret(dw.x, B * kw * 4); s.secret(dw.r, B * kw * 4); }
+  uint8_t* de = s.out(out_e, B * 32);
+  uint8_t* dl = s.out(out_e_len, B);
+  uint8_t* ds = s.out(out_status, B);
+  int32_t st = s.st;
+  if (!st) st = ensure(c, c->scratch[S_SAMPLE_STATUS], B);
+  uint8_t* sampler_status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p;
+  if (!st) st = range_sample_launch(c, d, (uint32_t)EF, key, first_index, wit[0], wit[1], wit[2], wit[3], sampler_status);
+  if (!st) st = zkp_range_ni_prove_batch(c, &d, &dw, de, dl, ds, ZKP_F_DEVICE_PTRS);      // (a null x or r is refused there: ZKP_EINVAL, after the sampler ran)
+  if (!st && ds) {
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_or_bytes, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, ds, (const uint8_t*)sampler_status, (uint64_t)B);
+    HIPCHK(c, hipGetLastError());
+  }
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_diag_witness_residue(zkp_ctx* c, uint64_t* out_nonzero_words) try {
+  if (!c || !out_nonzero_words) return ZKP_EINVAL;
+  *out_nonzero_words = 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->last_wiped.empty()) return ZKP_OK;
+  int32_t st = ensure(c, c->scratch[S_RESIDUE], 8);
+  if (st) return st;
+  unsigned long long* count = (unsigned long long*)c->scratch[S_RESIDUE].p;
+  HIPCHK(c, hipMemsetAsync(count, 0, 8, c->stream));
+  for (auto& w : c->last_wiped) {
+    bool cached = false;                                // only memory the ctx still owns is read
+    for (auto& b : c->stage_free) cached = cached || ((char*)w.first >= (char*)b.p && (char*)w.first + w.second <= (char*)b.p + b.cap);
+    if (!cached) { c->err = "zkp_diag_witness_residue: the blocks of the last seeded call have left the staging cache"; return ZKP_EINVAL; }
+    const uint64_t words = w.second / 4;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((words + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_count_nonzero, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t*)w.first, words, count);
+    HIPCHK(c, hipGetLastError());
+  }
+  unsigned long long host = 0;
+  HIPCHK(c, hipMemcpyAsync(&host, count, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *out_nonzero_words = host;
+  return ZKP_OK;
+} ZKP_CATCH(c)
+
 extern "C" int32_t zkp_range_generate_encrypted_pairs_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const zkp_range_ni_witness* w, uint32_t flags) try {
   ZKP_ROUTE_ENC(c, p ? p->batch * 2 * p->error_factor : 0, p ? 2 * p->n_bits : 0, p && p->n_stride == 0, zkp_range_generate_encrypted_pairs_batch, p, w, flags)
   return range_prove_entry(c, "zkp_range_generate_encrypted_pairs_batch", p, w, p ? p->error_factor : 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, flags);

@@ -293,13 +293,26 @@ class RangeProofNi {
     std::vector<uint8_t> status;
     void wipe_secrets() { for (RawBuf<uint32_t>* b : {&x, &r, &w1, &w2, &r1, &r2}) b->wipe_now(); }
     bool large() const { return c1.pooled(); }
-    ProveChunk(size_t lo_, size_t hi_, size_t kw, size_t EF)
-        : lo(lo_), hi(hi_), range((hi_ - lo_) * kw), ct((hi_ - lo_) * 2 * kw), x((hi_ - lo_) * kw, true), r((hi_ - lo_) * kw, true), w1((hi_ - lo_) * EF * kw, true),
-          w2((hi_ - lo_) * EF * kw, true), r1((hi_ - lo_) * EF * kw, true), r2((hi_ - lo_) * EF * kw, true) /* witnesses and nonces: wiped on release */, c1((hi_ - lo_) * EF * 2 * kw), c2((hi_ - lo_) * EF * 2 * kw), rw1((hi_ - lo_) * EF * kw), rr1((hi_ - lo_) * EF * kw),
+    // witness = false (prove_batch_seeded): the GPU expands w1, w2, r1, r2 itself, there are no host buffers for them
+    ProveChunk(size_t lo_, size_t hi_, size_t kw, size_t EF, bool witness = true)
+        : lo(lo_), hi(hi_), range((hi_ - lo_) * kw), ct((hi_ - lo_) * 2 * kw), x((hi_ - lo_) * kw, true), r((hi_ - lo_) * kw, true), w1(witness ? (hi_ - lo_) * EF * kw : 0, true),
+          w2(witness ? (hi_ - lo_) * EF * kw : 0, true), r1(witness ? (hi_ - lo_) * EF * kw : 0, true), r2(witness ? (hi_ - lo_) * EF * kw : 0, true) /* witnesses and nonces: wiped on release */, c1((hi_ - lo_) * EF * 2 * kw), c2((hi_ - lo_) * EF * 2 * kw), rw1((hi_ - lo_) * EF * kw), rr1((hi_ - lo_) * EF * kw),
           rw2((hi_ - lo_) * EF * kw), rr2((hi_ - lo_) * EF * kw), kind((hi_ - lo_) * EF), jj((hi_ - lo_) * EF), status(hi_ - lo_) {}
   };
-  static std::vector<RangeProofNi> prove_batch(const EncryptionKey& ek, const std::vector<Statement>& st) {
+  static std::vector<RangeProofNi> prove_batch(const EncryptionKey& ek, const std::vector<Statement>& st) { return prove_batch_impl(ek, st, false); }
+  // The same from what the reference's prove takes — statement and secret, nothing else: a fresh 32-byte seed from the operating system per
+  // call, expanded into (w1, w2, r1, r2) ON THE GPU (zkp_range_ni_prove_seeded_batch; the stream is defined in include/zkp_hip.h).  No
+  // witness is sampled, flattened, uploaded or kept on the host: HostTiming.sample_flatten_ms covers the flattening of the statements only.
+  // Chunks of a ZKP_HOST_PIPELINE call share the seed; chunk [lo, hi) passes first_index = lo, so the proofs are those of one call.
+  static std::vector<RangeProofNi> prove_batch_seeded(const EncryptionKey& ek, const std::vector<Statement>& st) { return prove_batch_impl(ek, st, true); }
+  struct SeedGuard {      // the seed is worth the whole witness: wiped on every path out of the call
+    uint8_t bytes[32];
+    explicit SeedGuard(bool draw) { if (draw) detail::ChaChaRng::os_random(bytes, sizeof bytes); else std::memset(bytes, 0, sizeof bytes); }
+    ~SeedGuard() { detail::ChaChaRng::wipe(bytes, sizeof bytes); }
+  };
+  static std::vector<RangeProofNi> prove_batch_impl(const EncryptionKey& ek, const std::vector<Statement>& st, bool seeded) {
     Engine& e = Engine::instance();
+    SeedGuard seed(seeded);
     const uint32_t nb = width_for(ek.n), kw = nb / 32;
     const size_t B = st.size(), EF = SECURITY_PARAMETER;
     RawBuf<uint32_t> n(kw);
@@ -315,6 +328,7 @@ class RangeProofNi {
         const size_t b = c.lo + k;
         st[b].range.to_limbs(&c.range[k * kw], kw); st[b].ciphertext.to_limbs(&c.ct[k * 2 * kw], 2 * kw);
         st[b].secret_x.to_limbs(&c.x[k * kw], kw); st[b].secret_r.to_limbs(&c.r[k * kw], kw);
+        if (seeded) return;
         const BigInt third = st[b].range.div_floor(BigInt(3)), two_thirds = BigInt(2) * third;   // range_proof.rs:133-134
         for (size_t i = 0; i < EF; i++) {
           BigInt a = BigInt::sample_range(third, two_thirds), cc = a - third;                     // :136-141
@@ -329,6 +343,10 @@ class RangeProofNi {
     auto gpu = [&](ProveChunk& c) {
       zkp_range_ni_proofs p{nb, (uint32_t)EF, c.hi - c.lo, 0, n.data(), c.range.data(), c.ct.data(), c.c1.data(), c.c2.data(), c.kind.data(), c.jj.data(),
                             c.rw1.data(), c.rr1.data(), c.rw2.data(), c.rr2.data()};
+      if (seeded) {
+        e.check(zkp_range_ni_prove_seeded_batch(e.ctx(), &p, c.x.data(), c.r.data(), seed.bytes, c.lo, nullptr, nullptr, c.status.data(), 0), "zkp_range_ni_prove_seeded_batch");
+        return;
+      }
       zkp_range_ni_witness w{c.x.data(), c.r.data(), c.w1.data(), c.w2.data(), c.r1.data(), c.r2.data()};
       e.check(zkp_range_ni_prove_batch(e.ctx(), &p, &w, nullptr, nullptr, c.status.data(), 0), "zkp_range_ni_prove_batch");
     };
@@ -376,7 +394,7 @@ class RangeProofNi {
     std::vector<std::unique_ptr<ProveChunk>> ch(chunks);
     auto bounds = [&](size_t k) { return std::make_pair(B * k / chunks, B * (k + 1) / chunks); };
     StopWatch sw;
-    ch[0].reset(new ProveChunk(bounds(0).first, bounds(0).second, kw, EF));
+    ch[0].reset(new ProveChunk(bounds(0).first, bounds(0).second, kw, EF, !seeded));
     sample_flatten(*ch[0], ~0u);
     tm.sample_flatten_ms = sw.lap();
     for (size_t k = 0; k < chunks; k++) {
@@ -386,7 +404,7 @@ class RangeProofNi {
           const unsigned few = std::max(1u, std::min(4u, host_threads() / 2));
           prealloc(*ch[k], few);                    // the objects this call's outputs will go to
           if (k + 1 < chunks) {                     // next chunk's inputs, on a few threads: the GPU call only waits
-            ch[k + 1].reset(new ProveChunk(bounds(k + 1).first, bounds(k + 1).second, kw, EF));
+            ch[k + 1].reset(new ProveChunk(bounds(k + 1).first, bounds(k + 1).second, kw, EF, !seeded));
             sample_flatten(*ch[k + 1], std::max(1u, host_threads() / 2));
           }
           if (k > 0) { fill(*ch[k - 1], std::max(1u, host_threads() / 2)); ch[k - 1].reset(); }
