@@ -440,6 +440,43 @@ pub fn range_ni_verify_batch(ek: &EncryptionKey, proofs: &[&RangeProofNi]) -> Op
     )
 }
 
+/// `serde_json::to_string(proof)` for many proofs under one key: radix conversion, sizing and assembly of the documents run on the GPU
+/// (`zkp_json_write_range_proof_ni_batch`), the text comes back finished.  `key_form` / `bare_form`: `sys::ZKP_BIGINT_DEC` / `_HEX` /
+/// `_BYTES`, the text forms of `ek.n` and of `range` / `ciphertext` in this build of curv and kzen-paillier.  `None` when the GPU cannot
+/// take the batch (another key, a value the fixed width cannot carry, no device): the caller then writes with serde.
+pub fn to_json_batch(ek: &EncryptionKey, proofs: &[&RangeProofNi], key_form: u32, bare_form: u32) -> Option<Vec<String>> {
+    let n_bits = width_for(&ek.n)?;
+    if proofs.is_empty() {
+        return Some(Vec::new());
+    }
+    let ef = proofs[0].error_factor;
+    if ef == 0 || ef > 256 {
+        return None;
+    }
+    let mut batch = RangeBatch::new(n_bits, proofs.len(), ef);
+    if !put_limbs(&mut batch.n, &ek.n) {
+        return None;
+    }
+    for (k, p) in proofs.iter().enumerate() {
+        if p.ek.n != ek.n || !batch.fill(k, p) {
+            return None;
+        }
+    }
+    let raw = batch.raw();
+    let forms = (key_form << 4) | bare_form;
+    let mut off = vec![0u64; proofs.len() + 1];
+    // the sizing call, one allocation, the writing call
+    with_ctx(|ctx| ok(unsafe { sys::zkp_json_write_range_proof_ni_batch(ctx, &raw, forms, ptr::null_mut(), 0, off.as_mut_ptr(), ptr::null_mut(), 0) }))?;
+    let mut text = vec![0u8; off[proofs.len()] as usize];
+    let cap = text.len() as u64;
+    with_ctx(|ctx| ok(unsafe { sys::zkp_json_write_range_proof_ni_batch(ctx, &raw, forms, text.as_mut_ptr() as *mut std::os::raw::c_char, cap, off.as_mut_ptr(), ptr::null_mut(), 0) }))?;
+    let mut docs = Vec::with_capacity(proofs.len());
+    for k in 0..proofs.len() {
+        docs.push(String::from_utf8(text[off[k] as usize..off[k + 1] as usize].to_vec()).ok()?);
+    }
+    Some(docs)
+}
+
 impl RangeProofNi {
     /// Many provers, one key, one GPU launch sequence.  Falls back to `RangeProofNi::prove` per statement (whose own dispatch ends
     /// in the original GMP body) when the GPU cannot take the batch.

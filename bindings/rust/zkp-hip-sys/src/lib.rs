@@ -36,6 +36,10 @@ pub const ZKP_DOC_HOST_PATH: u8 = 3;
 pub const ZKP_BIGINT_DEC: u32 = 0;
 pub const ZKP_BIGINT_HEX: u32 = 1;
 pub const ZKP_BIGINT_BYTES: u32 = 2;
+pub const ZKP_JSON_DOC_ENCRYPTED_PAIRS: u32 = 0;
+pub const ZKP_JSON_DOC_RANGE_PROOF: u32 = 1;
+pub const ZKP_JSON_DOC_RANGE_PROOF_NI: u32 = 2;
+pub const ZKP_JSON_DOC_CORRECT_KEY_PROOF: u32 = 3;
 pub const ZKP_GATHER_HOST: u32 = 0;
 pub const ZKP_GATHER_RCCL: u32 = 1;
 pub const ZKP_GATHER_COPY: u32 = 2;
@@ -143,6 +147,11 @@ extern "C" {
     pub fn zkp_json_range_proof_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, p: *const zkp_range_ni_proofs, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_range_proof_ni_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, bigint_forms: u32, p: *const zkp_range_ni_proofs, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_correct_key_proof_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, n_bits: u32, batch: u64, out_sigma: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_doc_bound(doc_kind: u32, n_bits: u32, error_factor: u32, bigint_forms: u32) -> u64;
+    pub fn zkp_json_write_encrypted_pairs_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_write_range_proof_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_write_range_proof_ni_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, bigint_forms: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_write_correct_key_proof_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, sigma: *const u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_multi_create(device_ids: *const i32, n_devices: u32, out: *mut *mut zkp_multi) -> i32;
     pub fn zkp_multi_destroy(m: *mut zkp_multi) -> i32;
     pub fn zkp_multi_size(m: *mut zkp_multi) -> u32;

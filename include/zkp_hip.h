@@ -410,6 +410,38 @@ int32_t zkp_json_range_proof_ni_batch(zkp_ctx* ctx, const char* text, const uint
 int32_t zkp_json_correct_key_proof_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
                                          uint64_t batch, uint32_t* out_sigma, uint8_t* out_status, uint32_t flags);
 
+/* The SoA batch -> serde_json documents: the mirror images of the four readers.  The text is byte for byte what serde_json::to_string
+ * gives for the reference's derives: compact, fields in declaration order, every annotated BigInt a decimal string as mpz_get_str writes
+ * it (no leading zeros, "0" for zero), `j` and `error_factor` bare numbers; ek.n, range and ciphertext in the forms `bigint_forms`
+ * names, exactly as the reader understands them (hex: lower case, two characters per byte of the big-endian magnitude, "00" for zero).
+ * Radix conversion, sizing and assembly all run on the GPU; only finished text leaves it.
+ *   Documents lie back to back in out_text, no separator, no terminator: document b is [out_doc_off[b], out_doc_off[b + 1]);
+ *   out_doc_off has batch + 1 entries (4096 proofs under a 2048-bit key are more than 2^31 bytes: everything here is 64 bits wide).
+ *   out_text == NULL: the sizing call — only the exact offsets are computed.  text_cap < out_doc_off[batch]: ZKP_EINVAL, the offsets
+ *   are written, the error string names both numbers, no byte of out_text is touched.  zkp_json_doc_bound (a pure host function, no
+ *   device needed): an upper bound of one document's length, so that batch * bound can be allocated once and the sizing call skipped;
+ *   0 for arguments no writer accepts.  doc_kind: ZKP_JSON_DOC_*; error_factor is ignored for a NiCorrectKeyProof, bigint_forms for
+ *   everything but a RangeProofNi.
+ *   out_status [batch] (nullable): ZKP_DOC_OK, or ZKP_DOC_INVALID where a row of proof b has a resp_kind that is neither ZKP_RESP_OPEN nor
+ *   ZKP_RESP_MASK: no Response has that variant, the document is empty (out_doc_off[b + 1] == out_doc_off[b]), the others are unaffected.
+ *   resp_j is written as the byte it is.  Reads c1, c2 (pairs); resp_* (proof); every field (RangeProofNi: n_stride == 0 writes the
+ *   shared key into every document).  n_bits in {1024, 2048, 4096}, error_factor 1 .. 256, batch 0 .. 2^24.
+ *   ZKP_F_DEVICE_PTRS applies to the p-> arrays, sigma and out_status — a batch is consumed as zkp_range_ni_prove_batch /
+ *   zkp_range_ni_prove_seeded_batch left it, no limb travels to the host; out_text and out_doc_off are host memory. */
+#define ZKP_JSON_DOC_ENCRYPTED_PAIRS 0u
+#define ZKP_JSON_DOC_RANGE_PROOF 1u
+#define ZKP_JSON_DOC_RANGE_PROOF_NI 2u
+#define ZKP_JSON_DOC_CORRECT_KEY_PROOF 3u
+uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms);
+int32_t zkp_json_write_encrypted_pairs_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
+                                             uint8_t* out_status, uint32_t flags);
+int32_t zkp_json_write_range_proof_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
+                                         uint8_t* out_status, uint32_t flags);
+int32_t zkp_json_write_range_proof_ni_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, uint32_t bigint_forms, char* out_text, uint64_t text_cap,
+                                            uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags);
+int32_t zkp_json_write_correct_key_proof_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* sigma, char* out_text, uint64_t text_cap,
+                                               uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags);
+
 /* ------------------------------------------------------------------ several GPUs behind one caller
  * The reference spreads a proof's rows over a rayon pool (src/zkproofs/range_proof.rs:161-187,270-348); here a batch
  * is cut into contiguous blocks of PROOF indices, one block per device context, one host thread per context

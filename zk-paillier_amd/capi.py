@@ -109,6 +109,11 @@ EXPORTS = {
     "zkp_json_range_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint32]),
     "zkp_json_range_proof_ni_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint32]),
     "zkp_json_correct_key_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_doc_bound": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "zkp_json_write_encrypted_pairs_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_write_range_proof_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_write_range_proof_ni_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_write_correct_key_proof_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_correct_key_ni_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "zkp_dlog_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -181,6 +186,12 @@ DEC_OK, DEC_INVALID, DEC_NEGATIVE, DEC_OVERFLOW = 0, 1, 2, 3
 BIGINT_DEC, BIGINT_HEX, BIGINT_BYTES = 0, 1, 2
 DOC_OK, DOC_INVALID, DOC_HOST_PATH = 0, 2, 3
 GATHER_HOST, GATHER_RCCL, GATHER_COPY = 0, 1, 2
+JSON_DOC_ENCRYPTED_PAIRS, JSON_DOC_RANGE_PROOF, JSON_DOC_RANGE_PROOF_NI, JSON_DOC_CORRECT_KEY_PROOF = 0, 1, 2, 3
+
+
+def json_doc_bound(doc_kind: int, n_bits: int, error_factor: int = SECURITY_PARAMETER, forms: int = 0) -> int:
+    """zkp_json_doc_bound: an upper bound of one written document's length (a pure host function: no GPU, no context)"""
+    return load().zkp_json_doc_bound(doc_kind, n_bits, error_factor, forms)
 
 
 def bigint_forms(key_form: int, bare_form: int) -> int:
@@ -600,3 +611,37 @@ class Context:
         buf, off, ln = self._json_docs(docs)
         self.check(self.lib.zkp_json_correct_key_proof_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), n_bits, len(docs), ptr(out_sigma),
                                                              ptr(out_status), self._flags(out_sigma, out_status)))
+
+    # ---- the writers: SoA batch -> serde_json documents (sizing call, one allocation, writing call)
+    def _json_write(self, call, batch, out_status):
+        """call(text pointer or None, capacity, offsets pointer) -> status.  Returns (text, offsets, status): text a numpy uint8 array
+        holding the documents back to back, document b = text[offsets[b]:offsets[b + 1]]"""
+        off = np.zeros(batch + 1, np.uint64)
+        self.check(call(None, 0, ptr(off)))
+        text = np.empty(int(off[batch]), np.uint8)
+        if text.size:
+            sized = off.copy()
+            self.check(call(ptr(text), text.size, ptr(off)))
+            assert np.array_equal(sized, off)
+        return text, off, out_status
+
+    def json_write_encrypted_pairs(self, proofs: RangeNiProofs, out_status=None, device: bool = False):
+        fl = ZKP_F_DEVICE_PTRS if device else 0
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_encrypted_pairs_batch(self.h, C.byref(proofs), t, cap, off, ptr(out_status), fl),
+                                proofs.batch, out_status)
+
+    def json_write_range_proof(self, proofs: RangeNiProofs, out_status=None, device: bool = False):
+        fl = ZKP_F_DEVICE_PTRS if device else 0
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_range_proof_batch(self.h, C.byref(proofs), t, cap, off, ptr(out_status), fl),
+                                proofs.batch, out_status)
+
+    def json_write_range_proof_ni(self, proofs: RangeNiProofs, forms: int = 0, out_status=None, device: bool = False):
+        """whole RangeProofNi documents; forms = bigint_forms(key_form, bare_form), as for json_range_proof_ni"""
+        fl = ZKP_F_DEVICE_PTRS if device else 0
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_range_proof_ni_batch(self.h, C.byref(proofs), forms, t, cap, off, ptr(out_status), fl),
+                                proofs.batch, out_status)
+
+    def json_write_correct_key_proof(self, n_bits: int, batch: int, sigma, out_status=None):
+        fl = self._flags(sigma, out_status)
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_correct_key_proof_batch(self.h, n_bits, batch, ptr(sigma), t, cap, off, ptr(out_status), fl),
+                                batch, out_status)

@@ -21,6 +21,7 @@
 #include "kernels_proofs.hpp"
 #include "kernels_inv.hpp"
 #include "kernels_serde.hpp"
+#include "kernels_serde_write.hpp"
 #include "kernels_sample.hpp"
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1

@@ -632,3 +632,175 @@ extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, c
   }
   return st;
 } ZKP_CATCH(c)
+
+// ---- the writers: the SoA batch -> serde_json documents, back to back in host memory (kernels_serde_write.hpp has the three phases).
+// Not modexp work: like the readers they run on this library whatever engine the ctx routes its proof calls to (no ZKP_ROUTE).
+namespace {
+// decimal digits of the largest value of `words` limbs (zkp_decimal_pitch is that plus one)
+uint64_t max_digits(uint32_t words) { return (uint64_t)zkp_decimal_pitch(words) - 1; }
+uint64_t max_form_len(uint32_t words, uint32_t form) {       // the body of an un-annotated BigInt, quotes / brackets excluded
+  const uint64_t nb = 4ull * words;
+  return form == ZKP_BIGINT_DEC ? max_digits(words) : form == ZKP_BIGINT_HEX ? 2 * nb : 4 * nb - 1;
+}
+uint64_t uint_digits(uint64_t v) { uint64_t d = 1; while (v >= 10) { v /= 10; d++; } return d; }
+constexpr uint64_t cstrlen(const char* s) { return *s ? 1 + cstrlen(s + 1) : 0; }
+}  // namespace
+
+extern "C" uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms) {
+  const uint32_t key_form = (bigint_forms >> 4) & 15u, bare_form = bigint_forms & 15u;
+  if ((n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || doc_kind > ZKP_JSON_DOC_CORRECT_KEY_PROOF || (bigint_forms >> 8) ||
+      key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (doc_kind != ZKP_JSON_DOC_CORRECT_KEY_PROOF && error_factor == 0))
+    return 0;
+  const uint32_t kw = n_bits / 32;
+  const uint64_t EF = error_factor, dn = max_digits(kw), dc = max_digits(2 * kw);
+  if (doc_kind == ZKP_JSON_DOC_CORRECT_KEY_PROOF) return cstrlen("{\"sigma_vec\":[") + ZKP_CORRECT_KEY_M2 * (dn + 3) - 1 + cstrlen("]}");
+  // {"c1":["..",".."],"c2":[..]}
+  const uint64_t pairs = cstrlen("{\"c1\":[") + cstrlen("],\"c2\":[") + cstrlen("]}") + 2 * (EF * (dc + 3) - 1);
+  // the longer of the two variants per row (Open for every width of this ABI; both are written down so that nothing depends on it)
+  const uint64_t open = cstrlen("{\"Open\":{\"w1\":\"\",\"r1\":\"\",\"w2\":\"\",\"r2\":\"\"}}") + 4 * dn;
+  const uint64_t mask = cstrlen("{\"Mask\":{\"j\":255,\"masked_x\":\"\",\"masked_r\":\"\"}}") + 2 * dn;
+  const uint64_t proof = 2 + EF * (std::max(open, mask) + 1) - 1;
+  if (doc_kind == ZKP_JSON_DOC_ENCRYPTED_PAIRS) return pairs;
+  if (doc_kind == ZKP_JSON_DOC_RANGE_PROOF) return proof;
+  return cstrlen("{\"ek\":{\"n\":},\"range\":,\"ciphertext\":,\"encrypted_pairs\":,\"proof\":,\"error_factor\":}") + 6 /* quotes or brackets */ +
+         max_form_len(kw, key_form) + max_form_len(kw, bare_form) + max_form_len(2 * kw, bare_form) + pairs + proof + uint_digits(EF);
+}
+
+static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, const zkp_range_ni_proofs* p, uint32_t n_bits, uint64_t B, uint64_t EF,
+                               const uint32_t* sigma, uint32_t forms, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags) {
+  if (!c) return ZKP_EINVAL;
+  const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
+  const bool ck = doc_kind == W_DOC_CK, ni = doc_kind == W_DOC_NI, has_pairs = doc_kind == W_DOC_PAIRS || ni, has_proof = doc_kind == W_DOC_PROOF || ni;
+  const uint32_t kw = n_bits / 32;
+  bool bad = !out_doc_off || (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24) ||
+             (forms >> 8) || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (!ck && !p) || (!ck && (EF == 0 || EF > 256));
+  if (!bad && B) {
+    if (ck) bad = !sigma;
+    else bad = (has_pairs && (!p->c1 || !p->c2)) || (has_proof && (!p->resp_kind || !p->resp_j || !p->resp_w1 || !p->resp_r1 || !p->resp_w2 || !p->resp_r2)) ||
+               (ni && (!p->n || !p->range || !p->ciphertext || (p->n_stride != 0 && p->n_stride != kw)));
+  }
+  if (bad) { c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL; }
+  out_doc_off[0] = 0;
+  if (B == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  Stage s(c, flags);
+  WJob J{};
+  J.B = B; J.ef = (uint32_t)EF; J.doc_kind = doc_kind; J.key_form = key_form; J.bare_form = bare_form;
+  J.per_proof_keys = ni && p->n_stride != 0;
+  J.slots = ck ? ZKP_CORRECT_KEY_M2 : (uint32_t)((ni ? 3 : 0) + (has_pairs ? 2 * EF : 0) + (has_proof ? 4 * EF : 0));
+  struct Todo { int arr; uint64_t count; uint32_t form; };
+  std::vector<Todo> todo;
+  auto add = [&](int arr, const uint32_t* src, uint64_t count, uint32_t words, uint32_t form) {
+    WArr& a = J.a[arr];
+    a.words = words; a.G = (uint32_t)((max_digits(words) + 8) / 9);
+    a.src = s.in(src, count * words);
+    a.len = (uint32_t*)s.take(count * sizeof(uint32_t));
+    a.groups = (uint32_t*)s.take(form == ZKP_BIGINT_DEC ? (count + 63) / 64 * 64 * a.G * sizeof(uint32_t) : count * sizeof(uint32_t));
+    todo.push_back({arr, count, form});
+  };
+  const uint64_t rows = B * EF;
+  if (ck) add(W_ARR_W1, sigma, B * ZKP_CORRECT_KEY_M2, kw, ZKP_BIGINT_DEC);
+  if (ni) {
+    add(W_ARR_N, p->n, p->n_stride ? B : 1, kw, key_form);
+    add(W_ARR_RANGE, p->range, B, kw, bare_form);
+    add(W_ARR_CT, p->ciphertext, B, 2 * kw, bare_form);
+  }
+  if (has_pairs) { add(W_ARR_C1, p->c1, rows, 2 * kw, ZKP_BIGINT_DEC); add(W_ARR_C2, p->c2, rows, 2 * kw, ZKP_BIGINT_DEC); }
+  if (has_proof) {
+    add(W_ARR_W1, p->resp_w1, rows, kw, ZKP_BIGINT_DEC); add(W_ARR_R1, p->resp_r1, rows, kw, ZKP_BIGINT_DEC);
+    add(W_ARR_W2, p->resp_w2, rows, kw, ZKP_BIGINT_DEC); add(W_ARR_R2, p->resp_r2, rows, kw, ZKP_BIGINT_DEC);
+    J.kind = s.in((const uint8_t*)p->resp_kind, rows); J.j = s.in((const uint8_t*)p->resp_j, rows);
+  }
+  uint8_t* dstat = s.out(out_status, B);
+  uint64_t* rel = (uint64_t*)s.take(B * J.slots * sizeof(uint64_t));
+  uint64_t* doclen = (uint64_t*)s.take(B * sizeof(uint64_t));
+  uint64_t* doff = (uint64_t*)s.take((B + 1) * sizeof(uint64_t));
+  int32_t st = s.st;
+  auto launched = [&](const char* what) { if (!st && hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = std::string(name) + ": " + what; } };
+  if (!st) {
+    // convert
+    for (const Todo& t : todo) {
+      const WArr& a = J.a[t.arr];
+      if (t.form == ZKP_BIGINT_DEC)
+        hipLaunchKernelGGL(k_w_convert, dim3((unsigned)((t.count + SERDE_LANES - 1) / SERDE_LANES)), dim3(SERDE_LANES), (size_t)a.words * SERDE_LANES * 4, c->stream, a.src,
+                           (int)a.words, t.count, a.groups, a.G, a.len);
+      else
+        hipLaunchKernelGGL(k_w_formlen, dim3((unsigned)((t.count + 255) / 256)), dim3(256), 0, c->stream, a.src, (int)a.words, t.count, t.form, a.groups, a.len);
+    }
+    launched("convert");
+    // size
+    if (!st) {
+      hipLaunchKernelGGL(k_w_doclen, dim3((unsigned)B), dim3(64), 0, c->stream, J, rel, doclen, dstat);
+      hipLaunchKernelGGL(k_w_scan, dim3(1), dim3(1024), 0, c->stream, (const uint64_t*)doclen, B, doff);
+      launched("size");
+    }
+    if (!st && (hipMemcpyAsync(out_doc_off, doff, (B + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                hipStreamSynchronize(c->stream) != hipSuccess)) { st = ZKP_EDEVICE; c->err = std::string(name) + ": offsets D2H"; }
+  }
+  const uint64_t total = st ? 0 : out_doc_off[B];
+  if (!st && out_text && text_cap < total) {
+    st = ZKP_EINVAL;
+    c->err = std::string(name) + ": text_cap " + std::to_string(text_cap) + " is less than the " + std::to_string(total) + " bytes of the documents";
+    const int32_t fin = s.finish();       // (the status bytes are still delivered; finish() returns the sticky status)
+    (void)fin;
+    return ZKP_EINVAL;
+  }
+  if (!st && out_text && total) {
+    // assemble, in runs of whole documents of at most `chunk` bytes: run k + 1 is assembled while run k travels to the host.  Every byte
+    // is placed by its absolute offset, so the text does not depend on where the runs are cut.
+    uint64_t chunk = 256ull << 20;
+    if (const char* e = std::getenv("ZKP_JSON_WRITE_CHUNK")) { const unsigned long long v = std::strtoull(e, nullptr, 10); if (v) chunk = v; }
+    uint64_t longest = 0;
+    for (uint64_t b = 0; b < B; b++) longest = std::max(longest, out_doc_off[b + 1] - out_doc_off[b]);
+    chunk = std::min(std::max(chunk, longest), total);
+    Piped pipe(c, s);
+    st = pipe.streams(2);
+    char* buf[2] = {nullptr, nullptr};
+    if (!st) { buf[0] = (char*)s.take(chunk + 8); buf[1] = chunk < total ? (char*)s.take(chunk + 8) : buf[0]; st = s.st; }
+    uint64_t lo = 0;
+    for (int k = 0; !st && lo < B; k++) {
+      uint64_t hi = lo + 1;
+      while (hi < B && out_doc_off[hi + 1] - out_doc_off[lo] <= chunk) hi++;
+      const uint64_t a0 = out_doc_off[lo], a1 = out_doc_off[hi], base = a0 & ~3ull;
+      hipEvent_t assembled = c->ev_pipe[k & 1], copied = c->ev_pipe[2 + (k & 1)];
+      if (a1 > a0) {
+        if (k >= 2 && hipStreamWaitEvent(c->stream, copied, 0) != hipSuccess) { st = ZKP_EDEVICE; c->err = "stream wait"; break; }
+        const uint64_t n_slots = (hi - lo) * J.slots;
+        hipLaunchKernelGGL(k_w_assemble, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, c->stream, J, (const uint64_t*)rel, (const uint64_t*)doff, lo * J.slots, n_slots,
+                           buf[k & 1], base);
+        launched("assemble");
+        if (!st && (hipEventRecord(assembled, c->stream) != hipSuccess || hipStreamWaitEvent(c->copy, assembled, 0) != hipSuccess ||
+                    hipMemcpyAsync(out_text + a0, buf[k & 1] + (a0 - base), a1 - a0, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
+                    hipEventRecord(copied, c->copy) != hipSuccess)) { st = ZKP_EDEVICE; c->err = std::string(name) + ": text D2H"; }
+        c->copy_busy = true;
+      }
+      lo = hi;
+    }
+    const int32_t pf = pipe.finish();
+    if (!st) st = pf;
+  }
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
+}
+
+extern "C" int32_t zkp_json_write_encrypted_pairs_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
+                                                        uint8_t* out_status, uint32_t flags) try {
+  return json_write_impl(c, "zkp_json_write_encrypted_pairs_batch", W_DOC_PAIRS, p, p ? p->n_bits : 0, p ? p->batch : 0, p ? p->error_factor : 0, nullptr, 0,
+                         out_text, text_cap, out_doc_off, out_status, flags);
+} ZKP_CATCH(c)
+extern "C" int32_t zkp_json_write_range_proof_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
+                                                    uint8_t* out_status, uint32_t flags) try {
+  return json_write_impl(c, "zkp_json_write_range_proof_batch", W_DOC_PROOF, p, p ? p->n_bits : 0, p ? p->batch : 0, p ? p->error_factor : 0, nullptr, 0,
+                         out_text, text_cap, out_doc_off, out_status, flags);
+} ZKP_CATCH(c)
+extern "C" int32_t zkp_json_write_range_proof_ni_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, uint32_t bigint_forms, char* out_text, uint64_t text_cap,
+                                                       uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags) try {
+  return json_write_impl(c, "zkp_json_write_range_proof_ni_batch", W_DOC_NI, p, p ? p->n_bits : 0, p ? p->batch : 0, p ? p->error_factor : 0, nullptr, bigint_forms,
+                         out_text, text_cap, out_doc_off, out_status, flags);
+} ZKP_CATCH(c)
+extern "C" int32_t zkp_json_write_correct_key_proof_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* sigma, char* out_text, uint64_t text_cap,
+                                                          uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags) try {
+  return json_write_impl(c, "zkp_json_write_correct_key_proof_batch", W_DOC_CK, nullptr, n_bits, batch, 0, sigma, 0, out_text, text_cap, out_doc_off, out_status, flags);
+} ZKP_CATCH(c)

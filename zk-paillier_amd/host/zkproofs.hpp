@@ -1325,6 +1325,107 @@ inline NiCorrectKeyProof correct_key_from_str(const EncryptionKey& ek, const std
 // range / ciphertext are un-annotated in the reference (range_proof_ni.rs:38-40): their text forms are the caller's to name,
 // separately (kzen-paillier's EncryptionKey and curv's BigInt need not agree), as for zkp_json_range_proof_ni_batch.
 enum class BigintText { Dec = ZKP_BIGINT_DEC, Hex = ZKP_BIGINT_HEX, Bytes = ZKP_BIGINT_BYTES };
+// ---- whole batches: zkp_json_write_*_batch converts, sizes and assembles the documents on the GPU; one call per batch, the text comes
+// back finished.  (RangeProofNi::prove_batch / prove_batch_seeded hand their result over as host BigInts — this layer keeps no
+// device-resident batch —, so these overloads stage the limbs in again; a caller that holds the SoA batch on the device uses the C ABI
+// entry points with ZKP_F_DEVICE_PTRS and moves no limb at all.)
+namespace detail_json {
+struct WriteBatch {
+  uint32_t nb = 0, kw = 0; size_t B = 0, EF = 0;
+  std::vector<uint32_t> n, range, ct, c1, c2, w1, r1, w2, r2;
+  std::vector<uint8_t> kind, jj;
+  zkp_range_ni_proofs p{};
+  WriteBatch(const BigInt& key, size_t B_, size_t EF_) : nb(width_for(key)), kw(nb / 32), B(B_), EF(EF_) {
+    p.n_bits = nb; p.error_factor = (uint32_t)EF; p.batch = B;
+  }
+  void pairs(size_t b, const EncryptedPairs& e) {
+    if (e.c1.size() != EF || e.c2.size() != EF) throw std::invalid_argument("to_string_batch: every document of a batch has the same number of rows");
+    if (c1.empty()) { c1.resize(B * EF * 2 * kw); c2.resize(B * EF * 2 * kw); p.c1 = c1.data(); p.c2 = c2.data(); }
+    for (size_t i = 0; i < EF; i++) { e.c1[i].to_limbs(&c1[(b * EF + i) * 2 * kw], 2 * kw); e.c2[i].to_limbs(&c2[(b * EF + i) * 2 * kw], 2 * kw); }
+  }
+  void proof(size_t b, const Proof& pr) {
+    if (pr.responses.size() != EF) throw std::invalid_argument("to_string_batch: every document of a batch has the same number of rows");
+    if (w1.empty()) {
+      for (auto* v : {&w1, &r1, &w2, &r2}) v->resize(B * EF * kw);
+      kind.resize(B * EF); jj.resize(B * EF);
+      p.resp_w1 = w1.data(); p.resp_r1 = r1.data(); p.resp_w2 = w2.data(); p.resp_r2 = r2.data(); p.resp_kind = kind.data(); p.resp_j = jj.data();
+    }
+    for (size_t i = 0; i < EF; i++) {
+      const Response& r = pr.responses[i];
+      const size_t t = b * EF + i;
+      if (r.kind == Response::Open) {
+        kind[t] = ZKP_RESP_OPEN;
+        r.w1.to_limbs(&w1[t * kw], kw); r.r1.to_limbs(&r1[t * kw], kw); r.w2.to_limbs(&w2[t * kw], kw); r.r2.to_limbs(&r2[t * kw], kw);
+      } else {
+        kind[t] = ZKP_RESP_MASK; jj[t] = r.j;
+        r.masked_x.to_limbs(&w1[t * kw], kw); r.masked_r.to_limbs(&r1[t * kw], kw);
+      }
+    }
+  }
+  // call(text or null, capacity, offsets) -> status: the sizing call, one allocation, the writing call
+  template <class F> std::vector<std::string> run(F call, const char* what) {
+    Engine& e = Engine::instance();
+    std::vector<uint64_t> off(B + 1, 0);
+    e.check(call((char*)nullptr, (uint64_t)0, off.data()), what);
+    std::string text((size_t)off[B], '\0');
+    if (!text.empty()) e.check(call(&text[0], (uint64_t)text.size(), off.data()), what);
+    std::vector<std::string> out(B);
+    for (size_t b = 0; b < B; b++) out[b] = text.substr((size_t)off[b], (size_t)(off[b + 1] - off[b]));
+    return out;
+  }
+};
+}  // namespace detail_json
+
+inline std::vector<std::string> to_string_batch(const std::vector<EncryptedPairs>& v, const EncryptionKey& ek) {
+  if (v.empty()) return {};
+  detail_json::WriteBatch w(ek.n, v.size(), v[0].c1.size());
+  for (size_t b = 0; b < v.size(); b++) w.pairs(b, v[b]);
+  Engine& e = Engine::instance();
+  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_encrypted_pairs_batch(e.ctx(), &w.p, t, cap, off, nullptr, 0); },
+               "zkp_json_write_encrypted_pairs_batch");
+}
+inline std::vector<std::string> to_string_batch(const std::vector<Proof>& v, const EncryptionKey& ek) {
+  if (v.empty()) return {};
+  detail_json::WriteBatch w(ek.n, v.size(), v[0].responses.size());
+  for (size_t b = 0; b < v.size(); b++) w.proof(b, v[b]);
+  Engine& e = Engine::instance();
+  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_range_proof_batch(e.ctx(), &w.p, t, cap, off, nullptr, 0); },
+               "zkp_json_write_range_proof_batch");
+}
+inline std::vector<std::string> to_string_batch(const std::vector<NiCorrectKeyProof>& v, const EncryptionKey& ek) {
+  if (v.empty()) return {};
+  Engine& e = Engine::instance();
+  const uint32_t nb = width_for(ek.n), kw = nb / 32;
+  std::vector<uint32_t> sigma(v.size() * ZKP_CORRECT_KEY_M2 * kw);
+  for (size_t b = 0; b < v.size(); b++) {
+    if (v[b].sigma_vec.size() != ZKP_CORRECT_KEY_M2) throw std::invalid_argument("to_string_batch: a NiCorrectKeyProof has 11 values");
+    for (size_t i = 0; i < ZKP_CORRECT_KEY_M2; i++) v[b].sigma_vec[i].to_limbs(&sigma[(b * ZKP_CORRECT_KEY_M2 + i) * kw], kw);
+  }
+  detail_json::WriteBatch w(ek.n, v.size(), 0);
+  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_correct_key_proof_batch(e.ctx(), nb, v.size(), sigma.data(), t, cap, off, nullptr, 0); },
+               "zkp_json_write_correct_key_proof_batch");
+}
+inline std::vector<std::string> to_string_batch(const std::vector<RangeProofNi>& v, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
+  if (v.empty()) return {};
+  detail_json::WriteBatch w(v[0].ek.n, v.size(), v[0].error_factor);
+  const uint32_t kw = w.kw;
+  w.n.resize(v.size() * kw); w.range.resize(v.size() * kw); w.ct.resize(v.size() * 2 * kw);
+  for (size_t b = 0; b < v.size(); b++) {
+    if (width_for(v[b].ek.n) != w.nb || v[b].error_factor != w.EF) throw std::invalid_argument("to_string_batch: one key width and one error_factor per batch");
+    v[b].ek.n.to_limbs(&w.n[b * kw], kw); v[b].range.to_limbs(&w.range[b * kw], kw); v[b].ciphertext.to_limbs(&w.ct[b * 2 * kw], 2 * kw);
+    w.pairs(b, v[b].encrypted_pairs); w.proof(b, v[b].proof);
+  }
+  w.p.n = w.n.data(); w.p.n_stride = kw; w.p.range = w.range.data(); w.p.ciphertext = w.ct.data();
+  const uint32_t forms = ZKP_BIGINT_FORMS((uint32_t)key_form, (uint32_t)bigint_form);
+  Engine& e = Engine::instance();
+  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_range_proof_ni_batch(e.ctx(), &w.p, forms, t, cap, off, nullptr, 0); },
+               "zkp_json_write_range_proof_ni_batch");
+}
+// the whole document (range_proof_ni.rs:36-44), the inverse of range_proof_ni_from_str
+inline std::string to_string(const RangeProofNi& p, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
+  return to_string_batch(std::vector<RangeProofNi>{p}, key_form, bigint_form)[0];
+}
+
 namespace detail_json {
 struct Cur {
   const std::string& t; size_t p = 0;
