@@ -2,12 +2,18 @@
 against pow(): the algebra, the per-key constants, the bounds the ladder relies on — and, at lane level, the two things the kernels add
 to the product of tests/test_lane_model.py: initial column values on the b side and the quotient digits taken from the a side, with the
 64-bit column bound of the FAST product restated for the extra 58-bit value a b-side column starts with."""
+import os
 import random
+import re
 
 import pytest
 
+import limit_keys
+from limit_keys import sn_limit_basen          # (kernels_basen.hpp COL_FAST_SN_LIMIT_BN: restated once, in tests/limit_keys.py)
 from basen_model import BaseN, LB, B, MASK, W
 from test_lane_model import to_limbs, from_limbs, fast_sn_limit
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zk-paillier_amd", "csrc")
 
 
 def odd_modulus(rnd, bits):
@@ -52,11 +58,6 @@ def test_enc_equals_pow(bits):
     for _ in range(2):
         r, msg = rnd.getrandbits(bits), rnd.randrange(n)
         assert m.enc(msg, r) == (1 + msg * n) * pow(r, n, n * n) % (n * n)
-
-
-def sn_limit_basen(Wd=W):
-    """kernels_basen.hpp COL_FAST_SN_LIMIT_BN"""
-    return ((1 << 64) - 1 - (1 << 36) - ((1 << LB) + 16) * (Wd * (1 << LB) + 16) - (1 << (2 * LB)) - (1 << LB)) >> LB
 
 
 def lane_product(N, G, A, Bv, init, stats):
@@ -136,3 +137,84 @@ def test_column_bound_with_the_initial_value():
     # the analytic bound of bigint29.hpp "column capacity" with the b side's initial column value (< 2^58 + 2^29) added:
     assert ((1 << LB) + 16) * (W * (1 << LB) + 16) + MASK * lim + (1 << 36) + (1 << (2 * LB)) + (1 << LB) < (1 << 64)
     assert ((1 << LB) + 16) * (W * (1 << LB) + 16) + MASK * (lim + (1 << LB)) + (1 << 36) + (1 << (2 * LB)) + (1 << LB) >= (1 << 64) - (1 << 59)
+
+
+def constexpr_from_source(path, name, env):
+    """the value of `constexpr <type> <name> = <expression>;` in a header, its C++ expression evaluated with 64-bit unsigned wrap-around
+    at every ~ (the only operator in these two definitions that could leave the range; the final value is asserted to be in it)"""
+    text = open(os.path.join(CSRC, path)).read()
+    m = re.search(r"^constexpr\s+\w+\s+" + name + r"\s*=\s*(.+?);", text, flags=re.M)
+    assert m, f"{path}: no definition of {name}"
+    expr = m.group(1)
+    expr = expr.replace("~0ull", "0xFFFFFFFFFFFFFFFF")
+    expr = re.sub(r"\b(\d+)(?:ull|u)\b", r"\1", expr)
+    assert re.fullmatch(r"[\sA-Za-z0-9_()+\-*<>&|]*", expr) and "~" not in expr, expr
+    v = eval(expr, {"__builtins__": {}}, dict(env))
+    assert 0 <= v < 1 << 64
+    return v
+
+
+def test_the_limit_constants_of_the_sources_are_the_ones_the_tests_restate():
+    """COL_FAST_SN_LIMIT (bigint29.hpp) and COL_FAST_SN_LIMIT_BN (kernels_basen.hpp) read out of the headers, for every engine's limbs per
+    lane, against the one Python restatement (tests/limit_keys.py) the models and the GPU tests compute their expectations from"""
+    import test_gpu_soak
+    import test_lane_model
+    assert test_lane_model.fast_sn_limit is limit_keys.fast_sn_limit is fast_sn_limit is test_gpu_soak.fast_sn_limit
+    lb = constexpr_from_source("bigint29.hpp", "LB", {})
+    assert lb == LB == limit_keys.LB
+    text = open(os.path.join(CSRC, "bigint29.hpp")).read()
+    assert re.search(r"^#define ZKP_W 36$", text, flags=re.M) and re.search(r"^constexpr int W = ZKP_W;", text, flags=re.M)
+    for Wd in (36, 18, 9):
+        env = {"LB": lb, "W": Wd}
+        fast = constexpr_from_source("bigint29.hpp", "COL_FAST_SN_LIMIT", env)
+        bn = constexpr_from_source("kernels_basen.hpp", "COL_FAST_SN_LIMIT_BN", env)
+        assert fast == fast_sn_limit(Wd)
+        assert bn == sn_limit_basen(Wd)
+        # only 36 limbs per lane can reach the limit at all: at 18 and 9 every key passes the digit-sum test
+        assert (Wd * MASK > bn) == (Wd == 36) and (Wd * MASK > fast) == (Wd == 36)
+
+
+@pytest.mark.parametrize("bits,G", [(2048, 2), (4096, 4)])
+def test_limit_key_constructor(bits, G):
+    """tests/limit_keys.py: keys whose Orup multiple has chosen lane sums — every lane at the limit, each single lane at limit + delta with
+    the others random, the modexp flavour (n1 = 1, the other constant) — are odd, full length, have the n1 asked for and a full-width M~"""
+    rnd = random.Random(bits)
+    lim = sn_limit_basen()
+    shapes = [[0] * G, [0] * (G - 1) + [1], [None] * G]
+    for j in range(G):
+        for delta in (-1, 0, 1, 1 << 20, -(1 << 20)):
+            shapes.append([delta if i == j else None for i in range(G)])
+    for deltas in shapes:
+        n = limit_keys.limit_key(bits, W, deltas, lim, rnd)
+        m = BaseN(n, G)
+        assert n & 1 and n.bit_length() == bits and m.n1 >> (LB - 1) == 1
+        assert m.Mt.bit_length() > bits + LB - 2 and 4 * m.Mt < m.R
+        if bits == 4096:
+            assert m.Mt >> (LB * 143) == 0 and (m.Mt >> (LB * 142)).bit_length() <= 7        # (limb 143 is zero, limb 142 has 7 bits)
+        sums = limit_keys.lane_sums(m.Mt, W, G)
+        for j, d in enumerate(deltas):
+            if d is None:
+                assert sums[j] < lim - (1 << 30), "a random lane is far below the limit"
+            else:
+                assert sums[j] == lim + d
+    # a given n1; and n1 = 1 with the modexp kernels' constant: M~ = n, as tests/test_gpu_soak.py limit_modulus builds it
+    n = limit_keys.limit_key(bits, W, [0] * G, lim, rnd, n1=0x12345679)
+    assert BaseN(n, G).n1 == 0x12345679
+    for j in range(G):
+        n = limit_keys.limit_key(bits, W, [1 if i == j else None for i in range(G)], fast_sn_limit(W), rnd, n1=1)
+        assert n & MASK == MASK and n.bit_length() == bits and limit_keys.lane_sums(n, W, G)[j] == fast_sn_limit(W) + 1
+    # the same seed gives the same key
+    assert limit_keys.limit_key(bits, W, [0] * G, lim, random.Random(5)) == limit_keys.limit_key(bits, W, [0] * G, lim, random.Random(5))
+
+
+def test_the_guard_key_set_has_both_sides_of_the_guard():
+    """the keys of tests/test_gpu_basen_limit.py: at 36 limbs per lane the deltas above zero are over the limit and the others within it; no
+    sum of 18 or 9 limbs reaches that engine's limit"""
+    for n_bits in (2048, 4096):
+        G = n_bits // 1024
+        keys = limit_keys.guard_key_set(n_bits)
+        assert len(keys) == len(limit_keys.DELTAS) * G + 2
+        verdicts = [limit_keys.qualifies(n, n_bits, 36) for _, _, n in keys]
+        assert verdicts == [d <= 0 for _ in range(G) for d in limit_keys.DELTAS] + [True, False]
+        for Wd in (18, 9):
+            assert all(limit_keys.qualifies(n, n_bits, Wd) for _, _, n in keys)

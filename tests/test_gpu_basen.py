@@ -118,7 +118,7 @@ def test_enc_batch_equals_python_and_the_n2_sized_kernels(ctx, n_bits):
     assert lanes == lanes_per_integer(ctx, n_bits) and ok, "the launch should have run in base-n form"
     for i in range(count):
         got = sum(int(w) << (32 * j) for j, w in enumerate(out[i]))
-        assert got == (1 + ms[i] * n) * pow(rs[i], n, nn) % nn, i
+        assert got == H.python_enc(n, ms[i], rs[i]), i
     # Enc-and-compare: right and wrong expected values, and products of two ciphertexts as the expected value
     exp = out.copy()
     exp[6, 5] ^= 1
@@ -152,7 +152,6 @@ def test_enc_under_keys_with_long_runs_of_equal_bits(ctx):
             (1 << 2047) | (rnd.getrandbits(300) << 1500) | rnd.getrandbits(200) | 1]     # islands of random bits in zeros
     for n in keys:
         assert n & 1 and n.bit_length() == n_bits
-        nn = n * n
         count = 40
         ms = [rnd.randrange(n) for _ in range(count)]
         rs = [rnd.randrange(n) for _ in range(count)]
@@ -163,7 +162,7 @@ def test_enc_under_keys_with_long_runs_of_equal_bits(ctx):
         lanes, ok = ctx.diag_basen_last()
         for i in range(count):
             got = sum(int(w) << (32 * j) for j, w in enumerate(out[i]))
-            assert got == (1 + ms[i] * n) * pow(rs[i], n, nn) % nn, (hex(n)[:20], i, lanes, ok)
+            assert got == H.python_enc(n, ms[i], rs[i]), (hex(n)[:20], i, lanes, ok)
 
 
 @pytest.mark.parametrize("n_bits", [2048, 4096])
@@ -186,7 +185,7 @@ def test_enc_batch_with_per_item_keys_equals_python(ctx, n_bits):
     for i in range(count):
         n = ns[i]
         got = sum(int(w) << (32 * j) for j, w in enumerate(out[i]))
-        assert got == (1 + ms[i] * n) * pow(rs[i], n, n * n) % (n * n), i
+        assert got == H.python_enc(n, ms[i], rs[i]), i
     # keys the form does not take are PARTITIONED off, item by item (round 5; round 4 sent the whole launch to the n^2-sized kernels):
     # a short key (1000 bits in the 2048-bit context: no room for the b parts) — its item comes back right from the n^2-sized launch behind
     ns2 = list(ns)
@@ -199,7 +198,7 @@ def test_enc_batch_with_per_item_keys_equals_python(ctx, n_bits):
     for i in range(count):
         n = ns2[i]
         got = sum(int(w) << (32 * j) for j, w in enumerate(out2[i]))
-        assert got == (1 + ms2[i] * n) * pow(rs[i], n, n * n) % (n * n), i
+        assert got == H.python_enc(n, ms2[i], rs[i]), i
     # an even key: the entry point reports it (no Montgomery form exists), the other items are done and equal to the clean batch's
     ns3 = list(ns)
     ns3[3] -= 1
@@ -291,7 +290,7 @@ def test_one_enc_per_wavefront_ladder_of_the_latency_engine(lanes):
                 if i >= 48 and i % 23:                              # (the two kernels agree on every item, above; Python checks the edge cases and a sample)
                     continue
                 got = sum(int(w) << (32 * j) for j, w in enumerate(outs[0][i]))
-                assert got == (1 + ms[i] * n) * pow(rs[i], n, nn) % nn, (trial, i)
+                assert got == H.python_enc(n, ms[i], rs[i]), (trial, i)
             c.set_r2l(2)
             exp = outs[0].copy(); exp[6, 5] ^= 1
             ok = np.full(count, 9, np.uint8)

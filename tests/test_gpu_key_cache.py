@@ -109,7 +109,7 @@ def test_the_record_of_a_buffer_changes_hands(kctx, oracle, engine):
             c.paillier_enc(2048, count, L.int_to_limbs(n, kw), 0, mw, rw, out)
             for i in range(count):
                 r = (3 + i) | (0x1234567 << (32 * 40))
-                assert L.limbs_to_int(out[i]) == (1 + (7 + i) * n) * pow(r, n, n * n) % (n * n), (hex(n)[:12], i)
+                assert L.limbs_to_int(out[i]) == H.python_enc(n, 7 + i, r), (hex(n)[:12], i)
     finally:
         c.set_geometry(0)
         c.set_enc_form("auto")

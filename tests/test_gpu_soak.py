@@ -14,6 +14,7 @@ import pytest
 
 import helpers as H  # noqa: F401  (puts the repo root and tests/ on sys.path)
 from helpers import pm, L
+from limit_keys import fast_sn_limit          # (bigint29.hpp COL_FAST_SN_LIMIT: restated once, in tests/limit_keys.py)
 import soak_gpu
 import soak_gpu_proofs
 
@@ -61,10 +62,6 @@ def test_randomised_soak_proofs(zkp, oracle):
         print("proofs soaked:", total)
     finally:
         ctx.close()
-
-
-def fast_sn_limit(W=36):
-    return ((1 << 64) - 1 - (1 << 36) - ((1 << LB) + 16) * (W * (1 << LB) + 16)) >> LB
 
 
 def limit_modulus(mod_bits, lane, delta, d, W=36):

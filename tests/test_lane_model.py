@@ -11,13 +11,10 @@ import random
 
 import pytest
 
+from limit_keys import fast_sn_limit          # (bigint29.hpp COL_FAST_SN_LIMIT: restated once, in tests/limit_keys.py)
+
 B = 29
 MASK = (1 << B) - 1
-
-
-def fast_sn_limit(W):
-    """bigint29.hpp COL_FAST_SN_LIMIT"""
-    return ((1 << 64) - 1 - (1 << 36) - ((1 << B) + 16) * (W * (1 << B) + 16)) >> B
 
 
 def to_limbs(x, n):
