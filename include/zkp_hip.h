@@ -399,13 +399,33 @@ int32_t zkp_json_range_proof_batch(zkp_ctx* ctx, const char* text, const uint64_
  * p->n_stride = n_bits/32: one key per proof, p->n receives the documents' keys (verify_self, range_proof_ni.rs:109-128).
  * p->n_stride = 0: p->n is the VERIFIER's key, an input that is never written; a document under another key is ZKP_DOC_INVALID
  * (RangeProofNi::verify asserts equality, :86), so no received document can change the key the others are verified under.
- * Writes p->range and p->ciphertext (inputs of the other entry points, hence const in the struct).  HOST pointers only (flags 0). */
+ * Writes p->range and p->ciphertext (inputs of the other entry points, hence const in the struct).
+ * flags 0: host arrays, tokenised on the host as described above.
+ * ZKP_F_DEVICE_PTRS: the p-> arrays and out_status are device memory (with n_stride == 0 the verifier's key p->n as well); text and
+ * offsets stay host memory.  The text is uploaded once and tokenised ON THE DEVICE (csrc/kernels_serde_scan.hpp): a document that is byte
+ * for byte what serde_json::to_string writes — compact, fields in declaration order, no escapes — is read there; any other document goes
+ * through the host tokeniser and is merged into the same arrays.  Arrays and statuses are those of the flags-0 call, byte for byte. */
 #define ZKP_BIGINT_DEC 0u     /* "1234": decimal string (serialize::bigint, serialize.rs:8-33) */
 #define ZKP_BIGINT_HEX 1u     /* "04d2": hex string of the big-endian magnitude */
 #define ZKP_BIGINT_BYTES 2u   /* [4,210]: array of big-endian byte values */
 #define ZKP_BIGINT_FORMS(key_form, bare_form) (((key_form) << 4) | (bare_form))
 int32_t zkp_json_range_proof_ni_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t bigint_forms,
                                       const zkp_range_ni_proofs* p, uint8_t* out_status, uint32_t flags);
+/* RangeProofNi::verify / verify_self on documents: text in, one status byte and one verdict byte per document out.
+ * = zkp_json_range_proof_ni_batch (device route) into arrays the call owns, then zkp_range_ni_verify_batch on them; no limb leaves the device.
+ * text, doc_off, doc_len and verifier_n are host memory; ZKP_F_DEVICE_PTRS applies to out_status and out_verdict only.
+ * verifier_n [n_bits/32]: RangeProofNi::verify under that key (a document under another key: ZKP_DOC_INVALID); NULL: verify_self, every
+ * document under its own key.  out_status[b]: ZKP_DOC_*, exactly what zkp_json_range_proof_ni_batch gives for the document in that key
+ * mode.  out_verdict[b]: what zkp_range_ni_verify_batch gives for the converted document where the status is ZKP_DOC_OK, and
+ * ZKP_VERDICT_REJECT everywhere else, so a caller who ignores the status never accepts an unread proof (ZKP_DOC_HOST_PATH documents do
+ * have a verdict in the reference: the caller's host path, see above).
+ * The WHOLE batch is verified and the verdicts of unconverted documents are MASKED AFTERWARDS: such a document leaves zero rows (and, with
+ * verify_self, a zero key), which costs its share of the launch, changes no other document's verdict and never fails the call. */
+int32_t zkp_range_ni_verify_json_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len,
+                                       uint64_t batch, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms,
+                                       const uint32_t* verifier_n /* [kw], NULL = verify_self: each document's own key */,
+                                       uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */,
+                                       uint32_t flags);
 /* {"sigma_vec":["..", x11]} -> sigma [B][11][n_bits/32] */
 int32_t zkp_json_correct_key_proof_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
                                          uint64_t batch, uint32_t* out_sigma, uint8_t* out_status, uint32_t flags);

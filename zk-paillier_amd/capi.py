@@ -60,6 +60,8 @@ DIAG_EXPORTS = {
     "zkp_diag_set_key_cache": (C.c_int32, [C.c_void_p, C.c_int32]),
     "zkp_diag_key_cache_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
     "zkp_diag_witness_residue": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "zkp_diag_last_json_scan": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "zkp_diag_last_json_scan_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 ENC_FORM_AUTO, ENC_FORM_N2, ENC_FORM_SHARED, ENC_FORM_ALWAYS = 0, 1, 2, 3
 ENC_FORMS = {"auto": ENC_FORM_AUTO, "n2": ENC_FORM_N2, "shared": ENC_FORM_SHARED, "basen": ENC_FORM_ALWAYS, "always": ENC_FORM_ALWAYS}
@@ -108,6 +110,8 @@ EXPORTS = {
     "zkp_json_encrypted_pairs_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint32]),
     "zkp_json_range_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint32]),
     "zkp_json_range_proof_ni_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint32]),
+    "zkp_range_ni_verify_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_correct_key_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_doc_bound": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "zkp_json_write_encrypted_pairs_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -600,12 +604,42 @@ class Context:
         self.check(self.lib.zkp_json_range_proof_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), C.byref(proofs), ptr(out_status),
                                                        ZKP_F_DEVICE_PTRS if device else 0))
 
-    def json_range_proof_ni(self, docs, forms: int, proofs, out_status):
-        """whole RangeProofNi documents -> every field of the (host) batch; forms = bigint_forms(key_form, bare_form): BIGINT_DEC /
+    def json_range_proof_ni(self, docs, forms: int, proofs, out_status, device: bool = False):
+        """whole RangeProofNi documents -> every field of the batch; forms = bigint_forms(key_form, bare_form): BIGINT_DEC /
         BIGINT_HEX / BIGINT_BYTES for the un-annotated ek.n and, separately, for range / ciphertext.  With a shared key proofs.n is
-        the verifier's key (an input)."""
+        the verifier's key (an input).  device: the batch and out_status live in device memory and the documents are tokenised
+        there (the documents themselves stay host text)."""
         buf, off, ln = self._json_docs(docs)
-        self.check(self.lib.zkp_json_range_proof_ni_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), forms, C.byref(proofs), ptr(out_status), 0))
+        self.check(self.lib.zkp_json_range_proof_ni_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), forms, C.byref(proofs), ptr(out_status),
+                                                          ZKP_F_DEVICE_PTRS if device else 0))
+
+    def range_ni_verify_json(self, docs, forms: int, n_bits: int, ef: int, verifier_n=None, device: bool = False, out_status=None, out_verdict=None):
+        """zkp_range_ni_verify_json_batch: documents -> (status, verdict) bytes, one pair per document.  verifier_n: numpy [n_bits / 32]
+        (RangeProofNi::verify under that key) or None (verify_self).  device: the two outputs are torch cuda tensors (made here
+        when not given)."""
+        buf, off, ln = self._json_docs(docs)
+        B = len(docs)
+        if out_status is None or out_verdict is None:
+            if device:
+                import torch
+                out_status = torch.zeros(B, dtype=torch.uint8, device="cuda"); out_verdict = torch.zeros(B, dtype=torch.uint8, device="cuda")
+            else:
+                out_status = np.zeros(B, np.uint8); out_verdict = np.zeros(B, np.uint8)
+        self.check(self.lib.zkp_range_ni_verify_json_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), B, n_bits, ef, forms, ptr(verifier_n),
+                                                           ptr(out_status), ptr(out_verdict), ZKP_F_DEVICE_PTRS if device else 0))
+        return out_status, out_verdict
+
+    def last_json_scan(self):
+        """(documents the device scanner took, documents it left to the host tokeniser) of the most recent scanning call"""
+        fast, fb = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.zkp_diag_last_json_scan(self.h, C.byref(fast), C.byref(fb)))
+        return fast.value, fb.value
+
+    def last_json_scan_ms(self):
+        """(upload, scan, convert + merge, verify) milliseconds of the most recent scanning call, between HIP events on the ctx stream"""
+        out = (C.c_double * 4)()
+        self.check(self.lib.zkp_diag_last_json_scan_ms(self.h, out))
+        return tuple(out)
 
     def json_correct_key_proof(self, docs, n_bits, out_sigma, out_status):
         buf, off, ln = self._json_docs(docs)

@@ -22,6 +22,7 @@
 #include "kernels_inv.hpp"
 #include "kernels_serde.hpp"
 #include "kernels_serde_write.hpp"
+#include "kernels_serde_scan.hpp"
 #include "kernels_sample.hpp"
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
@@ -80,6 +81,11 @@ struct zkp_ctx {
   std::vector<hipEvent_t> ev_pipe;
   bool copy_busy = false;        // copies enqueued on `copy` that nothing has waited for yet
   int last_host_blocks = 0;      // proof blocks of the most recent RangeProofNi host-pointer call (1: the plain path)
+  // the most recent call that read documents through the device scanner (kernels_serde_scan.hpp): documents it took / left to the host
+  // tokeniser, and the call's phases on the stream (upload, scan, convert + merge, verify) between events created on first use
+  uint64_t scan_fast = 0, scan_fallback = 0;
+  hipEvent_t ev_scan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int scan_phases = 0;           // events of ev_scan recorded by that call
   // A RangeProofNi call of 65 ... 96 proofs under one 2048-bit key runs as TWO concurrent calls (range_split in zkp_api_proofs.inc): one
   // wavefront per SIMD of the mid engine (64 proofs) on this ctx's stream, the rest on a second ctx of the latency engine with a stream of
   // its own — created on first use.  $ZKP_SPLIT=0 at zkp_ctx_create / zkp_diag_set_split turn it off.
@@ -952,6 +958,7 @@ extern "C" int32_t zkp_ctx_destroy(zkp_ctx* c) try {
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
   for (hipEvent_t e : c->ev_pipe) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_scan) if (e) (void)hipEventDestroy(e);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);

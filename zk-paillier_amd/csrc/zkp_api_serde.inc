@@ -492,7 +492,8 @@ extern "C" int32_t zkp_json_correct_key_proof_batch(zkp_ctx* c, const char* text
 //   ZKP_BIGINT_DEC   "1234"            decimal string (what serialize::bigint writes)
 //   ZKP_BIGINT_HEX   "04d2"            hex string of the big-endian magnitude (either case, odd length allowed)
 //   ZKP_BIGINT_BYTES [4,210]           array of big-endian byte values (serde_json's rendering of serialize_bytes)
-// EncryptionKey: an object with a field "n" in that form (other fields, e.g. "nn", are skipped).  Host pointers only.
+// EncryptionKey: an object with a field "n" in that form (other fields, e.g. "nn", are skipped).  This is the host-pointer reader (flags 0);
+// with ZKP_F_DEVICE_PTRS the documents go through the device scanner first (json_ni_scan below) and only its fall-backs come here.
 namespace {
 // -> 0 converted; ZKP_DOC_HOST_PATH: an integer this width cannot carry (negative or too wide; the token is consumed, dst is zero);
 // ZKP_DOC_INVALID: not an integer of this text form (j.ok = false)
@@ -551,16 +552,220 @@ int parse_bigint_value(JCur& j, uint32_t enc, uint32_t* dst, uint32_t words) {
 }
 }  // namespace
 
+// ---- the same documents through the device scanner (kernels_serde_scan.hpp): the text is uploaded once and tokenised there; what the
+// scanner does not take byte for byte goes through the host reader above, unchanged, and is merged into the same device arrays.
+namespace {
+int32_t scan_event(zkp_ctx* c, int k) {
+  if (!c->ev_scan[k]) HIPCHK(c, hipEventCreate(&c->ev_scan[k]));
+  HIPCHK(c, hipEventRecord(c->ev_scan[k], c->stream));
+  c->scan_phases = k + 1;
+  return ZKP_OK;
+}
+template <class T> int32_t scan_merge(zkp_ctx* c, Stage& s, const std::vector<T>& host, T* dst, uint64_t units_per_doc, const uint32_t* didx, uint64_t docs) {
+  const T* src = s.host_in(host.data(), host.size());
+  if (s.st) return s.st;
+  const uint64_t total = docs * units_per_doc;
+  hipLaunchKernelGGL(k_scan_merge<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, src, dst, units_per_doc, didx, docs);
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+
+// d: every array of the batch in device memory; d.n is the verifier's key when d.n_stride == 0 (an input), else it receives the documents' keys.
+// Statuses and arrays are what zkp_json_range_proof_ni_batch gives on host arrays, byte for byte:
+//   - a scanned document has no malformed number and no sign, so the only status left is k_dec2bin's overflow (ZKP_DOC_HOST_PATH);
+//   - the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader decides before
+//     it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH.
+int32_t json_ni_scan(zkp_ctx* c, Stage& s, const char* name, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                     const zkp_range_ni_proofs& d, uint8_t* dstat) {
+  const uint64_t B = d.batch, EF = d.error_factor, rows = B * EF;
+  const uint32_t kw = d.n_bits / 32;
+  const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
+  const bool per_key = d.n_stride != 0;
+  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
+  int32_t st = scan_event(c, 0);
+  if (st) return st;
+  uint64_t lo = ~0ull, hi = 0;
+  for (uint64_t b = 0; b < B; b++) if (doc_len[b]) { lo = std::min(lo, doc_off[b]); hi = std::max(hi, doc_off[b] + doc_len[b]); }
+  if (hi == 0) lo = 0;
+  const uint64_t span = hi - lo;
+  ScanJob J{};
+  char* dtext = (char*)s.take(span + 16);
+  J.doc_off = s.host_in(doc_off, B); J.doc_len = s.host_in(doc_len, B);
+  J.text = dtext; J.lo = lo; J.B = B; J.zero_at = span;
+  J.max_len = zkp_json_doc_bound(ZKP_JSON_DOC_RANGE_PROOF_NI, d.n_bits, d.error_factor, forms);
+  J.ef = (uint32_t)EF; J.kw = kw; J.key_form = key_form; J.bare_form = bare_form;
+  J.dig_n = zkp_decimal_pitch(kw) - 1; J.dig_c = zkp_decimal_pitch(2 * kw) - 1;      // (max_digits below)
+  uint32_t* const out_range = const_cast<uint32_t*>(d.range);
+  uint32_t* const out_ct = const_cast<uint32_t*>(d.ciphertext);
+  J.keys = per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4);
+  J.range = out_range; J.ct = out_ct; J.kind = d.resp_kind; J.j = d.resp_j;
+  for (int a = 0; a < W_ARRS; a++) {
+    const bool head = a < W_ARR_C1;
+    if (head && (a == W_ARR_N ? key_form : bare_form) != ZKP_BIGINT_DEC) continue;
+    J.items[a] = (zkp_dec_item*)s.take((head ? B : rows) * sizeof(zkp_dec_item));
+  }
+  J.row_doc = (uint32_t*)s.take(rows * 4); J.head_doc = (uint32_t*)s.take(B * 4);
+  J.fast = (uint8_t*)s.take(B); J.status = dstat;
+  uint8_t* item_status = (uint8_t*)s.take(std::max<uint64_t>(rows, B));
+  if (s.st) return s.st;
+  struct Target { int arr; uint32_t* dst; uint32_t words; };
+  const Target targets[W_ARRS] = {{W_ARR_N, J.keys, kw}, {W_ARR_RANGE, out_range, kw}, {W_ARR_CT, out_ct, 2 * kw}, {W_ARR_C1, d.c1, 2 * kw}, {W_ARR_C2, d.c2, 2 * kw},
+                                  {W_ARR_W1, d.resp_w1, kw}, {W_ARR_R1, d.resp_r1, kw}, {W_ARR_W2, d.resp_w2, kw}, {W_ARR_R2, d.resp_r2, kw}};
+  if (span) HIPCHK(c, hipMemcpyAsync(dtext, text + lo, span, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(dtext + span, '0', 16, c->stream));
+  for (const Target& t : targets) HIPCHK(c, hipMemsetAsync(t.dst, 0, (t.arr < W_ARR_C1 ? B : rows) * t.words * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(d.resp_kind, 0, rows, c->stream));
+  HIPCHK(c, hipMemsetAsync(d.resp_j, 0, rows, c->stream));
+  if ((st = scan_event(c, 1))) return st;
+  hipLaunchKernelGGL(k_json_scan, dim3((unsigned)B), dim3(64), 0, c->stream, J);
+  HIPCHK(c, hipGetLastError());
+  if ((st = scan_event(c, 2))) return st;
+  auto convert = [&](const Target& t) -> int32_t {
+    if (!J.items[t.arr]) return ZKP_OK;                      // a head integer in hex / byte-array form: the scanner wrote its limbs
+    const bool head = t.arr < W_ARR_C1;
+    const uint64_t count = head ? B : rows;
+    const int32_t e = launch_dec2bin(c, dtext, J.items[t.arr], count, t.dst, item_status, t.words);
+    if (e) return e;
+    hipLaunchKernelGGL(k_mark_docs, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, item_status, head ? J.head_doc : J.row_doc, count, dstat, 0);
+    HIPCHK(c, hipGetLastError());
+    return ZKP_OK;
+  };
+  for (int a = 0; a < W_ARR_C1 && !st; a++) st = convert(targets[a]);
+  if (st) return st;
+  if (!per_key) {
+    hipLaunchKernelGGL(k_scan_key_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)J.keys, d.n, kw, B, (const uint8_t*)J.fast, dstat);
+    HIPCHK(c, hipGetLastError());
+  }
+  for (int a = W_ARR_C1; a < W_ARRS && !st; a++) st = convert(targets[a]);
+  if (st) return st;
+  for (const Target& t : targets) {
+    if (t.arr == W_ARR_N && !per_key) continue;
+    clear_failed_docs(c, dstat, t.dst, (t.arr < W_ARR_C1 ? 1 : EF) * t.words, B);
+  }
+  clear_failed_docs(c, dstat, d.resp_kind, EF, B); clear_failed_docs(c, dstat, d.resp_j, EF, B);
+  HIPCHK(c, hipGetLastError());
+  // the documents the scanner left: the host reader, on host arrays of their own, merged into the batch
+  std::vector<uint8_t> fast(B);
+  HIPCHK(c, hipMemcpyAsync(fast.data(), J.fast, B, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<uint32_t> idx;
+  for (uint64_t b = 0; b < B; b++) if (!fast[b]) idx.push_back((uint32_t)b);
+  c->scan_fast = B - idx.size(); c->scan_fallback = idx.size();
+  if (!idx.empty()) {
+    const uint64_t nf = idx.size();
+    std::vector<uint64_t> foff(nf), flen(nf);
+    for (uint64_t i = 0; i < nf; i++) { foff[i] = doc_off[idx[i]]; flen[i] = doc_len[idx[i]]; }
+    std::vector<uint32_t> hn(per_key ? nf * kw : kw), hrange(nf * kw), hct(nf * 2 * kw), hc1(nf * EF * 2 * kw), hc2(nf * EF * 2 * kw), hw1(nf * EF * kw), hr1(nf * EF * kw),
+        hw2(nf * EF * kw), hr2(nf * EF * kw);
+    std::vector<uint8_t> hkind(nf * EF), hj(nf * EF), hst(nf, 0);
+    if (!per_key) { HIPCHK(c, hipMemcpyAsync(hn.data(), d.n, (size_t)kw * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+    zkp_range_ni_proofs hp = d;
+    hp.batch = nf; hp.n = hn.data(); hp.range = hrange.data(); hp.ciphertext = hct.data(); hp.c1 = hc1.data(); hp.c2 = hc2.data();
+    hp.resp_kind = hkind.data(); hp.resp_j = hj.data(); hp.resp_w1 = hw1.data(); hp.resp_r1 = hr1.data(); hp.resp_w2 = hw2.data(); hp.resp_r2 = hr2.data();
+    if ((st = zkp_json_range_proof_ni_batch(c, text, foff.data(), flen.data(), forms, &hp, hst.data(), 0))) { c->err = std::string(name) + ": host reader: " + c->err; return st; }
+    const uint32_t* didx = s.host_in(idx.data(), nf);
+    if (s.st) return s.st;
+    if (per_key) st = scan_merge(c, s, hn, J.keys, kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hrange, out_range, kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hct, out_ct, 2 * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hc1, d.c1, EF * 2 * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hc2, d.c2, EF * 2 * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hw1, d.resp_w1, EF * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hr1, d.resp_r1, EF * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hw2, d.resp_w2, EF * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hr2, d.resp_r2, EF * kw, didx, nf);
+    if (!st) st = scan_merge(c, s, hkind, d.resp_kind, EF, didx, nf);
+    if (!st) st = scan_merge(c, s, hj, d.resp_j, EF, didx, nf);
+    if (!st) st = scan_merge(c, s, hst, dstat, 1, didx, nf);
+    if (st) return st;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // the host vectors go out of scope
+  }
+  return scan_event(c, 3);
+}
+bool json_ni_common_args_ok(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t n_bits, uint32_t ef, uint32_t forms) {
+  return text && doc_off && doc_len && B <= (1ull << 24) && (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && ef != 0 && ef <= 256 && !(forms >> 8) &&
+         ((forms >> 4) & 15u) <= ZKP_BIGINT_BYTES && (forms & 15u) <= ZKP_BIGINT_BYTES;
+}
+}  // namespace
+
+extern "C" int32_t zkp_diag_last_json_scan(zkp_ctx* c, uint64_t* fast_docs, uint64_t* fallback_docs) {
+  if (!c || !fast_docs || !fallback_docs) return ZKP_EINVAL;
+  *fast_docs = c->scan_fast; *fallback_docs = c->scan_fallback;
+  return ZKP_OK;
+}
+extern "C" int32_t zkp_diag_last_json_scan_ms(zkp_ctx* c, double* out_ms) try {
+  if (!c || !out_ms) return ZKP_EINVAL;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 4; k++) {
+    float ms = 0;
+    if (k + 1 < c->scan_phases) HIPCHK(c, hipEventElapsedTime(&ms, c->ev_scan[k], c->ev_scan[k + 1]));
+    out_ms[k] = ms;
+  }
+  return ZKP_OK;
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_range_ni_verify_json_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t n_bits,
+                                                  uint32_t error_factor, uint32_t bigint_forms, const uint32_t* verifier_n, uint8_t* out_status,
+                                                  uint8_t* out_verdict, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  if ((flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !out_status || !out_verdict || !json_ni_common_args_ok(text, doc_off, doc_len, B, n_bits, error_factor, bigint_forms)) {
+    c->err = "zkp_range_ni_verify_json_batch: invalid argument"; return ZKP_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t kw = n_bits / 32, rows = B * error_factor;
+  Stage s(c, flags);
+  uint8_t* dstat = s.out(out_status, B);
+  uint8_t* dv = s.out(out_verdict, B);
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.error_factor = error_factor; d.batch = B; d.n_stride = verifier_n ? 0 : kw;
+  d.n = verifier_n ? s.host_in(verifier_n, kw) : (const uint32_t*)s.take(B * kw * 4);
+  d.range = (const uint32_t*)s.take(B * kw * 4); d.ciphertext = (const uint32_t*)s.take(B * 2 * kw * 4);
+  d.c1 = (uint32_t*)s.take(rows * 2 * kw * 4); d.c2 = (uint32_t*)s.take(rows * 2 * kw * 4);
+  d.resp_kind = (uint8_t*)s.take(rows); d.resp_j = (uint8_t*)s.take(rows);
+  d.resp_w1 = (uint32_t*)s.take(rows * kw * 4); d.resp_r1 = (uint32_t*)s.take(rows * kw * 4);
+  d.resp_w2 = (uint32_t*)s.take(rows * kw * 4); d.resp_r2 = (uint32_t*)s.take(rows * kw * 4);
+  int32_t st = s.st;
+  if (!st) st = json_ni_scan(c, s, "zkp_range_ni_verify_json_batch", text, doc_off, doc_len, bigint_forms, d, dstat);
+  // The whole batch is verified and the verdicts of the documents that were not converted are masked afterwards: their rows are zero, and
+  // with verify_self so is their key, which the verify kernels answer with a verdict of that proof alone (never an error of the call).
+  if (!st) st = zkp_range_ni_verify_batch(c, &d, dv, ZKP_F_DEVICE_PTRS);
+  if (!st) {
+    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
+  }
+  if (!st) st = scan_event(c, 4);
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
 extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t bigint_forms,
                                                  const zkp_range_ni_proofs* p, uint8_t* out_status, uint32_t flags) try {
   if (!c) return ZKP_EINVAL;
   if (!p || p->batch == 0) return ZKP_OK;
+  if (flags == ZKP_F_DEVICE_PTRS) {
+    // the batch and the statuses in device memory (with one shared key the verifier's key too): the device scanner's route
+    if (!out_status || !p->n || !p->range || !p->ciphertext || !p->c1 || !p->c2 || !p->resp_kind || !p->resp_j || !p->resp_w1 || !p->resp_r1 || !p->resp_w2 ||
+        !p->resp_r2 || (p->n_stride != 0 && p->n_stride != p->n_bits / 32) || !json_ni_common_args_ok(text, doc_off, doc_len, p->batch, p->n_bits, p->error_factor, bigint_forms)) {
+      c->err = "zkp_json_range_proof_ni_batch: invalid argument"; return ZKP_EINVAL;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    Stage s(c, flags);
+    int32_t st = json_ni_scan(c, s, "zkp_json_range_proof_ni_batch", text, doc_off, doc_len, bigint_forms, *p, out_status);
+    if (st && !s.st) s.st = st;
+    const int32_t fin = s.finish();
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+    return st ? st : fin;
+  }
   const uint64_t B = p->batch;
   const uint32_t kw = p->n_bits / 32;
   const uint32_t key_form = (bigint_forms >> 4) & 15u, bare_form = bigint_forms & 15u;
   if (flags != 0 || !text || !doc_off || !doc_len || !out_status || !p->n || !p->range || !p->ciphertext || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES ||
       (bigint_forms >> 8) || (p->n_stride != 0 && p->n_stride != kw) || (p->n_bits != 1024 && p->n_bits != 2048 && p->n_bits != 4096)) {
-    c->err = "zkp_json_range_proof_ni_batch: invalid argument (host pointers only)"; return ZKP_EINVAL;
+    c->err = "zkp_json_range_proof_ni_batch: invalid argument"; return ZKP_EINVAL;
   }
   // (range and ciphertext — and n with one key per proof — are inputs of every other entry point, hence const in the struct; here
   // they are what is produced.  With ONE shared key (n_stride == 0) p->n is the VERIFIER's key: an input, never written)

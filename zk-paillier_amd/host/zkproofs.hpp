@@ -647,6 +647,13 @@ class RangeProofNi {
     return r;
   }
   Result verify_self() const { Result r = verify_batch(ek, {this})[0]; (void)r.is_ok(); return r; }   // :109-128
+
+  // serde_json::from_str + verify (ek given) / verify_self (ek == nullptr) for whole batches of documents, one Result per document:
+  // zkp_range_ni_verify_json_batch tokenises, converts and verifies on the GPU; a document it hands back (ZKP_DOC_HOST_PATH: a valid
+  // RangeProofNi the fixed layout cannot carry) is parsed here and goes through verify_batch; a document that is no RangeProofNi, or —
+  // with ek — one made under another key, is the panic `from_str(..).unwrap()` / verify's assert_eq! is in the reference.
+  // forms = ZKP_BIGINT_FORMS(key form, bare form).  Defined behind serde_json, at the end of this header.
+  static std::vector<Result> verify_json_batch(const std::vector<std::string>& docs, uint32_t forms = 0, const EncryptionKey* ek = nullptr);
 };
 
 
@@ -1599,5 +1606,42 @@ inline RangeProofNi range_proof_ni_from_str(const std::string& doc, BigintText k
   return out;
 }
 }  // namespace serde_json
+
+inline std::vector<Result> RangeProofNi::verify_json_batch(const std::vector<std::string>& docs, uint32_t forms, const EncryptionKey* ek) {
+  const size_t B = docs.size();
+  if (B == 0) return {};
+  const auto kf = (serde_json::BigintText)((forms >> 4) & 15u), bf = (serde_json::BigintText)(forms & 15u);
+  auto parse = [&](const std::string& doc, RangeProofNi* out) -> std::string {
+    try { *out = serde_json::range_proof_ni_from_str(doc, kf, bf); return std::string(); } catch (const std::exception& e) { return e.what(); }
+  };
+  auto carried = [](const BigInt& n) { return !n.is_negative() && n.is_odd() && n.bit_length() <= 4096 && n.bit_length() >= 2; };
+  if (ek && !carried(ek->n)) return std::vector<Result>(B, Result::unsupported("RangeProofNi::verify: the key is not a positive odd integer of at most 4096 bits"));
+  // one key width per call: the verifier's, else that of the first document that parses and has a key the engine carries
+  uint32_t nb = ek ? width_for(ek->n) : 0;
+  for (size_t b = 0; b < B && nb == 0; b++) { RangeProofNi q; if (parse(docs[b], &q).empty() && carried(q.ek.n)) nb = width_for(q.ek.n); }
+  std::vector<Result> out(B, Result(false));
+  std::vector<uint8_t> status(B, ZKP_DOC_HOST_PATH), verdict(B, ZKP_VERDICT_REJECT);
+  if (nb) {
+    const uint32_t kw = nb / 32;
+    std::string text;
+    std::vector<uint64_t> off(B), len(B);
+    for (size_t b = 0; b < B; b++) { off[b] = text.size(); len[b] = docs[b].size(); text += docs[b]; }
+    std::vector<uint32_t> n(kw);
+    if (ek) ek->n.to_limbs(n.data(), kw);
+    Engine& e = Engine::instance();
+    if (zkp_range_ni_verify_json_batch(e.ctx(), text.data(), off.data(), len.data(), B, nb, SECURITY_PARAMETER, forms, ek ? n.data() : nullptr, status.data(),
+                                       verdict.data(), 0) != ZKP_OK)
+      throw std::runtime_error(std::string("zkp_range_ni_verify_json_batch: ") + zkp_last_error_string(e.ctx()));
+  }
+  for (size_t b = 0; b < B; b++) {
+    if (status[b] == ZKP_DOC_OK) { out[b] = Result(verdict[b] == ZKP_VERDICT_ACCEPT); continue; }
+    RangeProofNi q;
+    const std::string err = parse(docs[b], &q);
+    if (!err.empty()) { out[b] = Result::panicked("called `Result::unwrap()` on an `Err` value: " + err); continue; }
+    if (ek && !(q.ek == *ek)) { out[b] = Result::panicked("assertion failed: `(left == right)` ek"); continue; }
+    out[b] = verify_batch(q.ek, {&q})[0];       // ZKP_DOC_HOST_PATH (or a key of another width): the host path for integers of any size and sign
+  }
+  return out;
+}
 
 }  // namespace zkproofs
