@@ -576,6 +576,49 @@ pub fn correct_key_ni_verify_batch(items: &[(&EncryptionKey, &NiCorrectKeyProof)
     )
 }
 
+/// `serde_json::from_str::<NiCorrectKeyProof>` + `verify` for many (key, document) pairs in ONE `zkp_correct_key_ni_verify_json_batch`: the
+/// text is tokenised, converted and verified on the GPU.  Keys must share one width.  `None` for a pair: the key does not fit that width, or
+/// the document was not converted (`ZKP_DOC_INVALID`: serde's error; `ZKP_DOC_HOST_PATH`: a root the fixed layout cannot carry) — the caller
+/// keeps it on its serde + CPU path.
+pub fn correct_key_ni_verify_json_batch(items: &[(&EncryptionKey, &str)], salt: &[u8]) -> Option<Vec<Option<Verdict>>> {
+    if items.is_empty() {
+        return Some(Vec::new());
+    }
+    let n_bits = width_for(&items[0].0.n)?;
+    let kw = (n_bits / 32) as usize;
+    let mut slot: Vec<Option<usize>> = Vec::with_capacity(items.len());
+    let (mut n, mut text) = (Vec::<u32>::new(), Vec::<u8>::new());
+    let (mut off, mut len) = (Vec::<u64>::new(), Vec::<u64>::new());
+    for (ek, doc) in items.iter() {
+        let mut row_n = vec![0u32; kw];
+        if width_for(&ek.n) == Some(n_bits) && put_limbs(&mut row_n, &ek.n) {
+            n.extend_from_slice(&row_n);
+            off.push(text.len() as u64);
+            len.push(doc.len() as u64);
+            text.extend_from_slice(doc.as_bytes());
+            slot.push(Some(off.len() - 1));
+        } else {
+            slot.push(None);
+        }
+    }
+    let used = off.len();
+    let (mut status, mut verdict) = (vec![9u8; used], vec![9u8; used]);
+    if used > 0 {
+        text.push(b' '); // (never an empty buffer; no document reaches it)
+        with_ctx(|ctx| {
+            ok(unsafe {
+                sys::zkp_correct_key_ni_verify_json_batch(ctx, text.as_ptr() as *const std::os::raw::c_char, off.as_ptr(), len.as_ptr(), used as u64, n_bits, n.as_ptr(),
+                                                          salt.as_ptr(), salt.len() as u32, status.as_mut_ptr(), verdict.as_mut_ptr(), 0)
+            })
+        })?;
+    }
+    Some(
+        slot.iter()
+            .map(|s| s.and_then(|i| if status[i] != sys::ZKP_DOC_OK { None } else if verdict[i] == sys::ZKP_VERDICT_ACCEPT { Some(Verdict::Accept) } else { Some(Verdict::Reject) }))
+            .collect(),
+    )
+}
+
 /// Single-proof dispatch used by the patched `NiCorrectKeyProof::verify`.
 pub fn correct_key_ni_verify_one(proof: &NiCorrectKeyProof, ek: &EncryptionKey, salt: &[u8]) -> Option<Result<(), IncorrectProof>> {
     match correct_key_ni_verify_batch(&[(ek, proof)], salt)?.pop()?? {

@@ -148,6 +148,7 @@ extern "C" {
     pub fn zkp_json_range_proof_ni_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, bigint_forms: u32, p: *const zkp_range_ni_proofs, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_ni_verify_json_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, batch: u64, n_bits: u32, error_factor: u32, bigint_forms: u32, verifier_n: *const u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_correct_key_proof_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, n_bits: u32, batch: u64, out_sigma: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_correct_key_ni_verify_json_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, batch: u64, n_bits: u32, n: *const u32, salt: *const u8, salt_len: u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_doc_bound(doc_kind: u32, n_bits: u32, error_factor: u32, bigint_forms: u32) -> u64;
     pub fn zkp_json_write_encrypted_pairs_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_write_range_proof_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;

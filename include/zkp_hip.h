@@ -373,7 +373,8 @@ int32_t zkp_limbs_to_decimal_batch(zkp_ctx* ctx, const uint32_t* src, uint64_t s
  * and correct_key_ni.rs:35-39 ({"sigma_vec":[..]}).  The reader is as tolerant as serde_json with the derived Deserialize impls: white
  * space between tokens (to_string_pretty), object fields in any order, unknown fields skipped, string escapes decoded; duplicate
  * or missing fields, a Response with more than one variant key and values of the wrong JSON type are errors, as they are for serde.
- * The tokenising runs on the host (threads), every number is converted on the GPU into p->c1/c2 (pairs) or p->resp_*
+ * With flags == 0 the tokenising runs on the host (threads); with ZKP_F_DEVICE_PTRS on the device (see below
+ * zkp_json_correct_key_proof_batch).  Every number is converted on the GPU into p->c1/c2 (pairs) or p->resp_*
  * (proof); p->error_factor rows are expected.  out_status[b]:
  *   ZKP_DOC_OK        converted;
  *   ZKP_DOC_INVALID   document b is not a value of the expected type (serde_json::from_str is Err in Rust);
@@ -426,9 +427,27 @@ int32_t zkp_range_ni_verify_json_batch(zkp_ctx* ctx, const char* text, const uin
                                        const uint32_t* verifier_n /* [kw], NULL = verify_self: each document's own key */,
                                        uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */,
                                        uint32_t flags);
-/* {"sigma_vec":["..", x11]} -> sigma [B][11][n_bits/32] */
+/* {"sigma_vec":["..", x11]} -> sigma [B][11][n_bits/32].  A sigma_vec of another length is ZKP_DOC_INVALID; an over-wide or negative
+ * entry is ZKP_DOC_HOST_PATH (that entry is zero, the others are converted). */
 int32_t zkp_json_correct_key_proof_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
                                          uint64_t batch, uint32_t* out_sigma, uint8_t* out_status, uint32_t flags);
+/* The three readers above with ZKP_F_DEVICE_PTRS (outputs in device memory) take the route of zkp_json_range_proof_ni_batch: the text is
+ * uploaded once and tokenised ON THE DEVICE (csrc/kernels_serde_scan.hpp).  A document that is byte for byte what serde_json::to_string
+ * writes — {"c1":["D",..EF],"c2":["D",..EF]} / [ROW,..EF] / {"sigma_vec":["D",..11]}, compact, fields in declaration order, no escapes,
+ * every D of at most zkp_decimal_pitch(words) - 1 digits — is read there; any other document goes through the host tokeniser, as a
+ * sub-batch of the flags-0 call, and is merged into the same arrays.  Arrays and statuses are those of the flags-0 call, byte for byte.
+ *
+ * NiCorrectKeyProof::verify (correct_key_ni.rs:73-100) on documents: text in, one status byte and one verdict byte per document out.
+ * = zkp_json_correct_key_proof_batch (device route) into a sigma block the call owns, then zkp_correct_key_ni_verify_batch on it; no limb
+ * travels to the host.  text, doc_off, doc_len and salt are host memory; ZKP_F_DEVICE_PTRS applies to n, out_status and out_verdict.
+ * n [B][n_bits/32]: one key per document, as limbs.  out_status[b]: exactly what zkp_json_correct_key_proof_batch gives for document b.
+ * out_verdict[b]: what zkp_correct_key_ni_verify_batch gives for the converted proof where the status is ZKP_DOC_OK, ZKP_VERDICT_REJECT
+ * everywhere else.  The WHOLE batch is verified and the verdicts of unread documents are masked afterwards: such a document costs its
+ * share of the launch, changes no other verdict and never fails the call.  n_bits in {1024, 2048, 4096}, batch 0 .. 2^24. */
+int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len,
+                                             uint64_t batch, uint32_t n_bits, const uint32_t* n /* [B][n_bits/32], one key per document */,
+                                             const uint8_t* salt, uint32_t salt_len,
+                                             uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */, uint32_t flags);
 
 /* The SoA batch -> serde_json documents: the mirror images of the four readers.  The text is byte for byte what serde_json::to_string
  * gives for the reference's derives: compact, fields in declaration order, every annotated BigInt a decimal string as mpz_get_str writes

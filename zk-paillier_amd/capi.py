@@ -113,6 +113,8 @@ EXPORTS = {
     "zkp_range_ni_verify_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_correct_key_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_correct_key_ni_verify_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                         C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_doc_bound": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "zkp_json_write_encrypted_pairs_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_write_range_proof_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -645,6 +647,24 @@ class Context:
         buf, off, ln = self._json_docs(docs)
         self.check(self.lib.zkp_json_correct_key_proof_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), n_bits, len(docs), ptr(out_sigma),
                                                              ptr(out_status), self._flags(out_sigma, out_status)))
+
+    def correct_key_ni_verify_json(self, docs, n_bits: int, n, salt: bytes, device: bool = False, out_status=None, out_verdict=None):
+        """zkp_correct_key_ni_verify_json_batch: NiCorrectKeyProof documents -> (status, verdict) bytes, one pair per document.
+        n: [len(docs)][n_bits / 32], one key per document — numpy, or with device a torch cuda tensor like the two outputs (made here
+        when not given)."""
+        buf, off, ln = self._json_docs(docs)
+        B = len(docs)
+        if out_status is None or out_verdict is None:
+            if device:
+                import torch
+                out_status = torch.zeros(B, dtype=torch.uint8, device="cuda"); out_verdict = torch.zeros(B, dtype=torch.uint8, device="cuda")
+            else:
+                out_status = np.zeros(B, np.uint8); out_verdict = np.zeros(B, np.uint8)
+        sb = (C.c_uint8 * len(salt)).from_buffer_copy(salt) if salt else None
+        self.check(self.lib.zkp_correct_key_ni_verify_json_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), B, n_bits, ptr(n),
+                                                                 C.cast(sb, C.c_void_p) if sb else None, len(salt), ptr(out_status), ptr(out_verdict),
+                                                                 ZKP_F_DEVICE_PTRS if device else 0))
+        return out_status, out_verdict
 
     # ---- the writers: SoA batch -> serde_json documents (sizing call, one allocation, writing call)
     def _json_write(self, call, batch, out_status):

@@ -1,4 +1,4 @@
-// kernels_serde_scan.hpp — serde_json documents of a whole RangeProofNi -> the item lists of k_dec2bin, found on the GPU: the inverse of
+// kernels_serde_scan.hpp — serde_json documents of the four proof types -> the item lists of k_dec2bin, found on the GPU: the inverse of
 // the writer's grammar (w_slot() in kernels_serde_write.hpp).  One wavefront per document.
 //
 // CANONICAL is byte for byte what serde_json::to_string gives for the derives (and what the writer emits):
@@ -6,20 +6,26 @@
 //   ROW = {"Open":{"w1":"D","r1":"D","w2":"D","r2":"D"}} | {"Mask":{"j":U,"masked_x":"D","masked_r":"D"}}
 //   D = one or more of 0-9 (leading zeros allowed), at most as many as the widest value of the field has; U = 0 .. 255 without leading
 //   zeros; N = the batch's error_factor; X in the form the caller names: "D", a lower-case even-length hex string, or [U,U,..].
+// The other three kinds are pieces of that grammar, scanned by the same phases started at another literal (ScanShape):
+//   EncryptedPairs     {"c1":["D",..EF],"c2":["D",..EF]}
+//   Proof              [ROW,..EF]
+//   NiCorrectKeyProof  {"sigma_vec":["D",..11]}            one array instead of two
 // A document that differs in ONE byte from this is marked `fall back` and nothing else: the host tokeniser (zkp_api_serde.inc) reads it and
 // decides its status.  So the scanner never has an opinion about a document it does not fully understand, and for one it understands the
 // only thing left open is whether every number fits its field — k_dec2bin's overflow status, the host reader's ZKP_DOC_HOST_PATH.
 //
 // Phases inside the wavefront (every loop is bounded by the document's length, no byte outside [doc_off, doc_off + doc_len) is read):
-//   head    the three un-annotated integers: literal, value, literal ... — 64 bytes per step, the closing quote / bracket found by ballot
+//   head    (RangeProofNi only) the three un-annotated integers: literal, value, literal ... — 64 bytes per step, the closing quote /
+//           bracket found by ballot
 //   mark    one pass over the rest, 64 bytes per step: a digit behind a quote opens a number, `{"O` / `{"M` opens a row; ballots and
 //           popcounts number both (the slot of a number depends on the kinds of the rows before it) and count the non-digit bytes in
 //           front of every number.  Positions go to LDS.
 //   check   one lane per number / per row: the bytes between a number and the next one are exactly the literal the grammar puts there —
 //           that fixes the number's length — and the count of non-digit bytes between the two starts is exactly that literal's, so every
 //           byte of the number is a digit.  Literals, numbers and row openings tile the document: every byte has been compared.
-//   emit    zkp_dec_item records at fixed positions (document b, row r -> item b * EF + r of the array's list; an absent number — w2 / r2
-//           of a Mask row, everything of a fall-back document — is the item "0" into its own, already zero, destination)
+//   emit    zkp_dec_item records at fixed positions (document b, row r -> item b * EF + r of the array's list, element i of sigma_vec ->
+//           item b * 11 + i; an absent number — w2 / r2 of a Mask row, everything of a fall-back document — is the item "0" into its
+//           own, already zero, destination)
 #pragma once
 #include "kernels_serde.hpp"
 #include "kernels_serde_write.hpp"
@@ -37,14 +43,15 @@ struct ScanJob {
   uint64_t B;
   uint64_t zero_at;            // text[zero_at] == '0' (behind the span): the absent number
   uint64_t max_len;            // zkp_json_doc_bound: no canonical document is longer
-  uint32_t ef, kw, key_form, bare_form;
+  uint32_t doc_kind;           // W_DOC_*
+  uint32_t ef, kw, key_form, bare_form;      // ef: entries per array and rows per document (NiCorrectKeyProof: the 11 of sigma_vec)
   uint32_t dig_n, dig_c;       // decimal digits of the widest kw- / 2kw-word value
   uint32_t* keys;              // [B][kw] ek.n
   uint32_t* range; uint32_t* ct;
   uint8_t* kind; uint8_t* j;   // [B][EF], zero on entry
-  zkp_dec_item* items[W_ARRS]; // W_ARR_N, _RANGE, _CT: [B] (decimal forms only); W_ARR_C1 .. _R2: [B * EF]
+  zkp_dec_item* items[W_ARRS]; // W_ARR_N, _RANGE, _CT: [B] (decimal forms only); W_ARR_C1 .. _R2: [B * EF]; sigma_vec is W_ARR_W1, as for the writer
   uint32_t* row_doc;           // [B * EF] item -> document, for k_mark_docs
-  uint32_t* head_doc;          // [B]
+  uint32_t* head_doc;          // [B] (RangeProofNi only, like keys, range, ct)
   uint8_t* fast;               // [B] 1 = scanned here, 0 = fall back
   uint8_t* status;             // [B] ZKP_DOC_OK | ZKP_DOC_INVALID (a fall-back document, until the host reader has spoken)
 };
@@ -155,23 +162,82 @@ __device__ __forceinline__ const char* sc_after(bool mask, uint32_t f, uint32_t&
 // bytes of a row's opening up to its first number that are no digits: {"Open":{"w1":"  /  {"Mask":{"j":U,"masked_x":"
 __device__ __forceinline__ uint32_t sc_open_nd(bool mask) { return mask ? 26u : 14u; }
 
+// What the mark / check / emit phases need to know about a document kind: the arrays of strings in front of the rows, whether there are
+// rows, the literal in front of the first number (or row) and the one between the last number and the end of the document.
+struct ScanShape {
+  uint32_t arrs;                 // 2: c1, c2; 1: sigma_vec; 0: a bare Proof
+  uint32_t cnt;                  // entries per array
+  uint32_t arr_words, arr_dig;   // limbs and most digits of an entry
+  int arr_item;                  // W_ARR_* of the first array
+  bool rows;
+  const char* open; uint32_t open_n;
+  const char* close; uint32_t close_n, close_nd;      // (nd: its bytes that are no digits)
+};
+__device__ __forceinline__ ScanShape sc_shape(const ScanJob& J, const ScanLds& L) {
+  ScanShape S;
+  const bool ck = J.doc_kind == W_DOC_CK;
+  S.arrs = ck ? 1u : J.doc_kind == W_DOC_PROOF ? 0u : 2u;
+  S.cnt = J.ef;
+  S.arr_words = ck ? J.kw : 2 * J.kw; S.arr_dig = ck ? J.dig_n : J.dig_c;
+  S.arr_item = ck ? W_ARR_W1 : W_ARR_C1;
+  S.rows = J.doc_kind == W_DOC_NI || J.doc_kind == W_DOC_PROOF;
+  if (J.doc_kind == W_DOC_NI) {
+    S.open = ",\"encrypted_pairs\":{\"c1\":[\""; S.open_n = 27;
+    S.close = L.tail; S.close_n = 20 + (J.ef >= 100 ? 3 : J.ef >= 10 ? 2 : 1) + 1; S.close_nd = 21;
+  } else if (J.doc_kind == W_DOC_PROOF) {
+    S.open = "["; S.open_n = 1;
+    S.close = "\"}}]"; S.close_n = 4; S.close_nd = 4;
+  } else {
+    S.open = ck ? "{\"sigma_vec\":[\"" : "{\"c1\":[\""; S.open_n = ck ? 15 : 8;
+    S.close = "\"]}"; S.close_n = 3; S.close_nd = 3;
+  }
+  return S;
+}
+// the literal behind number k of the arrays (entry k % cnt of array k / cnt) and where it ends: the start of the next number, of row 0, or the
+// document's end.  nd: bytes between the starts of this number and of the next one that are no digits; nd_at: that count at the anchor
+__device__ __forceinline__ const char* sc_arr_after(const ScanShape& S, const ScanLds& L, uint32_t k, uint32_t len, uint32_t nd_total, uint32_t& n, uint32_t& nd,
+                                                    uint32_t& anchor, uint32_t& nd_at) {
+  const uint32_t which = k / S.cnt, i = k - which * S.cnt;
+  if (k + 1 < S.arrs * S.cnt) {
+    anchor = L.tok_pos[k + 1]; nd_at = L.tok_nd[k + 1];
+    if (i + 1 < S.cnt) { n = 3; nd = 3; return "\",\""; }
+    n = 10; nd = 9;
+    return "\"],\"c2\":[\"";
+  }
+  if (S.rows) { n = 13; nd = 13 + sc_open_nd(L.row_kind[0] != 0); anchor = L.row_pos[0]; nd_at = L.tok_nd[k + 1]; return "\"]},\"proof\":["; }
+  n = S.close_n; nd = S.close_nd; anchor = len; nd_at = nd_total;
+  return S.close;
+}
+// the same for number f of the nf numbers of row r (number k of the document)
+__device__ __forceinline__ const char* sc_row_after(const ScanShape& S, const ScanLds& L, uint32_t r, uint32_t f, uint32_t nf, bool mask, uint32_t k, uint32_t len,
+                                                    uint32_t nd_total, uint32_t& n, uint32_t& nd, uint32_t& anchor, uint32_t& nd_at) {
+  if (f + 1 < nf) { anchor = L.tok_pos[k + 1]; nd_at = L.tok_nd[k + 1]; return sc_after(mask, f, n, nd); }
+  if (r + 1 < S.cnt) { n = 4; nd = 4 + sc_open_nd(L.row_kind[r + 1] != 0); anchor = L.row_pos[r + 1]; nd_at = L.tok_nd[k + 1]; return "\"}},"; }
+  n = S.close_n; nd = S.close_nd; anchor = len; nd_at = nd_total;
+  return S.close;
+}
+
 // -> wave-uniform: document [t, t + len) is canonical.  On true: L holds its numbers and rows, head_* its head (already converted unless decimal)
-__device__ inline bool sc_scan_doc(const ScanJob& J, uint64_t b, const char* t, uint32_t len, uint64_t text_at, ScanLds& L, uint32_t& ntok, int lane) {
+__device__ inline bool sc_scan_doc(const ScanJob& J, const ScanShape& S, uint64_t b, const char* t, uint32_t len, uint64_t text_at, ScanLds& L, uint32_t& ntok, int lane) {
   const uint32_t ef = J.ef, kw = J.kw;
   uint32_t pos = 0;
-  if (!sc_lit(t, len, pos, "{\"ek\":{\"n\":", 11, lane)) return false;
-  pos += 11;
-  if (!sc_head_value(t, len, pos, J.key_form, kw, J.dig_n, J.keys + b * kw, J.items[W_ARR_N] ? J.items[W_ARR_N] + b : nullptr, text_at, b * kw, L, lane)) return false;
-  if (!sc_lit(t, len, pos, "},\"range\":", 10, lane)) return false;
-  pos += 10;
-  if (!sc_head_value(t, len, pos, J.bare_form, kw, J.dig_n, J.range + b * kw, J.items[W_ARR_RANGE] ? J.items[W_ARR_RANGE] + b : nullptr, text_at, b * kw, L, lane)) return false;
-  if (!sc_lit(t, len, pos, ",\"ciphertext\":", 14, lane)) return false;
-  pos += 14;
-  if (!sc_head_value(t, len, pos, J.bare_form, 2 * kw, J.dig_c, J.ct + b * 2 * kw, J.items[W_ARR_CT] ? J.items[W_ARR_CT] + b : nullptr, text_at, b * 2 * kw, L, lane)) return false;
+  if (J.doc_kind == W_DOC_NI) {
+    if (!sc_lit(t, len, pos, "{\"ek\":{\"n\":", 11, lane)) return false;
+    pos += 11;
+    if (!sc_head_value(t, len, pos, J.key_form, kw, J.dig_n, J.keys + b * kw, J.items[W_ARR_N] ? J.items[W_ARR_N] + b : nullptr, text_at, b * kw, L, lane)) return false;
+    if (!sc_lit(t, len, pos, "},\"range\":", 10, lane)) return false;
+    pos += 10;
+    if (!sc_head_value(t, len, pos, J.bare_form, kw, J.dig_n, J.range + b * kw, J.items[W_ARR_RANGE] ? J.items[W_ARR_RANGE] + b : nullptr, text_at, b * kw, L, lane)) return false;
+    if (!sc_lit(t, len, pos, ",\"ciphertext\":", 14, lane)) return false;
+    pos += 14;
+    if (!sc_head_value(t, len, pos, J.bare_form, 2 * kw, J.dig_c, J.ct + b * 2 * kw, J.items[W_ARR_CT] ? J.items[W_ARR_CT] + b : nullptr, text_at, b * 2 * kw, L, lane)) return false;
+  }
   const uint32_t T = pos;
-  if (!sc_lit(t, len, T, ",\"encrypted_pairs\":{\"c1\":[\"", 27, lane)) return false;
+  if (!sc_lit(t, len, T, S.open, S.open_n, lane)) return false;
 
   // ---- mark
+  const uint32_t na = S.arrs * S.cnt, want_rows = S.rows ? ef : 0u;
+  const uint32_t min_toks = na + 2 * want_rows, max_toks = na + 4 * want_rows;
   uint32_t toks = 0, rows = 0, nd_base = 0, last62 = 0, last63 = 0;
   bool over = false;
   for (uint32_t p0 = T; p0 < len; p0 += 64) {
@@ -191,36 +257,30 @@ __device__ inline bool sc_scan_doc(const ScanJob& J, uint64_t b, const char* t, 
     if (starts && k < (uint32_t)SCAN_MAX_TOK) { L.tok_pos[k] = p; L.tok_nd[k] = nd; }
     if (row && r < (uint32_t)SCAN_MAX_EF) { L.row_pos[r] = p - 2; L.row_tok[r] = k; L.row_kind[r] = ch == 'M'; }
     toks += (uint32_t)__popcll(m_start); rows += (uint32_t)__popcll(m_row); nd_base += (uint32_t)__popcll(m_nd);
-    over = toks > 6 * ef || rows > ef;
+    over = toks > max_toks || rows > want_rows;
     if (over) break;
   }
-  if (over || rows != ef || toks < 2 * ef + 2 * ef) return false;
+  if (over || rows != want_rows || toks < min_toks) return false;
   __syncthreads();
   ntok = toks;
   const uint32_t nd_total = nd_base;
-  if (L.tok_pos[0] != T + 27) return false;
+  if ((na ? L.tok_pos[0] : L.row_pos[0]) != T + S.open_n) return false;
 
   // ---- check
   bool bad = false;
-  // the pairs: number k = which * EF + i
-  for (uint32_t k = lane; k < 2 * ef; k += 64) {
-    const uint32_t i = k < ef ? k : k - ef;
-    const bool last = i == ef - 1, second = k >= ef;
-    const char* lit = !last ? "\",\"" : !second ? "\"],\"c2\":[\"" : "\"]},\"proof\":[";
-    const uint32_t n = !last ? 3 : !second ? 10 : 13;
-    uint32_t nd = !last ? 3 : !second ? 9 : 13;
+  // the arrays: number k = which * cnt + i
+  for (uint32_t k = lane; k < na; k += 64) {
+    uint32_t n, nd, anchor, nd_at;
+    const char* lit = sc_arr_after(S, L, k, len, nd_total, n, nd, anchor, nd_at);
     const uint32_t s = L.tok_pos[k];
-    uint32_t anchor = L.tok_pos[k + 1];
-    if (last && second) { anchor = L.row_pos[0]; nd += sc_open_nd(L.row_kind[0]); }
-    const bool fits = anchor > s + n && anchor - s - n <= J.dig_c;
-    bad = bad || !fits || !sc_eq(t, anchor - n, lit, n) || L.tok_nd[k + 1] - L.tok_nd[k] != nd;
+    const bool fits = anchor > s + n && anchor - s - n <= S.arr_dig;
+    bad = bad || !fits || !sc_eq(t, anchor - n, lit, n) || nd_at - L.tok_nd[k] != nd;
   }
   // the rows
-  const uint32_t tail_n = 20 + (ef >= 100 ? 3 : ef >= 10 ? 2 : 1) + 1;
-  for (uint32_t r = lane; r < ef; r += 64) {
+  for (uint32_t r = lane; r < want_rows; r += 64) {
     const bool mask = L.row_kind[r] != 0;
     const uint32_t R = L.row_pos[r], k0 = L.row_tok[r], nf = mask ? 2 : 4;
-    const uint32_t expect_k0 = r == 0 ? 2 * ef : L.row_tok[r - 1] + (L.row_kind[r - 1] ? 2u : 4u);
+    const uint32_t expect_k0 = r == 0 ? na : L.row_tok[r - 1] + (L.row_kind[r - 1] ? 2u : 4u);
     if (k0 != expect_k0 || k0 + nf > toks || (r == ef - 1 && k0 + nf != toks)) { bad = true; continue; }
     const uint32_t s0 = L.tok_pos[k0];
     // the opening
@@ -237,10 +297,7 @@ __device__ inline bool sc_scan_doc(const ScanJob& J, uint64_t b, const char* t, 
     for (uint32_t f = 0; f < nf; f++) {
       const uint32_t k = k0 + f, s = L.tok_pos[k];
       uint32_t n, nd, anchor, nd_at;
-      const char* lit;
-      if (f + 1 < nf) { lit = sc_after(mask, f, n, nd); anchor = L.tok_pos[k + 1]; nd_at = L.tok_nd[k + 1]; }
-      else if (r + 1 < ef) { lit = "\"}},"; n = 4; nd = 4 + sc_open_nd(L.row_kind[r + 1]); anchor = L.row_pos[r + 1]; nd_at = L.tok_nd[k + 1]; }
-      else { lit = L.tail; n = tail_n; nd = 21; anchor = len; nd_at = nd_total; }
+      const char* lit = sc_row_after(S, L, r, f, nf, mask, k, len, nd_total, n, nd, anchor, nd_at);
       const bool fits = anchor > s + n && anchor - s - n <= J.dig_n;
       bad = bad || !fits || !sc_eq(t, anchor - n, lit, n) || nd_at - L.tok_nd[k] != nd;
     }
@@ -254,7 +311,8 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
   const int lane = threadIdx.x;
   const uint32_t ef = J.ef, kw = J.kw;
   const uint64_t len64 = J.doc_len[b], off = J.doc_off[b];
-  if (lane == 0) {
+  const bool ni = J.doc_kind == W_DOC_NI;
+  if (ni && lane == 0) {
     // `"}}],"error_factor":N}`
     const char* head = "\"}}],\"error_factor\":";
     int n = 0;
@@ -265,11 +323,13 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
     L.tail[n++] = '}';
   }
   __syncthreads();
+  const ScanShape S = sc_shape(J, L);
   bool ok = len64 != 0 && len64 <= J.max_len;
   const uint64_t text_at = ok ? off - J.lo : 0;
   const char* t = J.text + text_at;
+  const uint32_t len = (uint32_t)len64;
   uint32_t ntok = 0;
-  if (ok) ok = sc_scan_doc(J, b, t, (uint32_t)len64, text_at, L, ntok, lane);
+  if (ok) ok = sc_scan_doc(J, S, b, t, len, text_at, L, ntok, lane);
   __syncthreads();
 
   // ---- emit
@@ -277,28 +337,27 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
   if (lane == 0) {
     J.fast[b] = ok ? 1 : 0;
     J.status[b] = ok ? ZKP_DOC_OK : ZKP_DOC_INVALID;
-    J.head_doc[b] = (uint32_t)b;
-    if (!ok) {
+    if (ni) J.head_doc[b] = (uint32_t)b;
+    if (ni && !ok) {
       if (J.items[W_ARR_N]) { zkp_dec_item it = none_n; it.dst_off = b * kw; J.items[W_ARR_N][b] = it; }
       if (J.items[W_ARR_RANGE]) { zkp_dec_item it = none_n; it.dst_off = b * kw; J.items[W_ARR_RANGE][b] = it; }
       if (J.items[W_ARR_CT]) { zkp_dec_item it = none_n; it.dst_off = b * 2 * kw; it.words = 2 * kw; J.items[W_ARR_CT][b] = it; }
     }
   }
-  for (uint32_t k = lane; k < 2 * ef; k += 64) {
-    const uint32_t which = k >= ef, i = k - which * ef;
-    const uint64_t slot = b * ef + i;
-    zkp_dec_item it{J.zero_at, slot * 2 * kw, 1, 2 * kw};
+  for (uint32_t k = lane; k < S.arrs * S.cnt; k += 64) {
+    const uint32_t which = k / S.cnt, i = k - which * S.cnt;
+    const uint64_t slot = b * S.cnt + i;
+    if (which == 0) J.row_doc[slot] = (uint32_t)b;
+    zkp_dec_item it{J.zero_at, slot * S.arr_words, 1, S.arr_words};
     if (ok) {
+      uint32_t n, nd, anchor, nd_at;
+      (void)sc_arr_after(S, L, k, len, 0, n, nd, anchor, nd_at);
       const uint32_t s = L.tok_pos[k];
-      const bool last = i == ef - 1;
-      const uint32_t n = !last ? 3 : !which ? 10 : 13;
-      const uint32_t anchor = last && which ? L.row_pos[0] : L.tok_pos[k + 1];
       it.text_off = text_at + s; it.len = anchor - s - n;
     }
-    J.items[W_ARR_C1 + which][slot] = it;
+    J.items[S.arr_item + which][slot] = it;
   }
-  const uint32_t tail_n = 20 + (ef >= 100 ? 3 : ef >= 10 ? 2 : 1) + 1;
-  for (uint32_t r = lane; r < ef; r += 64) {
+  for (uint32_t r = lane; S.rows && r < ef; r += 64) {
     const uint64_t slot = b * ef + r;
     J.row_doc[slot] = (uint32_t)b;
     const bool mask = ok && L.row_kind[r] != 0;
@@ -308,10 +367,8 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
       zkp_dec_item it{J.zero_at, slot * kw, 1, kw};
       if (f < nf) {
         const uint32_t k = L.row_tok[r] + f, s = L.tok_pos[k];
-        uint32_t n, nd, anchor;
-        if (f + 1 < nf) { (void)sc_after(mask, f, n, nd); anchor = L.tok_pos[k + 1]; }
-        else if (r + 1 < ef) { n = 4; anchor = L.row_pos[r + 1]; }
-        else { n = tail_n; anchor = (uint32_t)len64; }
+        uint32_t n, nd, anchor, nd_at;
+        (void)sc_row_after(S, L, r, f, nf, mask, k, len, 0, n, nd, anchor, nd_at);
         it.text_off = text_at + s; it.len = anchor - s - n;
       }
       J.items[W_ARR_W1 + f][slot] = it;

@@ -270,6 +270,22 @@ int32_t convert_lists(zkp_ctx* c, const TextSpan& ts, std::vector<ItemList>& lis
 }
 }  // namespace
 
+// With ZKP_F_DEVICE_PTRS every reader goes through the device scanner (json_scan, further down): the text is uploaded once and tokenised
+// there, and only the documents it leaves come back to the reader's flags-0 path, as a sub-batch.
+namespace {
+int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat);
+int32_t json_scan_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                        const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* out_status) {
+  Stage s(c, ZKP_F_DEVICE_PTRS);
+  int32_t st = json_scan(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, sigma, out_status);
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
+}
+}  // namespace
+
 // kind: 0 = EncryptedPairs -> c1, c2; 1 = Proof -> resp_*
 static int32_t json_range_entry(zkp_ctx* c, const char* name, int kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len,
                                 const zkp_range_ni_proofs* p, uint8_t* out_status, uint32_t flags) {
@@ -282,6 +298,7 @@ static int32_t json_range_entry(zkp_ctx* c, const char* name, int kind, const ch
     c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL;
   }
   HIPCHK(c, hipSetDevice(c->device));
+  if (flags & ZKP_F_DEVICE_PTRS) return json_scan_entry(c, name, kind == 0 ? W_DOC_PAIRS : W_DOC_PROOF, text, doc_off, doc_len, 0, *p, nullptr, out_status);
   const uint64_t rows = B * EF;
   std::vector<uint8_t> status(B, 0), kinds, js;
   if (kind == 1) { kinds.assign(rows, 0); js.assign(rows, 0); }
@@ -432,6 +449,11 @@ extern "C" int32_t zkp_json_correct_key_proof_batch(zkp_ctx* c, const char* text
     c->err = "zkp_json_correct_key_proof_batch: invalid argument"; return ZKP_EINVAL;
   }
   HIPCHK(c, hipSetDevice(c->device));
+  if (flags & ZKP_F_DEVICE_PTRS) {
+    zkp_range_ni_proofs d{};
+    d.n_bits = n_bits; d.batch = B;
+    return json_scan_entry(c, "zkp_json_correct_key_proof_batch", W_DOC_CK, text, doc_off, doc_len, 0, d, out_sigma, out_status);
+  }
   const uint32_t kw = n_bits / 32;
   const uint64_t M2 = ZKP_CORRECT_KEY_M2;
   std::vector<uint8_t> status(B, 0);
@@ -493,7 +515,7 @@ extern "C" int32_t zkp_json_correct_key_proof_batch(zkp_ctx* c, const char* text
 //   ZKP_BIGINT_HEX   "04d2"            hex string of the big-endian magnitude (either case, odd length allowed)
 //   ZKP_BIGINT_BYTES [4,210]           array of big-endian byte values (serde_json's rendering of serialize_bytes)
 // EncryptionKey: an object with a field "n" in that form (other fields, e.g. "nn", are skipped).  This is the host-pointer reader (flags 0);
-// with ZKP_F_DEVICE_PTRS the documents go through the device scanner first (json_ni_scan below) and only its fall-backs come here.
+// with ZKP_F_DEVICE_PTRS the documents go through the device scanner first (json_scan below) and only its fall-backs come here.
 namespace {
 // -> 0 converted; ZKP_DOC_HOST_PATH: an integer this width cannot carry (negative or too wide; the token is consumed, dst is zero);
 // ZKP_DOC_INVALID: not an integer of this text form (j.ok = false)
@@ -570,14 +592,18 @@ template <class T> int32_t scan_merge(zkp_ctx* c, Stage& s, const std::vector<T>
   return ZKP_OK;
 }
 
-// d: every array of the batch in device memory; d.n is the verifier's key when d.n_stride == 0 (an input), else it receives the documents' keys.
-// Statuses and arrays are what zkp_json_range_proof_ni_batch gives on host arrays, byte for byte:
+// One batch of documents of one kind (W_DOC_*) into device memory.  d: the arrays of the kind (RangeProofNi: every one; EncryptedPairs: c1, c2;
+// Proof: resp_*; NiCorrectKeyProof: none of them — `sigma` [B][11][kw] instead, with d.n_bits and d.batch); d.n is the verifier's key when
+// d.n_stride == 0 (an input), else it receives the documents' keys.
+// Statuses and arrays are what the kind's reader gives with flags == 0 on host arrays, byte for byte:
 //   - a scanned document has no malformed number and no sign, so the only status left is k_dec2bin's overflow (ZKP_DOC_HOST_PATH);
-//   - the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader decides before
-//     it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH.
-int32_t json_ni_scan(zkp_ctx* c, Stage& s, const char* name, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                     const zkp_range_ni_proofs& d, uint8_t* dstat) {
-  const uint64_t B = d.batch, EF = d.error_factor, rows = B * EF;
+//   - RangeProofNi: the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader
+//     decides before it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH;
+//   - what was converted of a document that ends up unconverted is cleared where the host reader clears it: everywhere but in sigma.
+int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat) {
+  const bool ni = doc_kind == W_DOC_NI, ck = doc_kind == W_DOC_CK, has_pairs = ni || doc_kind == W_DOC_PAIRS, has_rows = ni || doc_kind == W_DOC_PROOF;
+  const uint64_t B = d.batch, EF = ck ? ZKP_CORRECT_KEY_M2 : d.error_factor, rows = B * EF;
   const uint32_t kw = d.n_bits / 32;
   const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
   const bool per_key = d.n_stride != 0;
@@ -592,30 +618,36 @@ int32_t json_ni_scan(zkp_ctx* c, Stage& s, const char* name, const char* text, c
   char* dtext = (char*)s.take(span + 16);
   J.doc_off = s.host_in(doc_off, B); J.doc_len = s.host_in(doc_len, B);
   J.text = dtext; J.lo = lo; J.B = B; J.zero_at = span;
-  J.max_len = zkp_json_doc_bound(ZKP_JSON_DOC_RANGE_PROOF_NI, d.n_bits, d.error_factor, forms);
-  J.ef = (uint32_t)EF; J.kw = kw; J.key_form = key_form; J.bare_form = bare_form;
+  J.max_len = zkp_json_doc_bound(doc_kind, d.n_bits, d.error_factor, forms);
+  J.doc_kind = doc_kind; J.ef = (uint32_t)EF; J.kw = kw; J.key_form = key_form; J.bare_form = bare_form;
   J.dig_n = zkp_decimal_pitch(kw) - 1; J.dig_c = zkp_decimal_pitch(2 * kw) - 1;      // (max_digits below)
   uint32_t* const out_range = const_cast<uint32_t*>(d.range);
   uint32_t* const out_ct = const_cast<uint32_t*>(d.ciphertext);
-  J.keys = per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4);
-  J.range = out_range; J.ct = out_ct; J.kind = d.resp_kind; J.j = d.resp_j;
-  for (int a = 0; a < W_ARRS; a++) {
-    const bool head = a < W_ARR_C1;
-    if (head && (a == W_ARR_N ? key_form : bare_form) != ZKP_BIGINT_DEC) continue;
-    J.items[a] = (zkp_dec_item*)s.take((head ? B : rows) * sizeof(zkp_dec_item));
+  if (ni) { J.keys = per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4); J.range = out_range; J.ct = out_ct; }
+  if (has_rows) { J.kind = d.resp_kind; J.j = d.resp_j; }
+  struct Target { int arr; uint32_t* dst; uint32_t words; };      // arr < W_ARR_C1: one number per document, else EF
+  std::vector<Target> targets;
+  if (ni) targets.insert(targets.end(), {{W_ARR_N, J.keys, kw}, {W_ARR_RANGE, out_range, kw}, {W_ARR_CT, out_ct, 2 * kw}});
+  if (has_pairs) targets.insert(targets.end(), {{W_ARR_C1, d.c1, 2 * kw}, {W_ARR_C2, d.c2, 2 * kw}});
+  if (has_rows) targets.insert(targets.end(), {{W_ARR_W1, d.resp_w1, kw}, {W_ARR_R1, d.resp_r1, kw}, {W_ARR_W2, d.resp_w2, kw}, {W_ARR_R2, d.resp_r2, kw}});
+  if (ck) targets.push_back({W_ARR_W1, sigma, kw});
+  for (const Target& t : targets) {
+    const bool head = t.arr < W_ARR_C1;
+    if (head && (t.arr == W_ARR_N ? key_form : bare_form) != ZKP_BIGINT_DEC) continue;
+    J.items[t.arr] = (zkp_dec_item*)s.take((head ? B : rows) * sizeof(zkp_dec_item));
   }
-  J.row_doc = (uint32_t*)s.take(rows * 4); J.head_doc = (uint32_t*)s.take(B * 4);
+  J.row_doc = (uint32_t*)s.take(rows * 4);
+  if (ni) J.head_doc = (uint32_t*)s.take(B * 4);
   J.fast = (uint8_t*)s.take(B); J.status = dstat;
   uint8_t* item_status = (uint8_t*)s.take(std::max<uint64_t>(rows, B));
   if (s.st) return s.st;
-  struct Target { int arr; uint32_t* dst; uint32_t words; };
-  const Target targets[W_ARRS] = {{W_ARR_N, J.keys, kw}, {W_ARR_RANGE, out_range, kw}, {W_ARR_CT, out_ct, 2 * kw}, {W_ARR_C1, d.c1, 2 * kw}, {W_ARR_C2, d.c2, 2 * kw},
-                                  {W_ARR_W1, d.resp_w1, kw}, {W_ARR_R1, d.resp_r1, kw}, {W_ARR_W2, d.resp_w2, kw}, {W_ARR_R2, d.resp_r2, kw}};
   if (span) HIPCHK(c, hipMemcpyAsync(dtext, text + lo, span, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(dtext + span, '0', 16, c->stream));
   for (const Target& t : targets) HIPCHK(c, hipMemsetAsync(t.dst, 0, (t.arr < W_ARR_C1 ? B : rows) * t.words * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.resp_kind, 0, rows, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.resp_j, 0, rows, c->stream));
+  if (has_rows) {
+    HIPCHK(c, hipMemsetAsync(d.resp_kind, 0, rows, c->stream));
+    HIPCHK(c, hipMemsetAsync(d.resp_j, 0, rows, c->stream));
+  }
   if ((st = scan_event(c, 1))) return st;
   hipLaunchKernelGGL(k_json_scan, dim3((unsigned)B), dim3(64), 0, c->stream, J);
   HIPCHK(c, hipGetLastError());
@@ -630,20 +662,22 @@ int32_t json_ni_scan(zkp_ctx* c, Stage& s, const char* name, const char* text, c
     HIPCHK(c, hipGetLastError());
     return ZKP_OK;
   };
-  for (int a = 0; a < W_ARR_C1 && !st; a++) st = convert(targets[a]);
+  for (const Target& t : targets) if (t.arr < W_ARR_C1 && !st) st = convert(t);
   if (st) return st;
-  if (!per_key) {
+  if (ni && !per_key) {
     hipLaunchKernelGGL(k_scan_key_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)J.keys, d.n, kw, B, (const uint8_t*)J.fast, dstat);
     HIPCHK(c, hipGetLastError());
   }
-  for (int a = W_ARR_C1; a < W_ARRS && !st; a++) st = convert(targets[a]);
+  for (const Target& t : targets) if (t.arr >= W_ARR_C1 && !st) st = convert(t);
   if (st) return st;
-  for (const Target& t : targets) {
-    if (t.arr == W_ARR_N && !per_key) continue;
-    clear_failed_docs(c, dstat, t.dst, (t.arr < W_ARR_C1 ? 1 : EF) * t.words, B);
+  if (!ck) {
+    for (const Target& t : targets) {
+      if (t.arr == W_ARR_N && !per_key) continue;
+      clear_failed_docs(c, dstat, t.dst, (t.arr < W_ARR_C1 ? 1 : EF) * t.words, B);
+    }
+    if (has_rows) { clear_failed_docs(c, dstat, d.resp_kind, EF, B); clear_failed_docs(c, dstat, d.resp_j, EF, B); }
+    HIPCHK(c, hipGetLastError());
   }
-  clear_failed_docs(c, dstat, d.resp_kind, EF, B); clear_failed_docs(c, dstat, d.resp_j, EF, B);
-  HIPCHK(c, hipGetLastError());
   // the documents the scanner left: the host reader, on host arrays of their own, merged into the batch
   std::vector<uint8_t> fast(B);
   HIPCHK(c, hipMemcpyAsync(fast.data(), J.fast, B, hipMemcpyDeviceToHost, c->stream));
@@ -655,27 +689,29 @@ int32_t json_ni_scan(zkp_ctx* c, Stage& s, const char* name, const char* text, c
     const uint64_t nf = idx.size();
     std::vector<uint64_t> foff(nf), flen(nf);
     for (uint64_t i = 0; i < nf; i++) { foff[i] = doc_off[idx[i]]; flen[i] = doc_len[idx[i]]; }
-    std::vector<uint32_t> hn(per_key ? nf * kw : kw), hrange(nf * kw), hct(nf * 2 * kw), hc1(nf * EF * 2 * kw), hc2(nf * EF * 2 * kw), hw1(nf * EF * kw), hr1(nf * EF * kw),
-        hw2(nf * EF * kw), hr2(nf * EF * kw);
-    std::vector<uint8_t> hkind(nf * EF), hj(nf * EF), hst(nf, 0);
-    if (!per_key) { HIPCHK(c, hipMemcpyAsync(hn.data(), d.n, (size_t)kw * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+    std::vector<std::vector<uint32_t>> h(W_ARRS);
+    for (const Target& t : targets) h[t.arr].resize(t.arr == W_ARR_N && !per_key ? kw : nf * (t.arr < W_ARR_C1 ? 1 : EF) * t.words);
+    std::vector<uint8_t> hkind(has_rows ? nf * EF : 0), hj(has_rows ? nf * EF : 0), hst(nf, 0);
+    if (ni && !per_key) { HIPCHK(c, hipMemcpyAsync(h[W_ARR_N].data(), d.n, (size_t)kw * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
     zkp_range_ni_proofs hp = d;
-    hp.batch = nf; hp.n = hn.data(); hp.range = hrange.data(); hp.ciphertext = hct.data(); hp.c1 = hc1.data(); hp.c2 = hc2.data();
-    hp.resp_kind = hkind.data(); hp.resp_j = hj.data(); hp.resp_w1 = hw1.data(); hp.resp_r1 = hr1.data(); hp.resp_w2 = hw2.data(); hp.resp_r2 = hr2.data();
-    if ((st = zkp_json_range_proof_ni_batch(c, text, foff.data(), flen.data(), forms, &hp, hst.data(), 0))) { c->err = std::string(name) + ": host reader: " + c->err; return st; }
+    hp.batch = nf; hp.n = h[W_ARR_N].data(); hp.range = h[W_ARR_RANGE].data(); hp.ciphertext = h[W_ARR_CT].data(); hp.c1 = h[W_ARR_C1].data(); hp.c2 = h[W_ARR_C2].data();
+    hp.resp_kind = hkind.data(); hp.resp_j = hj.data();
+    hp.resp_w1 = h[W_ARR_W1].data(); hp.resp_r1 = h[W_ARR_R1].data(); hp.resp_w2 = h[W_ARR_W2].data(); hp.resp_r2 = h[W_ARR_R2].data();
+    st = ni              ? zkp_json_range_proof_ni_batch(c, text, foff.data(), flen.data(), forms, &hp, hst.data(), 0)
+         : ck            ? zkp_json_correct_key_proof_batch(c, text, foff.data(), flen.data(), d.n_bits, nf, h[W_ARR_W1].data(), hst.data(), 0)
+         : has_pairs     ? zkp_json_encrypted_pairs_batch(c, text, foff.data(), flen.data(), &hp, hst.data(), 0)
+                         : zkp_json_range_proof_batch(c, text, foff.data(), flen.data(), &hp, hst.data(), 0);
+    if (st) { c->err = std::string(name) + ": host reader: " + c->err; return st; }
     const uint32_t* didx = s.host_in(idx.data(), nf);
     if (s.st) return s.st;
-    if (per_key) st = scan_merge(c, s, hn, J.keys, kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hrange, out_range, kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hct, out_ct, 2 * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hc1, d.c1, EF * 2 * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hc2, d.c2, EF * 2 * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hw1, d.resp_w1, EF * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hr1, d.resp_r1, EF * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hw2, d.resp_w2, EF * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hr2, d.resp_r2, EF * kw, didx, nf);
-    if (!st) st = scan_merge(c, s, hkind, d.resp_kind, EF, didx, nf);
-    if (!st) st = scan_merge(c, s, hj, d.resp_j, EF, didx, nf);
+    for (const Target& t : targets) {
+      if (t.arr == W_ARR_N && !per_key) continue;
+      if (!st) st = scan_merge(c, s, h[t.arr], t.dst, (t.arr < W_ARR_C1 ? 1 : EF) * t.words, didx, nf);
+    }
+    if (has_rows) {
+      if (!st) st = scan_merge(c, s, hkind, d.resp_kind, EF, didx, nf);
+      if (!st) st = scan_merge(c, s, hj, d.resp_j, EF, didx, nf);
+    }
     if (!st) st = scan_merge(c, s, hst, dstat, 1, didx, nf);
     if (st) return st;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the host vectors go out of scope
@@ -727,10 +763,44 @@ extern "C" int32_t zkp_range_ni_verify_json_batch(zkp_ctx* c, const char* text, 
   d.resp_w1 = (uint32_t*)s.take(rows * kw * 4); d.resp_r1 = (uint32_t*)s.take(rows * kw * 4);
   d.resp_w2 = (uint32_t*)s.take(rows * kw * 4); d.resp_r2 = (uint32_t*)s.take(rows * kw * 4);
   int32_t st = s.st;
-  if (!st) st = json_ni_scan(c, s, "zkp_range_ni_verify_json_batch", text, doc_off, doc_len, bigint_forms, d, dstat);
+  if (!st) st = json_scan(c, s, "zkp_range_ni_verify_json_batch", W_DOC_NI, text, doc_off, doc_len, bigint_forms, d, nullptr, dstat);
   // The whole batch is verified and the verdicts of the documents that were not converted are masked afterwards: their rows are zero, and
   // with verify_self so is their key, which the verify kernels answer with a verdict of that proof alone (never an error of the call).
   if (!st) st = zkp_range_ni_verify_batch(c, &d, dv, ZKP_F_DEVICE_PTRS);
+  if (!st) {
+    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
+  }
+  if (!st) st = scan_event(c, 4);
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
+// NiCorrectKeyProof::verify on documents: the same three steps with sigma in a block the call owns.  An unread document leaves zero (or, where
+// one number overflowed, partly converted) sigma rows: k_ck_check answers them with a verdict of that proof alone, masked afterwards.
+extern "C" int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t n_bits,
+                                                        const uint32_t* n, const uint8_t* salt, uint32_t salt_len, uint8_t* out_status, uint8_t* out_verdict,
+                                                        uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  if ((flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !text || !doc_off || !doc_len || !n || !out_status || !out_verdict || (salt_len && !salt) ||
+      (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24)) {
+    c->err = "zkp_correct_key_ni_verify_json_batch: invalid argument"; return ZKP_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t kw = n_bits / 32;
+  Stage s(c, flags);
+  uint8_t* dstat = s.out(out_status, B);
+  uint8_t* dv = s.out(out_verdict, B);
+  const uint32_t* dn = s.in(n, B * kw);
+  uint32_t* dsig = (uint32_t*)s.take(B * ZKP_CORRECT_KEY_M2 * kw * 4);
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.batch = B;
+  int32_t st = s.st;
+  if (!st) st = json_scan(c, s, "zkp_correct_key_ni_verify_json_batch", W_DOC_CK, text, doc_off, doc_len, 0, d, dsig, dstat);
+  if (!st) st = zkp_correct_key_ni_verify_batch(c, n_bits, B, dn, dsig, salt, salt_len, dv, ZKP_F_DEVICE_PTRS);
   if (!st) {
     hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
     if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
@@ -753,12 +823,7 @@ extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, c
       c->err = "zkp_json_range_proof_ni_batch: invalid argument"; return ZKP_EINVAL;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    Stage s(c, flags);
-    int32_t st = json_ni_scan(c, s, "zkp_json_range_proof_ni_batch", text, doc_off, doc_len, bigint_forms, *p, out_status);
-    if (st && !s.st) s.st = st;
-    const int32_t fin = s.finish();
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-    return st ? st : fin;
+    return json_scan_entry(c, "zkp_json_range_proof_ni_batch", W_DOC_NI, text, doc_off, doc_len, bigint_forms, *p, nullptr, out_status);
   }
   const uint64_t B = p->batch;
   const uint32_t kw = p->n_bits / 32;

@@ -886,6 +886,13 @@ class NiCorrectKeyProof {
     (void)r.is_ok();                          // a single proof panics right here, as the reference does
     return r;
   }
+  // serde_json::from_str + verify for whole batches of (key, document) pairs, one Result per pair: zkp_correct_key_ni_verify_json_batch
+  // tokenises, converts and verifies on the GPU (one call per key width).  A document it does not convert is parsed here: one that is no
+  // NiCorrectKeyProof is the panic `from_str(..).unwrap()` is in the reference; every other one (ZKP_DOC_HOST_PATH: a root the fixed
+  // layout cannot carry; a sigma_vec of another length), and every document under a key the engine does not take, goes through
+  // verify_batch.  Defined behind serde_json, at the end of this header.
+  static std::vector<Result> verify_json_batch(const std::vector<std::pair<const EncryptionKey*, std::string>>& items, const uint8_t* salt = SALT_STRING,
+                                               size_t salt_len = 4);
 };
 
 // ------------------------------------------------------------------ interactive CorrectKey (src/zkproofs/correct_key.rs:28-183)
@@ -1640,6 +1647,41 @@ inline std::vector<Result> RangeProofNi::verify_json_batch(const std::vector<std
     if (!err.empty()) { out[b] = Result::panicked("called `Result::unwrap()` on an `Err` value: " + err); continue; }
     if (ek && !(q.ek == *ek)) { out[b] = Result::panicked("assertion failed: `(left == right)` ek"); continue; }
     out[b] = verify_batch(q.ek, {&q})[0];       // ZKP_DOC_HOST_PATH (or a key of another width): the host path for integers of any size and sign
+  }
+  return out;
+}
+
+inline std::vector<Result> NiCorrectKeyProof::verify_json_batch(const std::vector<std::pair<const EncryptionKey*, std::string>>& items, const uint8_t* salt,
+                                                                size_t salt_len) {
+  const size_t B = items.size();
+  std::vector<Result> out(B, Result(false));
+  std::vector<uint8_t> status(B, ZKP_DOC_HOST_PATH), verdict(B, ZKP_VERDICT_REJECT);
+  auto carried = [](const BigInt& n) { return !n.is_negative() && n.is_odd() && n.bit_length() >= 2 && n.bit_length() <= 4096; };
+  Engine& e = Engine::instance();
+  for (uint32_t nb : {1024u, 2048u, 4096u}) {
+    const uint32_t kw = nb / 32;
+    std::vector<size_t> idx;
+    for (size_t k = 0; k < B; k++) if (carried(items[k].first->n) && width_for(items[k].first->n) == nb) idx.push_back(k);
+    if (idx.empty()) continue;
+    std::string text;
+    std::vector<uint64_t> off(idx.size()), len(idx.size());
+    std::vector<uint32_t> n(idx.size() * kw);
+    std::vector<uint8_t> st(idx.size(), ZKP_DOC_HOST_PATH), v(idx.size(), ZKP_VERDICT_REJECT);
+    for (size_t q = 0; q < idx.size(); q++) {
+      const std::string& doc = items[idx[q]].second;
+      off[q] = text.size(); len[q] = doc.size(); text += doc;
+      items[idx[q]].first->n.to_limbs(&n[q * kw], kw);
+    }
+    if (zkp_correct_key_ni_verify_json_batch(e.ctx(), text.data(), off.data(), len.data(), idx.size(), nb, n.data(), salt, (uint32_t)salt_len, st.data(), v.data(), 0) != ZKP_OK)
+      throw std::runtime_error(std::string("zkp_correct_key_ni_verify_json_batch: ") + zkp_last_error_string(e.ctx()));
+    for (size_t q = 0; q < idx.size(); q++) { status[idx[q]] = st[q]; verdict[idx[q]] = v[q]; }
+  }
+  for (size_t k = 0; k < B; k++) {
+    if (status[k] == ZKP_DOC_OK) { out[k] = Result(verdict[k] == ZKP_VERDICT_ACCEPT); continue; }
+    NiCorrectKeyProof q;
+    try { q = serde_json::correct_key_from_str_host(items[k].second); }
+    catch (const std::exception& err) { out[k] = Result::panicked(std::string("called `Result::unwrap()` on an `Err` value: ") + err.what()); continue; }
+    out[k] = verify_batch({{items[k].first, &q}}, salt, salt_len)[0];
   }
   return out;
 }
