@@ -678,6 +678,114 @@ pub fn dlog_prove_one(statement: &DLogStatement, secret: &BigInt) -> Option<Comp
     Some(CompositeDLogProof { x: get_limbs(&x), y: get_limbs(&y) })
 }
 
+/// `serde_json::from_str` of a `DLogStatement` and a `CompositeDLogProof` document + `verify`, for many pairs of ONE modulus width in one
+/// `zkp_dlog_verify_json_batch`: both documents are scanned, converted, range-checked and verified on the GPU.  `bare_form`: the text form
+/// curv's `BigInt` has in this build (`sys::ZKP_BIGINT_DEC` / `_HEX` / `_BYTES`).  `None` for a pair: it was not verified here
+/// (`ZKP_DOC_INVALID`: serde's error; `ZKP_DOC_HOST_PATH`: a field the layout cannot carry, an even N, g / ni / x >= N; or one of the
+/// reference's three assertions would panic) — the caller keeps it on its serde + GMP path, which gives the reference's answer.
+pub fn dlog_verify_json_batch(n_bits: u32, bare_form: u32, pairs: &[(&str, &str)]) -> Option<Vec<Option<Result<(), IncorrectProof>>>> {
+    if pairs.is_empty() {
+        return Some(Vec::new());
+    }
+    let b = pairs.len();
+    let mut text = Vec::<u8>::new();
+    let (mut s_off, mut s_len, mut p_off, mut p_len) = (Vec::<u64>::new(), Vec::<u64>::new(), Vec::<u64>::new(), Vec::<u64>::new());
+    for (statement, _) in pairs.iter() {
+        s_off.push(text.len() as u64);
+        s_len.push(statement.len() as u64);
+        text.extend_from_slice(statement.as_bytes());
+    }
+    for (_, proof) in pairs.iter() {
+        p_off.push(text.len() as u64);
+        p_len.push(proof.len() as u64);
+        text.extend_from_slice(proof.as_bytes());
+    }
+    text.push(b' '); // (never an empty buffer; no document reaches it)
+    let (mut status, mut verdict) = (vec![9u8; b], vec![9u8; b]);
+    with_ctx(|ctx| {
+        ok(unsafe {
+            sys::zkp_dlog_verify_json_batch(ctx, text.as_ptr() as *const std::os::raw::c_char, s_off.as_ptr(), s_len.as_ptr(), p_off.as_ptr(), p_len.as_ptr(), b as u64, n_bits,
+                                            DLOG_Y_BITS, bare_form, status.as_mut_ptr(), verdict.as_mut_ptr(), 0)
+        })
+    })?;
+    Some(
+        (0..b)
+            .map(|i| if status[i] != sys::ZKP_DOC_OK { None } else if verdict[i] == sys::ZKP_VERDICT_ACCEPT { Some(Ok(())) } else if verdict[i] == sys::ZKP_VERDICT_REJECT { Some(Err(IncorrectProof)) } else { None })
+            .collect(),
+    )
+}
+
+/// `zkp_json_dlog_statement_batch` on host arrays: N, g, ni `[B][n_bits / 32]`.  Returns the status bytes (`ZKP_DOC_*`).
+/// Safety: every output pointer holds `docs.len() * n_bits / 32` words.  (Device-resident outputs: `sys::` with `ZKP_F_DEVICE_PTRS`.)
+pub unsafe fn json_dlog_statement_batch(n_bits: u32, bare_form: u32, docs: &[&str], out_n: *mut u32, out_g: *mut u32, out_ni: *mut u32) -> Option<Vec<u8>> {
+    let (text, off, len) = pack_docs(docs);
+    let mut status = vec![9u8; docs.len()];
+    with_ctx(|ctx| ok(sys::zkp_json_dlog_statement_batch(ctx, text.as_ptr() as *const std::os::raw::c_char, off.as_ptr(), len.as_ptr(), n_bits, docs.len() as u64, bare_form, out_n, out_g, out_ni, status.as_mut_ptr(), 0)))?;
+    Some(status)
+}
+
+/// `zkp_json_dlog_proof_batch` on host arrays: x `[B][n_bits / 32]`, y `[B][768 / 32]`.
+pub unsafe fn json_dlog_proof_batch(n_bits: u32, bare_form: u32, docs: &[&str], out_x: *mut u32, out_y: *mut u32) -> Option<Vec<u8>> {
+    let (text, off, len) = pack_docs(docs);
+    let mut status = vec![9u8; docs.len()];
+    with_ctx(|ctx| ok(sys::zkp_json_dlog_proof_batch(ctx, text.as_ptr() as *const std::os::raw::c_char, off.as_ptr(), len.as_ptr(), n_bits, DLOG_Y_BITS, docs.len() as u64, bare_form, out_x, out_y, status.as_mut_ptr(), 0)))?;
+    Some(status)
+}
+
+fn pack_docs(docs: &[&str]) -> (Vec<u8>, Vec<u64>, Vec<u64>) {
+    let (mut text, mut off, mut len) = (Vec::<u8>::new(), Vec::<u64>::new(), Vec::<u64>::new());
+    for d in docs.iter() {
+        off.push(text.len() as u64);
+        len.push(d.len() as u64);
+        text.extend_from_slice(d.as_bytes());
+    }
+    text.push(b' ');
+    (text, off, len)
+}
+
+/// `serde_json::to_string` of many statements of one width in one `zkp_json_write_dlog_statement_batch` (sizing call, then the writing call).
+pub fn json_write_dlog_statement_batch(statements: &[&DLogStatement], bare_form: u32) -> Option<Vec<String>> {
+    if statements.is_empty() {
+        return Some(Vec::new());
+    }
+    let n_bits = width_for(&statements[0].N)?;
+    let kw = (n_bits / 32) as usize;
+    let b = statements.len();
+    let (mut nn, mut g, mut ni) = (vec![0u32; b * kw], vec![0u32; b * kw], vec![0u32; b * kw]);
+    for (k, s) in statements.iter().enumerate() {
+        if !(put_limbs(&mut nn[k * kw..(k + 1) * kw], &s.N) && put_limbs(&mut g[k * kw..(k + 1) * kw], &s.g) && put_limbs(&mut ni[k * kw..(k + 1) * kw], &s.ni)) {
+            return None;
+        }
+    }
+    write_docs(b, |ctx, text, cap, off| unsafe { sys::zkp_json_write_dlog_statement_batch(ctx, n_bits, b as u64, nn.as_ptr(), g.as_ptr(), ni.as_ptr(), bare_form, text, cap, off, ptr::null_mut(), 0) })
+}
+
+/// `serde_json::to_string` of many proofs under moduli of `n_bits` bits in one `zkp_json_write_dlog_proof_batch`.
+pub fn json_write_dlog_proof_batch(n_bits: u32, proofs: &[&CompositeDLogProof], bare_form: u32) -> Option<Vec<String>> {
+    if proofs.is_empty() {
+        return Some(Vec::new());
+    }
+    let (kw, yw) = ((n_bits / 32) as usize, (DLOG_Y_BITS / 32) as usize);
+    let b = proofs.len();
+    let (mut x, mut y) = (vec![0u32; b * kw], vec![0u32; b * yw]);
+    for (k, p) in proofs.iter().enumerate() {
+        if !(put_limbs(&mut x[k * kw..(k + 1) * kw], &p.x) && put_limbs(&mut y[k * yw..(k + 1) * yw], &p.y)) {
+            return None;
+        }
+    }
+    write_docs(b, |ctx, text, cap, off| unsafe { sys::zkp_json_write_dlog_proof_batch(ctx, n_bits, DLOG_Y_BITS, b as u64, x.as_ptr(), y.as_ptr(), bare_form, text, cap, off, ptr::null_mut(), 0) })
+}
+
+/// sizing call, one allocation, writing call; documents cut at the offsets
+fn write_docs<F: Fn(*mut sys::zkp_ctx, *mut std::os::raw::c_char, u64, *mut u64) -> i32>(b: usize, call: F) -> Option<Vec<String>> {
+    let mut off = vec![0u64; b + 1];
+    with_ctx(|ctx| ok(call(ctx, ptr::null_mut(), 0, off.as_mut_ptr())))?;
+    let mut text = vec![0u8; off[b] as usize + 1];
+    let total = off[b];
+    with_ctx(|ctx| ok(call(ctx, text.as_mut_ptr() as *mut std::os::raw::c_char, total, off.as_mut_ptr())))?;
+    Some((0..b).map(|k| String::from_utf8_lossy(&text[off[k] as usize..off[k + 1] as usize]).into_owned()).collect())
+}
+
 /// `CompositeDLogProof::verify` (wi_dlog_proof.rs:67-91).  `None` also when the reference's pre-checks would panic (:69,72,73):
 /// the GMP path then raises that panic.
 pub fn dlog_verify_one(proof: &CompositeDLogProof, statement: &DLogStatement) -> Option<Result<(), IncorrectProof>> {

@@ -40,6 +40,8 @@ pub const ZKP_JSON_DOC_ENCRYPTED_PAIRS: u32 = 0;
 pub const ZKP_JSON_DOC_RANGE_PROOF: u32 = 1;
 pub const ZKP_JSON_DOC_RANGE_PROOF_NI: u32 = 2;
 pub const ZKP_JSON_DOC_CORRECT_KEY_PROOF: u32 = 3;
+pub const ZKP_JSON_DOC_DLOG_PROOF: u32 = 5;
+pub const ZKP_JSON_DOC_DLOG_STATEMENT: u32 = 6;
 pub const ZKP_GATHER_HOST: u32 = 0;
 pub const ZKP_GATHER_RCCL: u32 = 1;
 pub const ZKP_GATHER_COPY: u32 = 2;
@@ -154,6 +156,11 @@ extern "C" {
     pub fn zkp_json_write_range_proof_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_write_range_proof_ni_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, bigint_forms: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_write_correct_key_proof_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, sigma: *const u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_dlog_statement_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, n_bits: u32, batch: u64, bare_form: u32, out_N: *mut u32, out_g: *mut u32, out_ni: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_dlog_proof_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, n_bits: u32, y_bits: u32, batch: u64, bare_form: u32, out_x: *mut u32, out_y: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_write_dlog_statement_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, N: *const u32, g: *const u32, ni: *const u32, bare_form: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_write_dlog_proof_batch(ctx: *mut zkp_ctx, n_bits: u32, y_bits: u32, batch: u64, x: *const u32, y: *const u32, bare_form: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_dlog_verify_json_batch(ctx: *mut zkp_ctx, text: *const c_char, st_off: *const u64, st_len: *const u64, pf_off: *const u64, pf_len: *const u64, batch: u64, n_bits: u32, y_bits: u32, bare_form: u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_multi_create(device_ids: *const i32, n_devices: u32, out: *mut *mut zkp_multi) -> i32;
     pub fn zkp_multi_destroy(m: *mut zkp_multi) -> i32;
     pub fn zkp_multi_size(m: *mut zkp_multi) -> u32;

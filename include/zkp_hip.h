@@ -459,8 +459,8 @@ int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* ctx, const char* text, con
  *   out_text == NULL: the sizing call — only the exact offsets are computed.  text_cap < out_doc_off[batch]: ZKP_EINVAL, the offsets
  *   are written, the error string names both numbers, no byte of out_text is touched.  zkp_json_doc_bound (a pure host function, no
  *   device needed): an upper bound of one document's length, so that batch * bound can be allocated once and the sizing call skipped;
- *   0 for arguments no writer accepts.  doc_kind: ZKP_JSON_DOC_*; error_factor is ignored for a NiCorrectKeyProof, bigint_forms for
- *   everything but a RangeProofNi.
+ *   0 for arguments no writer accepts.  doc_kind: ZKP_JSON_DOC_*; error_factor is ignored for a NiCorrectKeyProof and the two
+ *   DLog kinds, bigint_forms for everything but a RangeProofNi and the two DLog kinds (whose bare form it is).
  *   out_status [batch] (nullable): ZKP_DOC_OK, or ZKP_DOC_INVALID where a row of proof b has a resp_kind that is neither ZKP_RESP_OPEN nor
  *   ZKP_RESP_MASK: no Response has that variant, the document is empty (out_doc_off[b + 1] == out_doc_off[b]), the others are unaffected.
  *   resp_j is written as the byte it is.  Reads c1, c2 (pairs); resp_* (proof); every field (RangeProofNi: n_stride == 0 writes the
@@ -471,6 +471,9 @@ int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* ctx, const char* text, con
 #define ZKP_JSON_DOC_RANGE_PROOF 1u
 #define ZKP_JSON_DOC_RANGE_PROOF_NI 2u
 #define ZKP_JSON_DOC_CORRECT_KEY_PROOF 3u
+/* (4 is no kind, and stays none: zkp_json_doc_bound answers 0 for it, as callers written against the first four kinds expect) */
+#define ZKP_JSON_DOC_DLOG_PROOF 5u         /* bigint_forms = the bare form alone; error_factor is ignored; the bound is taken at y_bits == n_bits, */
+#define ZKP_JSON_DOC_DLOG_STATEMENT 6u     /* the widest y the entry points accept, so it holds for every y_bits */
 uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms);
 int32_t zkp_json_write_encrypted_pairs_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
                                              uint8_t* out_status, uint32_t flags);
@@ -480,6 +483,55 @@ int32_t zkp_json_write_range_proof_ni_batch(zkp_ctx* ctx, const zkp_range_ni_pro
                                             uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags);
 int32_t zkp_json_write_correct_key_proof_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* sigma, char* out_text, uint64_t text_cap,
                                                uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags);
+
+/* ------------------------------------------------------------------ CompositeDLogProof and DLogStatement as documents
+ * wi_dlog_proof.rs:32-43, field order of the derives:
+ *   CompositeDLogProof   {"x":X,"y":X}            x [B][kw], y [B][y_bits/32]
+ *   DLogStatement        {"N":X,"g":X,"ni":X}     N, g, ni [B][kw]
+ * kw = n_bits/32; n_bits in {1024, 2048, 4096}; y_bits a multiple of 32, 544 .. n_bits (as for zkp_dlog_verify_batch); batch 0 .. 2^24.
+ * Every X is an un-annotated curv BigInt; bare_form (ZKP_BIGINT_DEC / _HEX / _BYTES) names its text form and means exactly what it means
+ * for `range` and `ciphertext` of a RangeProofNi document.
+ *
+ * Readers.  out_status[b]: ZKP_DOC_OK; ZKP_DOC_INVALID (not a value of the type: a missing or duplicate field, a wrong JSON type, a string
+ * that is not an integer of the named form; every field of the document is zero); ZKP_DOC_HOST_PATH (a valid value the fixed layout
+ * cannot carry: a negative field, or one wider than its array; THAT field is zero, the others are converted).
+ * flags 0: host arrays, tokenised on the host by the tolerant tokeniser of the readers above (white space, any field order, unknown
+ * fields skipped, escapes in field names decoded).  ZKP_F_DEVICE_PTRS: outputs and status in device memory, text and offsets host memory;
+ * the text is uploaded once; a document that is byte for byte canonical — compact, fields in declaration order, X = "D" with at most
+ * zkp_decimal_pitch(words) - 1 digits | lower-case even-length hex of at most 8 * words characters | [U,..] of at most 4 * words byte
+ * values — is read on the device, any other falls back to the flags-0 path as a sub-batch and is merged in.  Arrays and statuses equal
+ * the flags-0 call's, byte for byte. */
+int32_t zkp_json_dlog_statement_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
+                                      uint64_t batch, uint32_t bare_form, uint32_t* out_N, uint32_t* out_g, uint32_t* out_ni,
+                                      uint8_t* out_status, uint32_t flags);
+int32_t zkp_json_dlog_proof_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
+                                  uint32_t y_bits, uint64_t batch, uint32_t bare_form, uint32_t* out_x, uint32_t* out_y,
+                                  uint8_t* out_status, uint32_t flags);
+/* Writers: the contract of the four writers above (sizing call with out_text == NULL, batch + 1 offsets of 64 bits, ZKP_EINVAL with no
+ * byte touched when text_cap is short, out_status nullable and always ZKP_DOC_OK here).  ZKP_F_DEVICE_PTRS applies to the limb arrays
+ * and out_status, so the output of zkp_dlog_prove_batch is serialised where it lies.  The text is what the readers call canonical:
+ * decimal without leading zeros, hex with two characters per byte of the magnitude ("00" for zero), byte arrays without a leading zero
+ * byte ([0] for zero). */
+int32_t zkp_json_write_dlog_statement_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* N, const uint32_t* g,
+                                            const uint32_t* ni, uint32_t bare_form, char* out_text, uint64_t text_cap,
+                                            uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags);
+int32_t zkp_json_write_dlog_proof_batch(zkp_ctx* ctx, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* x,
+                                        const uint32_t* y, uint32_t bare_form, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
+                                        uint8_t* out_status, uint32_t flags);
+/* CompositeDLogProof::verify (wi_dlog_proof.rs:67-91) on documents: statement b and proof b are two spans of the same `text` (host memory,
+ * uploaded once); one status byte and one verdict byte per pair come out; ZKP_F_DEVICE_PTRS applies to out_status and out_verdict only.
+ * = both readers (device route) into arrays the call owns, a domain check on the device, zkp_dlog_verify_batch on those arrays.
+ * out_status[b] starts as the worse of the two documents' statuses (ZKP_DOC_INVALID beats ZKP_DOC_HOST_PATH beats ZKP_DOC_OK).  A pair
+ * still OK becomes ZKP_DOC_HOST_PATH when N is even or zero, or one of g, ni, x is >= N: such a pair has a verdict in the reference
+ * (mod_pow reduces its base, x >= N never equals the product, an even N is legal), which the limb kernels cannot give; the caller's
+ * host path does (host/zkproofs.hpp: CompositeDLogProof::verify).  This is STRICTER than zkp_dlog_verify_batch, which assumes
+ * x, g, ni < N unchecked and reports an even N as ZKP_VERDICT_MALFORMED (its documented deviation): here no such pair reaches it.
+ * out_verdict[b]: what zkp_dlog_verify_batch gives where the status is ZKP_DOC_OK (ZKP_VERDICT_MALFORMED for the reference's three
+ * assertions included), ZKP_VERDICT_REJECT everywhere else.  The whole batch is launched and the verdicts of unread pairs are masked
+ * afterwards: such a pair is five zero rows, costs its share of the launch, changes no other verdict and never fails the call. */
+int32_t zkp_dlog_verify_json_batch(zkp_ctx* ctx, const char* text, const uint64_t* st_off, const uint64_t* st_len, const uint64_t* pf_off,
+                                   const uint64_t* pf_len, uint64_t batch, uint32_t n_bits, uint32_t y_bits, uint32_t bare_form,
+                                   uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */, uint32_t flags);
 
 /* ------------------------------------------------------------------ several GPUs behind one caller
  * The reference spreads a proof's rows over a rayon pool (src/zkproofs/range_proof.rs:161-187,270-348); here a batch

@@ -105,9 +105,12 @@ int32_t zkp_diag_key_cache_state(zkp_ctx* ctx, int32_t which, uint32_t* out);
 int32_t zkp_diag_witness_residue(zkp_ctx* ctx, uint64_t* out_nonzero_words);
 
 /* The most recent call of this ctx that read documents through the device scanner (zkp_range_ni_verify_json_batch,
- * zkp_correct_key_ni_verify_json_batch, any of the four zkp_json_*_batch readers with ZKP_F_DEVICE_PTRS): the documents the scanner took itself, and the documents it left to the host
- * tokeniser.  zkp_diag_last_json_scan_ms: that call's phases on the ctx stream, between HIP events, in milliseconds: out_ms[4] = {upload of
- * the text, scan, conversion and merge of the fall-back documents, verify (0 for the reader alone)}; synchronises the stream. */
+ * zkp_correct_key_ni_verify_json_batch, zkp_dlog_verify_json_batch, any of the six zkp_json_*_batch readers — zkp_json_dlog_statement_batch and
+ * zkp_json_dlog_proof_batch among them — with ZKP_F_DEVICE_PTRS): the documents the scanner took itself, and the documents it left to the host
+ * tokeniser (zkp_dlog_verify_json_batch scans twice: statements and proofs are counted together, 2 * batch documents).
+ * zkp_diag_last_json_scan_ms: that call's phases on the ctx stream, between HIP events, in milliseconds: out_ms[4] = {upload of
+ * the text, scan, conversion and merge of the fall-back documents, verify (0 for the reader alone)}; synchronises the stream.
+ * zkp_dlog_verify_json_batch: {upload, statements (scan, conversion, merge), proofs (the same), domain check and verify}. */
 int32_t zkp_diag_last_json_scan(zkp_ctx* ctx, uint64_t* fast_docs, uint64_t* fallback_docs);
 int32_t zkp_diag_last_json_scan_ms(zkp_ctx* ctx, double* out_ms);
 

@@ -120,6 +120,16 @@ EXPORTS = {
     "zkp_json_write_range_proof_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_write_range_proof_ni_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_json_write_correct_key_proof_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_dlog_statement_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_uint32]),
+    "zkp_json_dlog_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint32]),
+    "zkp_json_write_dlog_statement_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                        C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_write_dlog_proof_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                    C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_dlog_verify_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_correct_key_ni_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "zkp_dlog_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -193,6 +203,7 @@ BIGINT_DEC, BIGINT_HEX, BIGINT_BYTES = 0, 1, 2
 DOC_OK, DOC_INVALID, DOC_HOST_PATH = 0, 2, 3
 GATHER_HOST, GATHER_RCCL, GATHER_COPY = 0, 1, 2
 JSON_DOC_ENCRYPTED_PAIRS, JSON_DOC_RANGE_PROOF, JSON_DOC_RANGE_PROOF_NI, JSON_DOC_CORRECT_KEY_PROOF = 0, 1, 2, 3
+JSON_DOC_DLOG_PROOF, JSON_DOC_DLOG_STATEMENT = 5, 6
 
 
 def json_doc_bound(doc_kind: int, n_bits: int, error_factor: int = SECURITY_PARAMETER, forms: int = 0) -> int:
@@ -699,3 +710,42 @@ class Context:
         fl = self._flags(sigma, out_status)
         return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_correct_key_proof_batch(self.h, n_bits, batch, ptr(sigma), t, cap, off, ptr(out_status), fl),
                                 batch, out_status)
+
+    # ---- CompositeDLogProof / DLogStatement documents: {"x":X,"y":X} and {"N":X,"g":X,"ni":X}, X in the one form `bare_form` names
+    def json_dlog_statement(self, docs, n_bits: int, bare_form: int, out_N, out_g, out_ni, out_status):
+        """numpy outputs: tokenised on the host; torch cuda tensors: scanned on the device (the documents stay host text)"""
+        buf, off, ln = self._json_docs(docs)
+        self.check(self.lib.zkp_json_dlog_statement_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), n_bits, len(docs), bare_form, ptr(out_N), ptr(out_g),
+                                                          ptr(out_ni), ptr(out_status), self._flags(out_N, out_g, out_ni, out_status)))
+
+    def json_dlog_proof(self, docs, n_bits: int, y_bits: int, bare_form: int, out_x, out_y, out_status):
+        buf, off, ln = self._json_docs(docs)
+        self.check(self.lib.zkp_json_dlog_proof_batch(self.h, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), n_bits, y_bits, len(docs), bare_form, ptr(out_x), ptr(out_y),
+                                                      ptr(out_status), self._flags(out_x, out_y, out_status)))
+
+    def json_write_dlog_statement(self, n_bits: int, batch: int, N, g, ni, bare_form: int = BIGINT_DEC, out_status=None):
+        fl = self._flags(N, g, ni, out_status)
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_dlog_statement_batch(self.h, n_bits, batch, ptr(N), ptr(g), ptr(ni), bare_form, t, cap, off,
+                                                                                                 ptr(out_status), fl), batch, out_status)
+
+    def json_write_dlog_proof(self, n_bits: int, y_bits: int, batch: int, x, y, bare_form: int = BIGINT_DEC, out_status=None):
+        fl = self._flags(x, y, out_status)
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_dlog_proof_batch(self.h, n_bits, y_bits, batch, ptr(x), ptr(y), bare_form, t, cap, off,
+                                                                                             ptr(out_status), fl), batch, out_status)
+
+    def dlog_verify_json(self, statements, proofs, n_bits: int, y_bits: int, bare_form: int = BIGINT_DEC, device: bool = False, out_status=None, out_verdict=None):
+        """zkp_dlog_verify_json_batch: statement b and proof b (two lists of documents) -> (status, verdict) bytes, one pair per pair.
+        device: the two outputs are torch cuda tensors (made here when not given)."""
+        assert len(statements) == len(proofs)
+        B = len(statements)
+        buf, off, ln = self._json_docs(list(statements) + list(proofs))
+        if out_status is None or out_verdict is None:
+            if device:
+                import torch
+                out_status = torch.zeros(B, dtype=torch.uint8, device="cuda"); out_verdict = torch.zeros(B, dtype=torch.uint8, device="cuda")
+            else:
+                out_status = np.zeros(B, np.uint8); out_verdict = np.zeros(B, np.uint8)
+        s_off, s_len, p_off, p_len = (np.ascontiguousarray(a) for a in (off[:B], ln[:B], off[B:], ln[B:]))
+        self.check(self.lib.zkp_dlog_verify_json_batch(self.h, C.cast(buf, C.c_void_p), ptr(s_off), ptr(s_len), ptr(p_off), ptr(p_len), B, n_bits, y_bits, bare_form,
+                                                       ptr(out_status), ptr(out_verdict), ZKP_F_DEVICE_PTRS if device else 0))
+        return out_status, out_verdict

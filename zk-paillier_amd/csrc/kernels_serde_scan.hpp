@@ -10,13 +10,15 @@
 //   EncryptedPairs     {"c1":["D",..EF],"c2":["D",..EF]}
 //   Proof              [ROW,..EF]
 //   NiCorrectKeyProof  {"sigma_vec":["D",..11]}            one array instead of two
+//   CompositeDLogProof {"x":X,"y":X}                       heads only: the head phase, then `}` and the document's end
+//   DLogStatement      {"N":X,"g":X,"ni":X}
 // A document that differs in ONE byte from this is marked `fall back` and nothing else: the host tokeniser (zkp_api_serde.inc) reads it and
 // decides its status.  So the scanner never has an opinion about a document it does not fully understand, and for one it understands the
 // only thing left open is whether every number fits its field — k_dec2bin's overflow status, the host reader's ZKP_DOC_HOST_PATH.
 //
 // Phases inside the wavefront (every loop is bounded by the document's length, no byte outside [doc_off, doc_off + doc_len) is read):
-//   head    (RangeProofNi only) the three un-annotated integers: literal, value, literal ... — 64 bytes per step, the closing quote /
-//           bracket found by ballot
+//   head    (RangeProofNi and the two DLog kinds) the un-annotated integers: literal, value, literal ... — 64 bytes per step, the closing
+//           quote / bracket found by ballot; every value is bounded by ITS field's width (ScanJob::head_words, head_dig)
 //   mark    one pass over the rest, 64 bytes per step: a digit behind a quote opens a number, `{"O` / `{"M` opens a row; ballots and
 //           popcounts number both (the slot of a number depends on the kinds of the rows before it) and count the non-digit bytes in
 //           front of every number.  Positions go to LDS.
@@ -34,7 +36,7 @@ namespace zkp {
 
 constexpr int SCAN_MAX_EF = 256;
 constexpr int SCAN_MAX_TOK = 6 * SCAN_MAX_EF;
-constexpr int SCAN_MAX_BYTES = 1024;            // bytes of the widest head integer (ciphertext under a 4096-bit key)
+constexpr int SCAN_MAX_BYTES = 1024;            // bytes of the widest head integer (ciphertext under a 4096-bit key; a DLog field has at most half)
 
 struct ScanJob {
   const char* text;            // the uploaded span: byte `a` of the caller's text is text[a - lo]
@@ -46,12 +48,13 @@ struct ScanJob {
   uint32_t doc_kind;           // W_DOC_*
   uint32_t ef, kw, key_form, bare_form;      // ef: entries per array and rows per document (NiCorrectKeyProof: the 11 of sigma_vec)
   uint32_t dig_n, dig_c;       // decimal digits of the widest kw- / 2kw-word value
-  uint32_t* keys;              // [B][kw] ek.n
-  uint32_t* range; uint32_t* ct;
+  uint32_t head_words[3], head_dig[3];       // limbs and most decimal digits of head integer i (w_heads(doc_kind) of them)
+  uint32_t* keys;              // [B][kw] ek.n                       head 0: also N of a DLogStatement, x of a CompositeDLogProof
+  uint32_t* range; uint32_t* ct;             // heads 1 and 2: also g, ni / y
   uint8_t* kind; uint8_t* j;   // [B][EF], zero on entry
-  zkp_dec_item* items[W_ARRS]; // W_ARR_N, _RANGE, _CT: [B] (decimal forms only); W_ARR_C1 .. _R2: [B * EF]; sigma_vec is W_ARR_W1, as for the writer
+  zkp_dec_item* items[W_ARRS]; // W_ARR_N, _RANGE, _CT: [B] (the heads, decimal forms only); W_ARR_C1 .. _R2: [B * EF]; sigma_vec is W_ARR_W1, as for the writer
   uint32_t* row_doc;           // [B * EF] item -> document, for k_mark_docs
-  uint32_t* head_doc;          // [B] (RangeProofNi only, like keys, range, ct)
+  uint32_t* head_doc;          // [B] (kinds with heads only, like keys, range, ct)
   uint8_t* fast;               // [B] 1 = scanned here, 0 = fall back
   uint8_t* status;             // [B] ZKP_DOC_OK | ZKP_DOC_INVALID (a fall-back document, until the host reader has spoken)
 };
@@ -176,7 +179,7 @@ struct ScanShape {
 __device__ __forceinline__ ScanShape sc_shape(const ScanJob& J, const ScanLds& L) {
   ScanShape S;
   const bool ck = J.doc_kind == W_DOC_CK;
-  S.arrs = ck ? 1u : J.doc_kind == W_DOC_PROOF ? 0u : 2u;
+  S.arrs = ck ? 1u : J.doc_kind == W_DOC_PROOF || w_heads_only(J.doc_kind) ? 0u : 2u;
   S.cnt = J.ef;
   S.arr_words = ck ? J.kw : 2 * J.kw; S.arr_dig = ck ? J.dig_n : J.dig_c;
   S.arr_item = ck ? W_ARR_W1 : W_ARR_C1;
@@ -217,21 +220,35 @@ __device__ __forceinline__ const char* sc_row_after(const ScanShape& S, const Sc
   return S.close;
 }
 
+// the literal in front of head integer i
+__device__ __forceinline__ const char* sc_head_lit(uint32_t doc_kind, uint32_t i, uint32_t& n) {
+  if (doc_kind == W_DOC_NI) {
+    if (i == 0) { n = 11; return "{\"ek\":{\"n\":"; }
+    if (i == 1) { n = 10; return "},\"range\":"; }
+    n = 14; return ",\"ciphertext\":";
+  }
+  if (doc_kind == W_DOC_DLOG_PROOF) { n = 5; return i == 0 ? "{\"x\":" : ",\"y\":"; }
+  if (i == 2) { n = 6; return ",\"ni\":"; }
+  n = 5; return i == 0 ? "{\"N\":" : ",\"g\":";
+}
+
 // -> wave-uniform: document [t, t + len) is canonical.  On true: L holds its numbers and rows, head_* its head (already converted unless decimal)
 __device__ inline bool sc_scan_doc(const ScanJob& J, const ScanShape& S, uint64_t b, const char* t, uint32_t len, uint64_t text_at, ScanLds& L, uint32_t& ntok, int lane) {
   const uint32_t ef = J.ef, kw = J.kw;
   uint32_t pos = 0;
-  if (J.doc_kind == W_DOC_NI) {
-    if (!sc_lit(t, len, pos, "{\"ek\":{\"n\":", 11, lane)) return false;
-    pos += 11;
-    if (!sc_head_value(t, len, pos, J.key_form, kw, J.dig_n, J.keys + b * kw, J.items[W_ARR_N] ? J.items[W_ARR_N] + b : nullptr, text_at, b * kw, L, lane)) return false;
-    if (!sc_lit(t, len, pos, "},\"range\":", 10, lane)) return false;
-    pos += 10;
-    if (!sc_head_value(t, len, pos, J.bare_form, kw, J.dig_n, J.range + b * kw, J.items[W_ARR_RANGE] ? J.items[W_ARR_RANGE] + b : nullptr, text_at, b * kw, L, lane)) return false;
-    if (!sc_lit(t, len, pos, ",\"ciphertext\":", 14, lane)) return false;
-    pos += 14;
-    if (!sc_head_value(t, len, pos, J.bare_form, 2 * kw, J.dig_c, J.ct + b * 2 * kw, J.items[W_ARR_CT] ? J.items[W_ARR_CT] + b : nullptr, text_at, b * 2 * kw, L, lane)) return false;
+  const uint32_t heads = w_heads(J.doc_kind);
+  for (uint32_t i = 0; i < heads; i++) {
+    uint32_t n;
+    const char* lit = sc_head_lit(J.doc_kind, i, n);
+    if (!sc_lit(t, len, pos, lit, n, lane)) return false;
+    pos += n;
+    const uint32_t words = J.head_words[i];
+    uint32_t* dst = i == 0 ? J.keys : i == 1 ? J.range : J.ct;
+    if (!sc_head_value(t, len, pos, i == 0 ? J.key_form : J.bare_form, words, J.head_dig[i], dst + b * words, J.items[i] ? J.items[i] + b : nullptr, text_at, b * words, L,
+                       lane))
+      return false;
   }
+  if (w_heads_only(J.doc_kind)) { ntok = 0; return sc_lit(t, len, pos, "}", 1, lane) && pos + 1 == len; }
   const uint32_t T = pos;
   if (!sc_lit(t, len, T, S.open, S.open_n, lane)) return false;
 
@@ -312,6 +329,7 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
   const uint32_t ef = J.ef, kw = J.kw;
   const uint64_t len64 = J.doc_len[b], off = J.doc_off[b];
   const bool ni = J.doc_kind == W_DOC_NI;
+  const uint32_t heads = w_heads(J.doc_kind);
   if (ni && lane == 0) {
     // `"}}],"error_factor":N}`
     const char* head = "\"}}],\"error_factor\":";
@@ -333,16 +351,12 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
   __syncthreads();
 
   // ---- emit
-  const zkp_dec_item none_n{J.zero_at, 0, 1, kw};
   if (lane == 0) {
     J.fast[b] = ok ? 1 : 0;
     J.status[b] = ok ? ZKP_DOC_OK : ZKP_DOC_INVALID;
-    if (ni) J.head_doc[b] = (uint32_t)b;
-    if (ni && !ok) {
-      if (J.items[W_ARR_N]) { zkp_dec_item it = none_n; it.dst_off = b * kw; J.items[W_ARR_N][b] = it; }
-      if (J.items[W_ARR_RANGE]) { zkp_dec_item it = none_n; it.dst_off = b * kw; J.items[W_ARR_RANGE][b] = it; }
-      if (J.items[W_ARR_CT]) { zkp_dec_item it = none_n; it.dst_off = b * 2 * kw; it.words = 2 * kw; J.items[W_ARR_CT][b] = it; }
-    }
+    if (heads) J.head_doc[b] = (uint32_t)b;
+    for (uint32_t i = 0; i < heads && !ok; i++)
+      if (J.items[i]) J.items[i][b] = zkp_dec_item{J.zero_at, b * J.head_words[i], 1, J.head_words[i]};
   }
   for (uint32_t k = lane; k < S.arrs * S.cnt; k += 64) {
     const uint32_t which = k / S.cnt, i = k - which * S.cnt;
@@ -401,6 +415,41 @@ template <class T> __global__ void __launch_bounds__(256) k_scan_merge(const T* 
 __global__ void __launch_bounds__(256) k_scan_mask_verdicts(const uint8_t* __restrict__ status, uint8_t* __restrict__ verdict, uint64_t B) {
   const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (b < B && status[b] != ZKP_DOC_OK) verdict[b] = ZKP_VERDICT_REJECT;
+}
+
+// ---- CompositeDLogProof::verify on documents: is pair b inside the domain of the limb kernels?
+// wave-uniform: v < n, both kw words, most significant word first: the highest word in which they differ decides (found by ballot)
+__device__ __forceinline__ bool sc_less(const uint32_t* __restrict__ v, const uint32_t* __restrict__ n, uint32_t kw, int lane) {
+  for (int c0 = (int)((kw - 1) & ~63u); c0 >= 0; c0 -= 64) {
+    const uint32_t w = (uint32_t)c0 + (uint32_t)lane;
+    const uint32_t a = w < kw ? v[w] : 0u, m = w < kw ? n[w] : 0u;
+    const unsigned long long differ = __ballot(a != m);
+    if (differ) return __shfl((int)(a < m), 63 - __clzll((long long)differ)) != 0;
+  }
+  return false;
+}
+// The status of pair b starts as the worse of its two documents' (INVALID beats HOST_PATH beats OK).  A pair still OK whose N is even or zero,
+// or with one of g, ni, x >= N, has a verdict in the reference (mod_pow reduces its base, an even N is legal there) that the Montgomery
+// kernels cannot give: ZKP_DOC_HOST_PATH.  The five fields of every pair that is not OK are zeroed: N = 0 is answered by k_dlog_hash with
+// MALFORMED before any arithmetic, and k_setup marks the modulus so that no ladder stores a result.  One wavefront per pair.
+__global__ void __launch_bounds__(256) k_dlog_domain_check(uint32_t* __restrict__ N, uint32_t* __restrict__ g, uint32_t* __restrict__ ni, uint32_t* __restrict__ x,
+                                                           uint32_t* __restrict__ y, uint32_t kw, uint32_t yw, uint64_t B, const uint8_t* __restrict__ proof_status,
+                                                           uint8_t* __restrict__ status) {
+  const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const uint8_t s1 = status[b], s2 = proof_status[b];
+  uint8_t st = (s1 == ZKP_DOC_INVALID || s2 == ZKP_DOC_INVALID) ? (uint8_t)ZKP_DOC_INVALID : (s1 != ZKP_DOC_OK || s2 != ZKP_DOC_OK) ? (uint8_t)ZKP_DOC_HOST_PATH : (uint8_t)ZKP_DOC_OK;
+  if (st == ZKP_DOC_OK) {
+    const uint32_t* n = N + b * kw;
+    const bool odd = (n[0] & 1u) != 0;
+    const bool lg = sc_less(g + b * kw, n, kw, lane), lni = sc_less(ni + b * kw, n, kw, lane), lx = sc_less(x + b * kw, n, kw, lane);
+    if (!(odd && lg && lni && lx)) st = ZKP_DOC_HOST_PATH;
+  }
+  if (lane == 0) status[b] = st;
+  if (st == ZKP_DOC_OK) return;
+  for (uint32_t w = lane; w < kw; w += 64) { N[b * kw + w] = 0; g[b * kw + w] = 0; ni[b * kw + w] = 0; x[b * kw + w] = 0; }
+  for (uint32_t w = lane; w < yw; w += 64) y[b * yw + w] = 0;
 }
 
 }  // namespace zkp

@@ -15,7 +15,11 @@
 namespace zkp {
 
 enum { W_ARR_N = 0, W_ARR_RANGE, W_ARR_CT, W_ARR_C1, W_ARR_C2, W_ARR_W1, W_ARR_R1, W_ARR_W2, W_ARR_R2, W_ARRS };   // NiCorrectKeyProof: sigma is W_ARR_W1
-enum { W_DOC_PAIRS = 0, W_DOC_PROOF = 1, W_DOC_NI = 2, W_DOC_CK = 3 };
+enum { W_DOC_PAIRS = 0, W_DOC_PROOF = 1, W_DOC_NI = 2, W_DOC_CK = 3, W_DOC_DLOG_PROOF = 5, W_DOC_DLOG_STATEMENT = 6 };      // == ZKP_JSON_DOC_* (4 is no kind)
+// CompositeDLogProof {"x":X,"y":X} and DLogStatement {"N":X,"g":X,"ni":X} are heads only: field i of the document is array W_ARR_N + i (one
+// number per document, the batch's bare_form), and there is nothing behind the heads.
+__host__ __device__ constexpr bool w_heads_only(uint32_t doc_kind) { return doc_kind == W_DOC_DLOG_PROOF || doc_kind == W_DOC_DLOG_STATEMENT; }
+__host__ __device__ constexpr uint32_t w_heads(uint32_t doc_kind) { return doc_kind == W_DOC_DLOG_PROOF ? 2u : doc_kind == W_DOC_NI || doc_kind == W_DOC_DLOG_STATEMENT ? 3u : 0u; }
 enum { W_FORM_DEC = ZKP_BIGINT_DEC, W_FORM_HEX = ZKP_BIGINT_HEX, W_FORM_BYTES = ZKP_BIGINT_BYTES, W_FORM_NONE = 3 };
 
 // one SoA array of numbers: number i is src[i * words .. + words); its converted form is
@@ -59,6 +63,14 @@ __device__ inline WSlot w_slot(const WJob& J, uint64_t b, uint32_t s, int want) 
     if (s == 0) W_PRE("{\"sigma_vec\":[\""); else W_PRE(",\"");
     W_POST("\"");
     if (s == ZKP_CORRECT_KEY_M2 - 1) W_POST("]}");
+  } else if (w_heads_only(J.doc_kind)) {
+    const bool pf = J.doc_kind == W_DOC_DLOG_PROOF;
+    o.arr = (int)s; o.form = J.bare_form; o.idx = b;
+    if (s == 0) { if (pf) W_PRE("{\"x\":"); else W_PRE("{\"N\":"); }
+    else if (s == 1) { if (pf) W_PRE(",\"y\":"); else W_PRE(",\"g\":"); }
+    else W_PRE(",\"ni\":");
+    if (o.form == W_FORM_BYTES) { W_PRE("["); W_POST("]"); } else { W_PRE("\""); W_POST("\""); }
+    if (s + 1 == J.slots) W_POST("}");
   } else if (ni && t < 3) {
     o.arr = (int)t; o.form = t == 0 ? J.key_form : J.bare_form;
     o.idx = t == 0 ? (J.per_proof_keys ? b : 0) : b;

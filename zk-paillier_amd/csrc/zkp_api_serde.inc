@@ -273,12 +273,15 @@ int32_t convert_lists(zkp_ctx* c, const TextSpan& ts, std::vector<ItemList>& lis
 // With ZKP_F_DEVICE_PTRS every reader goes through the device scanner (json_scan, further down): the text is uploaded once and tokenised
 // there, and only the documents it leaves come back to the reader's flags-0 path, as a sub-batch.
 namespace {
+// the text of a call that scans twice (zkp_dlog_verify_json_batch), uploaded by the caller: byte `a` of the caller's text is d[a - lo], and
+// 16 bytes '0' follow the span
+struct ScanText { char* d; uint64_t lo, span; };
 int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat);
+                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits = 0, const ScanText* pre = nullptr);
 int32_t json_scan_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                        const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* out_status) {
+                        const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* out_status, uint32_t y_bits = 0) {
   Stage s(c, ZKP_F_DEVICE_PTRS);
-  int32_t st = json_scan(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, sigma, out_status);
+  int32_t st = json_scan(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, sigma, out_status, y_bits);
   if (st && !s.st) s.st = st;
   const int32_t fin = s.finish();
   if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
@@ -600,34 +603,59 @@ template <class T> int32_t scan_merge(zkp_ctx* c, Stage& s, const std::vector<T>
 //   - RangeProofNi: the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader
 //     decides before it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH;
 //   - what was converted of a document that ends up unconverted is cleared where the host reader clears it: everywhere but in sigma.
-int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat) {
-  const bool ni = doc_kind == W_DOC_NI, ck = doc_kind == W_DOC_CK, has_pairs = ni || doc_kind == W_DOC_PAIRS, has_rows = ni || doc_kind == W_DOC_PROOF;
-  const uint64_t B = d.batch, EF = ck ? ZKP_CORRECT_KEY_M2 : d.error_factor, rows = B * EF;
-  const uint32_t kw = d.n_bits / 32;
-  const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
-  const bool per_key = d.n_stride != 0;
-  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
-  int32_t st = scan_event(c, 0);
-  if (st) return st;
-  uint64_t lo = ~0ull, hi = 0;
-  for (uint64_t b = 0; b < B; b++) if (doc_len[b]) { lo = std::min(lo, doc_off[b]); hi = std::max(hi, doc_off[b] + doc_len[b]); }
+int32_t json_dlog_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t bare_form, uint32_t kw, uint32_t yw,
+                       uint32_t* const* out, uint8_t* out_status);
+void scan_span(const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint64_t* lo, uint64_t* hi) {
+  for (uint64_t b = 0; b < B; b++) if (doc_len[b]) { *lo = std::min(*lo, doc_off[b]); *hi = std::max(*hi, doc_off[b] + doc_len[b]); }
+}
+int32_t scan_upload(zkp_ctx* c, Stage& s, const char* text, uint64_t lo, uint64_t hi, ScanText* o) {
   if (hi == 0) lo = 0;
-  const uint64_t span = hi - lo;
+  o->lo = lo; o->span = hi - lo;
+  o->d = (char*)s.take(o->span + 16);
+  if (s.st) return s.st;
+  if (o->span) HIPCHK(c, hipMemcpyAsync(o->d, text + lo, o->span, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(o->d + o->span, '0', 16, c->stream));
+  return ZKP_OK;
+}
+// The two DLog kinds (heads only): d.n, d.range, d.ciphertext are the destinations of N, g, ni / x, y (y: y_bits / 32 words), d.n_stride = kw, forms
+// is the bare form alone, and nothing is cleared afterwards: as with sigma, an over-wide field is zero and the others stay converted.
+// pre: the text is already on the device (the caller also keeps the diagnostics: events and counters of BOTH scans of its call).
+int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits, const ScanText* pre) {
+  const bool ni = doc_kind == W_DOC_NI, ck = doc_kind == W_DOC_CK, has_pairs = ni || doc_kind == W_DOC_PAIRS, has_rows = ni || doc_kind == W_DOC_PROOF;
+  const bool dl = w_heads_only(doc_kind), heads = ni || dl;
+  const uint64_t B = d.batch, EF = ck ? ZKP_CORRECT_KEY_M2 : dl ? 0 : d.error_factor, rows = B * EF;
+  const uint32_t kw = d.n_bits / 32, yw = y_bits / 32;
+  const uint32_t key_form = dl ? forms & 15u : (forms >> 4) & 15u, bare_form = forms & 15u;
+  const bool per_key = d.n_stride != 0;
+  int32_t st = ZKP_OK;
+  ScanText up{};
+  if (pre) up = *pre;
+  else {
+    c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
+    if ((st = scan_event(c, 0))) return st;
+    uint64_t lo = ~0ull, hi = 0;
+    scan_span(doc_off, doc_len, B, &lo, &hi);
+    if ((st = scan_upload(c, s, text, lo, hi, &up))) return st;
+  }
+  const uint64_t lo = up.lo, span = up.span;
   ScanJob J{};
-  char* dtext = (char*)s.take(span + 16);
+  char* dtext = up.d;
   J.doc_off = s.host_in(doc_off, B); J.doc_len = s.host_in(doc_len, B);
   J.text = dtext; J.lo = lo; J.B = B; J.zero_at = span;
   J.max_len = zkp_json_doc_bound(doc_kind, d.n_bits, d.error_factor, forms);
   J.doc_kind = doc_kind; J.ef = (uint32_t)EF; J.kw = kw; J.key_form = key_form; J.bare_form = bare_form;
   J.dig_n = zkp_decimal_pitch(kw) - 1; J.dig_c = zkp_decimal_pitch(2 * kw) - 1;      // (max_digits below)
+  const uint32_t head_words[3] = {kw, doc_kind == W_DOC_DLOG_PROOF ? yw : kw, ni ? 2 * kw : kw};
+  for (int i = 0; i < 3; i++) { J.head_words[i] = head_words[i]; J.head_dig[i] = zkp_decimal_pitch(head_words[i]) - 1; }
   uint32_t* const out_range = const_cast<uint32_t*>(d.range);
   uint32_t* const out_ct = const_cast<uint32_t*>(d.ciphertext);
-  if (ni) { J.keys = per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4); J.range = out_range; J.ct = out_ct; }
+  if (heads) { J.keys = per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4); J.range = out_range; J.ct = out_ct; }
   if (has_rows) { J.kind = d.resp_kind; J.j = d.resp_j; }
   struct Target { int arr; uint32_t* dst; uint32_t words; };      // arr < W_ARR_C1: one number per document, else EF
   std::vector<Target> targets;
-  if (ni) targets.insert(targets.end(), {{W_ARR_N, J.keys, kw}, {W_ARR_RANGE, out_range, kw}, {W_ARR_CT, out_ct, 2 * kw}});
+  if (heads) targets.insert(targets.end(), {{W_ARR_N, J.keys, head_words[0]}, {W_ARR_RANGE, out_range, head_words[1]}});
+  if (w_heads(doc_kind) == 3) targets.push_back({W_ARR_CT, out_ct, head_words[2]});
   if (has_pairs) targets.insert(targets.end(), {{W_ARR_C1, d.c1, 2 * kw}, {W_ARR_C2, d.c2, 2 * kw}});
   if (has_rows) targets.insert(targets.end(), {{W_ARR_W1, d.resp_w1, kw}, {W_ARR_R1, d.resp_r1, kw}, {W_ARR_W2, d.resp_w2, kw}, {W_ARR_R2, d.resp_r2, kw}});
   if (ck) targets.push_back({W_ARR_W1, sigma, kw});
@@ -637,21 +665,19 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     J.items[t.arr] = (zkp_dec_item*)s.take((head ? B : rows) * sizeof(zkp_dec_item));
   }
   J.row_doc = (uint32_t*)s.take(rows * 4);
-  if (ni) J.head_doc = (uint32_t*)s.take(B * 4);
+  if (heads) J.head_doc = (uint32_t*)s.take(B * 4);
   J.fast = (uint8_t*)s.take(B); J.status = dstat;
   uint8_t* item_status = (uint8_t*)s.take(std::max<uint64_t>(rows, B));
   if (s.st) return s.st;
-  if (span) HIPCHK(c, hipMemcpyAsync(dtext, text + lo, span, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(dtext + span, '0', 16, c->stream));
   for (const Target& t : targets) HIPCHK(c, hipMemsetAsync(t.dst, 0, (t.arr < W_ARR_C1 ? B : rows) * t.words * 4, c->stream));
   if (has_rows) {
     HIPCHK(c, hipMemsetAsync(d.resp_kind, 0, rows, c->stream));
     HIPCHK(c, hipMemsetAsync(d.resp_j, 0, rows, c->stream));
   }
-  if ((st = scan_event(c, 1))) return st;
+  if (!pre && (st = scan_event(c, 1))) return st;
   hipLaunchKernelGGL(k_json_scan, dim3((unsigned)B), dim3(64), 0, c->stream, J);
   HIPCHK(c, hipGetLastError());
-  if ((st = scan_event(c, 2))) return st;
+  if (!pre && (st = scan_event(c, 2))) return st;
   auto convert = [&](const Target& t) -> int32_t {
     if (!J.items[t.arr]) return ZKP_OK;                      // a head integer in hex / byte-array form: the scanner wrote its limbs
     const bool head = t.arr < W_ARR_C1;
@@ -670,7 +696,7 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
   }
   for (const Target& t : targets) if (t.arr >= W_ARR_C1 && !st) st = convert(t);
   if (st) return st;
-  if (!ck) {
+  if (!ck && !dl) {
     for (const Target& t : targets) {
       if (t.arr == W_ARR_N && !per_key) continue;
       clear_failed_docs(c, dstat, t.dst, (t.arr < W_ARR_C1 ? 1 : EF) * t.words, B);
@@ -684,7 +710,7 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<uint32_t> idx;
   for (uint64_t b = 0; b < B; b++) if (!fast[b]) idx.push_back((uint32_t)b);
-  c->scan_fast = B - idx.size(); c->scan_fallback = idx.size();
+  c->scan_fast += B - idx.size(); c->scan_fallback += idx.size();
   if (!idx.empty()) {
     const uint64_t nf = idx.size();
     std::vector<uint64_t> foff(nf), flen(nf);
@@ -697,7 +723,9 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     hp.batch = nf; hp.n = h[W_ARR_N].data(); hp.range = h[W_ARR_RANGE].data(); hp.ciphertext = h[W_ARR_CT].data(); hp.c1 = h[W_ARR_C1].data(); hp.c2 = h[W_ARR_C2].data();
     hp.resp_kind = hkind.data(); hp.resp_j = hj.data();
     hp.resp_w1 = h[W_ARR_W1].data(); hp.resp_r1 = h[W_ARR_R1].data(); hp.resp_w2 = h[W_ARR_W2].data(); hp.resp_r2 = h[W_ARR_R2].data();
-    st = ni              ? zkp_json_range_proof_ni_batch(c, text, foff.data(), flen.data(), forms, &hp, hst.data(), 0)
+    uint32_t* const hdl[3] = {h[W_ARR_N].data(), h[W_ARR_RANGE].data(), h[W_ARR_CT].data()};
+    st = dl              ? json_dlog_host(text, foff.data(), flen.data(), nf, doc_kind, bare_form, kw, yw, hdl, hst.data())
+         : ni            ? zkp_json_range_proof_ni_batch(c, text, foff.data(), flen.data(), forms, &hp, hst.data(), 0)
          : ck            ? zkp_json_correct_key_proof_batch(c, text, foff.data(), flen.data(), d.n_bits, nf, h[W_ARR_W1].data(), hst.data(), 0)
          : has_pairs     ? zkp_json_encrypted_pairs_batch(c, text, foff.data(), flen.data(), &hp, hst.data(), 0)
                          : zkp_json_range_proof_batch(c, text, foff.data(), flen.data(), &hp, hst.data(), 0);
@@ -716,7 +744,7 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     if (st) return st;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the host vectors go out of scope
   }
-  return scan_event(c, 3);
+  return pre ? ZKP_OK : scan_event(c, 3);
 }
 bool json_ni_common_args_ok(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t n_bits, uint32_t ef, uint32_t forms) {
   return text && doc_off && doc_len && B <= (1ull << 24) && (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && ef != 0 && ef <= 256 && !(forms >> 8) &&
@@ -918,10 +946,14 @@ constexpr uint64_t cstrlen(const char* s) { return *s ? 1 + cstrlen(s + 1) : 0; 
 
 extern "C" uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms) {
   const uint32_t key_form = (bigint_forms >> 4) & 15u, bare_form = bigint_forms & 15u;
-  if ((n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || doc_kind > ZKP_JSON_DOC_CORRECT_KEY_PROOF || (bigint_forms >> 8) ||
-      key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (doc_kind != ZKP_JSON_DOC_CORRECT_KEY_PROOF && error_factor == 0))
+  const bool dl = doc_kind == ZKP_JSON_DOC_DLOG_PROOF || doc_kind == ZKP_JSON_DOC_DLOG_STATEMENT;
+  if ((n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || (doc_kind > ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl) || (bigint_forms >> 8) ||
+      key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (doc_kind != ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl && error_factor == 0))
     return 0;
   const uint32_t kw = n_bits / 32;
+  // (the proof's y at its widest, y_bits == n_bits)
+  if (doc_kind == ZKP_JSON_DOC_DLOG_PROOF) return cstrlen("{\"x\":,\"y\":}") + 4 + 2 * max_form_len(kw, bare_form);
+  if (doc_kind == ZKP_JSON_DOC_DLOG_STATEMENT) return cstrlen("{\"N\":,\"g\":,\"ni\":}") + 6 + 3 * max_form_len(kw, bare_form);
   const uint64_t EF = error_factor, dn = max_digits(kw), dc = max_digits(2 * kw);
   if (doc_kind == ZKP_JSON_DOC_CORRECT_KEY_PROOF) return cstrlen("{\"sigma_vec\":[") + ZKP_CORRECT_KEY_M2 * (dn + 3) - 1 + cstrlen("]}");
   // {"c1":["..",".."],"c2":[..]}
@@ -936,16 +968,21 @@ extern "C" uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint3
          max_form_len(kw, key_form) + max_form_len(kw, bare_form) + max_form_len(2 * kw, bare_form) + pairs + proof + uint_digits(EF);
 }
 
+// the fields of a heads-only document (the two DLog kinds): field i is one number of words[i] limbs per document
+struct WHeads { const uint32_t* a[3]; uint32_t words[3]; };
 static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, const zkp_range_ni_proofs* p, uint32_t n_bits, uint64_t B, uint64_t EF,
-                               const uint32_t* sigma, uint32_t forms, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags) {
+                               const uint32_t* sigma, uint32_t forms, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags,
+                               const WHeads* hd = nullptr) {
   if (!c) return ZKP_EINVAL;
   const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
   const bool ck = doc_kind == W_DOC_CK, ni = doc_kind == W_DOC_NI, has_pairs = doc_kind == W_DOC_PAIRS || ni, has_proof = doc_kind == W_DOC_PROOF || ni;
+  const bool dl = w_heads_only(doc_kind);
   const uint32_t kw = n_bits / 32;
   bool bad = !out_doc_off || (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24) ||
-             (forms >> 8) || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (!ck && !p) || (!ck && (EF == 0 || EF > 256));
+             (forms >> 8) || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (!ck && !dl && !p) || (!ck && !dl && (EF == 0 || EF > 256));
   if (!bad && B) {
-    if (ck) bad = !sigma;
+    if (dl) { bad = !hd; for (uint32_t i = 0; !bad && i < w_heads(doc_kind); i++) bad = !hd->a[i]; }
+    else if (ck) bad = !sigma;
     else bad = (has_pairs && (!p->c1 || !p->c2)) || (has_proof && (!p->resp_kind || !p->resp_j || !p->resp_w1 || !p->resp_r1 || !p->resp_w2 || !p->resp_r2)) ||
                (ni && (!p->n || !p->range || !p->ciphertext || (p->n_stride != 0 && p->n_stride != kw)));
   }
@@ -957,7 +994,7 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
   WJob J{};
   J.B = B; J.ef = (uint32_t)EF; J.doc_kind = doc_kind; J.key_form = key_form; J.bare_form = bare_form;
   J.per_proof_keys = ni && p->n_stride != 0;
-  J.slots = ck ? ZKP_CORRECT_KEY_M2 : (uint32_t)((ni ? 3 : 0) + (has_pairs ? 2 * EF : 0) + (has_proof ? 4 * EF : 0));
+  J.slots = ck ? ZKP_CORRECT_KEY_M2 : dl ? w_heads(doc_kind) : (uint32_t)((ni ? 3 : 0) + (has_pairs ? 2 * EF : 0) + (has_proof ? 4 * EF : 0));
   struct Todo { int arr; uint64_t count; uint32_t form; };
   std::vector<Todo> todo;
   auto add = [&](int arr, const uint32_t* src, uint64_t count, uint32_t words, uint32_t form) {
@@ -970,6 +1007,7 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
   };
   const uint64_t rows = B * EF;
   if (ck) add(W_ARR_W1, sigma, B * ZKP_CORRECT_KEY_M2, kw, ZKP_BIGINT_DEC);
+  if (dl) for (uint32_t i = 0; i < w_heads(doc_kind); i++) add(W_ARR_N + (int)i, hd->a[i], B, hd->words[i], bare_form);
   if (ni) {
     add(W_ARR_N, p->n, p->n_stride ? B : 1, kw, key_form);
     add(W_ARR_RANGE, p->range, B, kw, bare_form);
@@ -1073,4 +1111,147 @@ extern "C" int32_t zkp_json_write_range_proof_ni_batch(zkp_ctx* c, const zkp_ran
 extern "C" int32_t zkp_json_write_correct_key_proof_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* sigma, char* out_text, uint64_t text_cap,
                                                           uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags) try {
   return json_write_impl(c, "zkp_json_write_correct_key_proof_batch", W_DOC_CK, nullptr, n_bits, batch, 0, sigma, 0, out_text, text_cap, out_doc_off, out_status, flags);
+} ZKP_CATCH(c)
+
+// ---- CompositeDLogProof and DLogStatement (wi_dlog_proof.rs:32-43): {"x":X,"y":X} and {"N":X,"g":X,"ni":X}, every X an un-annotated curv BigInt
+// in the one form the caller names.
+namespace {
+// The flags-0 reader: the tolerant tokeniser, every number converted on the host (parse_bigint_value, as for the head of a RangeProofNi
+// document).  out[i]: [B][words of field i].  An invalid document leaves zero rows; an over-wide or negative field is zero, the others converted.
+int32_t json_dlog_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t bare_form, uint32_t kw, uint32_t yw,
+                       uint32_t* const* out, uint8_t* out_status) {
+  const bool pf = doc_kind == W_DOC_DLOG_PROOF;
+  const unsigned nf = w_heads(doc_kind);
+  static const char* const pf_names[2] = {"x", "y"};
+  static const char* const st_names[3] = {"N", "g", "ni"};
+  const char* const* names = pf ? pf_names : st_names;
+  const uint32_t words[3] = {kw, pf ? yw : kw, kw};
+  for (unsigned f = 0; f < nf; f++) memset(out[f], 0, (size_t)B * words[f] * 4);
+  for_docs(B, [&](uint64_t b, unsigned) {
+    JCur j{text, doc_off[b], doc_off[b] + doc_len[b]};
+    unsigned seen = 0;
+    bool host = false;
+    j.object([&](const std::string& nm) {
+      int f = -1;
+      for (unsigned q = 0; q < nf; q++) if (nm == names[q]) f = (int)q;
+      if (f < 0) return false;
+      if (seen & (1u << f)) { j.ok = false; return true; }                      // duplicate field
+      seen |= 1u << f;
+      host |= parse_bigint_value(j, bare_form, out[f] + b * words[f], words[f]) == ZKP_DOC_HOST_PATH;
+      return true;
+    });
+    if (seen != (1u << nf) - 1) j.ok = false;                                   // missing field
+    const uint8_t st = !j.done() ? ZKP_DOC_INVALID : host ? ZKP_DOC_HOST_PATH : ZKP_DOC_OK;
+    out_status[b] = st;
+    if (st == ZKP_DOC_INVALID) for (unsigned f = 0; f < nf; f++) memset(out[f] + b * words[f], 0, (size_t)words[f] * 4);
+  });
+  return ZKP_OK;
+}
+
+int32_t json_dlog_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
+                        uint32_t y_bits, uint64_t B, uint32_t bare_form, uint32_t* const* out, uint8_t* out_status, uint32_t flags) {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  bool bad = (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !text || !doc_off || !doc_len || !out_status || bare_form > ZKP_BIGINT_BYTES || !dlog_args_ok(n_bits, y_bits, B);
+  for (unsigned f = 0; f < w_heads(doc_kind); f++) bad = bad || !out[f];
+  if (bad) { c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL; }
+  const uint32_t kw = n_bits / 32;
+  if (!(flags & ZKP_F_DEVICE_PTRS)) return json_dlog_host(text, doc_off, doc_len, B, doc_kind, bare_form, kw, y_bits / 32, out, out_status);
+  HIPCHK(c, hipSetDevice(c->device));
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
+  d.n = out[0]; d.range = out[1]; d.ciphertext = out[2];
+  return json_scan_entry(c, name, doc_kind, text, doc_off, doc_len, bare_form, d, nullptr, out_status, y_bits);
+}
+}  // namespace
+
+extern "C" int32_t zkp_json_dlog_statement_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits, uint64_t B,
+                                                 uint32_t bare_form, uint32_t* out_N, uint32_t* out_g, uint32_t* out_ni, uint8_t* out_status, uint32_t flags) try {
+  uint32_t* const out[3] = {out_N, out_g, out_ni};
+  return json_dlog_entry(c, "zkp_json_dlog_statement_batch", W_DOC_DLOG_STATEMENT, text, doc_off, doc_len, n_bits, n_bits, B, bare_form, out, out_status, flags);
+} ZKP_CATCH(c)
+extern "C" int32_t zkp_json_dlog_proof_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits, uint32_t y_bits,
+                                             uint64_t B, uint32_t bare_form, uint32_t* out_x, uint32_t* out_y, uint8_t* out_status, uint32_t flags) try {
+  uint32_t* const out[3] = {out_x, out_y, nullptr};
+  return json_dlog_entry(c, "zkp_json_dlog_proof_batch", W_DOC_DLOG_PROOF, text, doc_off, doc_len, n_bits, y_bits, B, bare_form, out, out_status, flags);
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_json_write_dlog_statement_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* N, const uint32_t* g, const uint32_t* ni,
+                                                       uint32_t bare_form, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status,
+                                                       uint32_t flags) try {
+  const uint32_t kw = n_bits / 32;
+  const WHeads hd{{N, g, ni}, {kw, kw, kw}};
+  if (c && bare_form > ZKP_BIGINT_BYTES) { c->err = "zkp_json_write_dlog_statement_batch: invalid argument"; return ZKP_EINVAL; }
+  return json_write_impl(c, "zkp_json_write_dlog_statement_batch", W_DOC_DLOG_STATEMENT, nullptr, n_bits, batch, 0, nullptr, bare_form, out_text, text_cap, out_doc_off,
+                         out_status, flags, &hd);
+} ZKP_CATCH(c)
+extern "C" int32_t zkp_json_write_dlog_proof_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* x, const uint32_t* y,
+                                                   uint32_t bare_form, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status,
+                                                   uint32_t flags) try {
+  const WHeads hd{{x, y, nullptr}, {n_bits / 32, y_bits / 32, 0}};
+  if (c && (bare_form > ZKP_BIGINT_BYTES || !dlog_args_ok(n_bits, y_bits, batch))) { c->err = "zkp_json_write_dlog_proof_batch: invalid argument"; return ZKP_EINVAL; }
+  return json_write_impl(c, "zkp_json_write_dlog_proof_batch", W_DOC_DLOG_PROOF, nullptr, n_bits, batch, 0, nullptr, bare_form, out_text, text_cap, out_doc_off, out_status,
+                         flags, &hd);
+} ZKP_CATCH(c)
+
+// CompositeDLogProof::verify (wi_dlog_proof.rs:67-91) on documents: statement b and proof b are two spans of one text, uploaded once.  Both are read
+// by the device route into arrays the call owns; k_dlog_domain_check folds the two statuses and keeps every pair the limb kernels are not defined for
+// (N even or zero, g / ni / x >= N) away from them; then zkp_dlog_verify_batch on the whole batch, the verdicts of unread pairs masked afterwards.
+// An unread pair is five zero rows.  N = 0: k_setup marks the modulus (status 2, before any loop that depends on its value; every later loop runs
+// over the fixed limb count or the exponent's bits), so k_modexp / k_modmul compute on zeros and store nothing, k_dlog_hash answers MALFORMED from
+// the `N > 2^128` test without entering the GCD, and k_dlog_compare leaves that verdict alone: no placeholder modulus is needed.
+// The events of zkp_diag_last_json_scan_ms are: upload | statements read | proofs read | domain check and verify.
+extern "C" int32_t zkp_dlog_verify_json_batch(zkp_ctx* c, const char* text, const uint64_t* st_off, const uint64_t* st_len, const uint64_t* pf_off,
+                                              const uint64_t* pf_len, uint64_t B, uint32_t n_bits, uint32_t y_bits, uint32_t bare_form, uint8_t* out_status,
+                                              uint8_t* out_verdict, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  if ((flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !text || !st_off || !st_len || !pf_off || !pf_len || !out_status || !out_verdict || bare_form > ZKP_BIGINT_BYTES ||
+      !dlog_args_ok(n_bits, y_bits, B)) {
+    c->err = "zkp_dlog_verify_json_batch: invalid argument"; return ZKP_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t kw = n_bits / 32, yw = y_bits / 32;
+  const char* name = "zkp_dlog_verify_json_batch";
+  Stage s(c, flags);
+  uint8_t* dstat = s.out(out_status, B);
+  uint8_t* dv = s.out(out_verdict, B);
+  uint32_t* arr[4];
+  for (auto& a : arr) a = (uint32_t*)s.take(B * kw * 4);
+  uint32_t* dy = (uint32_t*)s.take(B * yw * 4);
+  uint8_t* dstat2 = (uint8_t*)s.take(B);
+  int32_t st = s.st;
+  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
+  if (!st) st = scan_event(c, 0);
+  ScanText up{};
+  if (!st) {
+    uint64_t lo = ~0ull, hi = 0;
+    scan_span(st_off, st_len, B, &lo, &hi);
+    scan_span(pf_off, pf_len, B, &lo, &hi);
+    st = scan_upload(c, s, text, lo, hi, &up);
+  }
+  if (!st) st = scan_event(c, 1);
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
+  d.n = arr[0]; d.range = arr[1]; d.ciphertext = arr[2];
+  if (!st) st = json_scan(c, s, name, W_DOC_DLOG_STATEMENT, text, st_off, st_len, bare_form, d, nullptr, dstat, y_bits, &up);
+  if (!st) st = scan_event(c, 2);
+  d.n = arr[3]; d.range = dy; d.ciphertext = nullptr;
+  if (!st) st = json_scan(c, s, name, W_DOC_DLOG_PROOF, text, pf_off, pf_len, bare_form, d, nullptr, dstat2, y_bits, &up);
+  if (!st) st = scan_event(c, 3);
+  if (!st) {
+    hipLaunchKernelGGL(k_dlog_domain_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, arr[0], arr[1], arr[2], arr[3], dy, (uint32_t)kw, (uint32_t)yw, B,
+                       (const uint8_t*)dstat2, dstat);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_dlog_domain_check launch"; }
+  }
+  if (!st) st = zkp_dlog_verify_batch(c, n_bits, y_bits, B, arr[0], arr[1], arr[2], arr[3], dy, dv, ZKP_F_DEVICE_PTRS);
+  if (!st) {
+    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
+  }
+  if (!st) st = scan_event(c, 4);
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
 } ZKP_CATCH(c)

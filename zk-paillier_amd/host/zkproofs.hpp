@@ -1014,6 +1014,12 @@ class CompositeDLogProof {
     if (v == ZKP_VERDICT_MALFORMED) throw Panic("assertion failed in CompositeDLogProof::verify (N > 2^128, gcd(g,N) = gcd(ni,N) = 1)");   // :69,72,73
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
+  // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_dlog_verify_json_batch
+  // scans, converts, range-checks and verifies on the GPU.  A pair it hands back (ZKP_DOC_HOST_PATH: a field the fixed layout cannot
+  // carry, an even N, g / ni / x >= N) is parsed here and goes through verify() above, so the caller gets the reference's answer for it;
+  // a document that is no value of its type is the panic `from_str(..).unwrap()` is in the reference, and so are verify's assertions.
+  // bare_form: ZKP_BIGINT_DEC / _HEX / _BYTES, the text form of every integer of the batch.
+  static std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t bare_form = ZKP_BIGINT_DEC);
 };
 
 // ------------------------------------------------------------------ ZeroProof (src/zkproofs/zero_enc_proof.rs:26-95)
@@ -1540,6 +1546,52 @@ inline NiCorrectKeyProof correct_key_from_str_host(const std::string& doc) {
   return out;
 }
 
+// CompositeDLogProof {"x":X,"y":X} and DLogStatement {"N":X,"g":X,"ni":X} (wi_dlog_proof.rs:32-43): un-annotated BigInts of any size and sign, on
+// the host (whole batches: zkp_json_write_dlog_*_batch / zkp_json_dlog_*_batch of the C ABI, CompositeDLogProof::verify_json_batch)
+inline std::string bigint_text(const BigInt& v, BigintText form) {
+  if (form == BigintText::Dec) return "\"" + v.to_str_radix10() + "\"";
+  const std::vector<uint8_t> b = v.to_bytes();
+  std::string s = form == BigintText::Hex ? (v.is_negative() ? "\"-" : "\"") : "[";
+  for (size_t i = 0; i < b.size(); i++) {
+    if (form == BigintText::Hex) { static const char* d = "0123456789abcdef"; s.push_back(d[b[i] >> 4]); s.push_back(d[b[i] & 15]); }
+    else s += (i ? "," : "") + std::to_string((unsigned)b[i]);
+  }
+  return s + (form == BigintText::Hex ? "\"" : "]");
+}
+inline std::string to_string(const CompositeDLogProof& p, BigintText form = BigintText::Dec) { return "{\"x\":" + bigint_text(p.x, form) + ",\"y\":" + bigint_text(p.y, form) + "}"; }
+inline std::string to_string(const DLogStatement& s, BigintText form = BigintText::Dec) {
+  return "{\"N\":" + bigint_text(s.N, form) + ",\"g\":" + bigint_text(s.g, form) + ",\"ni\":" + bigint_text(s.ni, form) + "}";
+}
+namespace detail_json {
+inline void bigint_fields(const std::string& doc, BigintText form, const std::vector<std::pair<const char*, BigInt*>>& fields) {
+  Cur j{doc};
+  unsigned seen = 0;
+  j.object([&](const std::string& nm) {
+    for (size_t f = 0; f < fields.size(); f++) {
+      if (nm != fields[f].first) continue;
+      if (seen & (1u << f)) j.fail("duplicate field");
+      seen |= 1u << f;
+      *fields[f].second = j.bigint(form);
+      return true;
+    }
+    return false;
+  });
+  if (seen != (1u << fields.size()) - 1) j.fail("missing field");
+  j.ws();
+  if (j.p != doc.size()) j.fail("trailing characters");
+}
+}  // namespace detail_json
+inline CompositeDLogProof dlog_proof_from_str(const std::string& doc, BigintText form = BigintText::Dec) {
+  CompositeDLogProof p;
+  detail_json::bigint_fields(doc, form, {{"x", &p.x}, {"y", &p.y}});
+  return p;
+}
+inline DLogStatement dlog_statement_from_str(const std::string& doc, BigintText form = BigintText::Dec) {
+  DLogStatement s;
+  detail_json::bigint_fields(doc, form, {{"N", &s.N}, {"g", &s.g}, {"ni", &s.ni}});
+  return s;
+}
+
 inline RangeProofNi range_proof_ni_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
   detail_json::Cur j{doc};
   RangeProofNi out;
@@ -1647,6 +1699,42 @@ inline std::vector<Result> RangeProofNi::verify_json_batch(const std::vector<std
     if (!err.empty()) { out[b] = Result::panicked("called `Result::unwrap()` on an `Err` value: " + err); continue; }
     if (ek && !(q.ek == *ek)) { out[b] = Result::panicked("assertion failed: `(left == right)` ek"); continue; }
     out[b] = verify_batch(q.ek, {&q})[0];       // ZKP_DOC_HOST_PATH (or a key of another width): the host path for integers of any size and sign
+  }
+  return out;
+}
+
+inline std::vector<Result> CompositeDLogProof::verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t bare_form) {
+  const size_t B = statements.size();
+  if (proofs.size() != B) throw std::invalid_argument("CompositeDLogProof::verify_json_batch: one proof per statement");
+  if (bare_form > ZKP_BIGINT_BYTES) throw std::invalid_argument("CompositeDLogProof::verify_json_batch: unknown text form");
+  const auto form = (serde_json::BigintText)bare_form;
+  std::vector<Result> out(B, Result(false));
+  std::vector<uint8_t> status(B, ZKP_DOC_HOST_PATH), verdict(B, ZKP_VERDICT_REJECT);
+  // one modulus width per call: that of the first statement that parses and has a modulus the engine carries
+  uint32_t nb = 0;
+  for (size_t b = 0; b < B && nb == 0; b++) {
+    try {
+      const DLogStatement s = serde_json::dlog_statement_from_str(statements[b], form);
+      if (!s.N.is_negative() && s.N.is_odd() && s.N.bit_length() >= 2 && s.N.bit_length() <= 4096) nb = width_for(s.N);
+    } catch (const std::exception&) {}
+  }
+  if (nb) {
+    std::string text;
+    std::vector<uint64_t> so(B), sl(B), po(B), pl(B);
+    for (size_t b = 0; b < B; b++) { so[b] = text.size(); sl[b] = statements[b].size(); text += statements[b]; }
+    for (size_t b = 0; b < B; b++) { po[b] = text.size(); pl[b] = proofs[b].size(); text += proofs[b]; }
+    Engine& e = Engine::instance();
+    if (zkp_dlog_verify_json_batch(e.ctx(), text.data(), so.data(), sl.data(), po.data(), pl.data(), B, nb, Y_BITS, bare_form, status.data(), verdict.data(), 0) != ZKP_OK)
+      throw std::runtime_error(std::string("zkp_dlog_verify_json_batch: ") + zkp_last_error_string(e.ctx()));
+  }
+  for (size_t b = 0; b < B; b++) {
+    if (status[b] == ZKP_DOC_OK && verdict[b] != ZKP_VERDICT_MALFORMED) { out[b] = Result(verdict[b] == ZKP_VERDICT_ACCEPT); continue; }
+    try {
+      DLogStatement s; CompositeDLogProof p;
+      try { s = serde_json::dlog_statement_from_str(statements[b], form); p = serde_json::dlog_proof_from_str(proofs[b], form); }
+      catch (const std::exception& err) { out[b] = Result::panicked(std::string("called `Result::unwrap()` on an `Err` value: ") + err.what()); continue; }
+      out[b] = p.verify(s);         // (a MALFORMED verdict as well: verify() names the assertion that failed)
+    } catch (const Panic& panic) { out[b] = Result::panicked(panic.what()); }
   }
   return out;
 }
