@@ -5,9 +5,10 @@ import numpy as np
 import pytest
 
 import helpers as H
+import small_proof_cases as SC
 from helpers import pm, L, zkp
 
-MALFORMED = zkp.VERDICT_MALFORMED
+ACCEPT, REJECT, MALFORMED = zkp.VERDICT_ACCEPT, zkp.VERDICT_REJECT, zkp.VERDICT_MALFORMED
 
 
 # ------------------------------------------------------------------ mod_inv
@@ -268,3 +269,290 @@ def test_gpu_correct_message_matches_oracle(ctx, oracle, n_bits, shared, K):
     assert v[0] == 0 and v[1] == MALFORMED and v[2] == MALFORMED      # a_vec feeds the challenge: the sum check fails first
     ct2 = cto.copy(); ct2[0, 0] ^= 1
     assert both(ct2, evo, zvo, avo)[0] == 0
+
+
+# ================================================================== wide batches and operand edges (tests/small_proof_cases.py)
+# ---- MulProof
+def _mul_prove_verify(oracle, cs):
+    bt, a = cs["bt"], cs["a"]
+    *o, st = oracle.mul_proof_prove(*bt.key(), *[a[k] for k in SC.MUL_IN])
+    return tuple(o), st, oracle.mul_proof_verify(*bt.key(), a["e_a"], a["e_b"], a["e_c"], *o)
+
+
+def _mul_wide(oracle):
+    def build():
+        oracle.set_threads(min(8, oracle.max_threads()))
+        cs = SC.mul_wide(oracle)
+        bt, a = cs["bt"], cs["a"]
+        o, st, vh = _mul_prove_verify(oracle, cs)
+        t = list(o)
+        for k in range(3):                              # f, z1, z2 tampered in different proofs
+            t[k] = SC.flip(o[k], cs["tamper"][2 * k:2 * k + 2], salt=k)
+        t[4] = o[4].copy()
+        for b in cs["bad_edb"]:
+            SC.set_int(t[4], b, bt.pq[b][0] * (98765 + b))
+        return cs, o, st, vh, tuple(t), oracle.mul_proof_verify(*bt.key(), a["e_a"], a["e_b"], a["e_c"], *t)
+    return SC.cached("mul-wide", build)
+
+
+def _check_mul_wide(cs, st, vh, vt):
+    B = cs["bt"].B
+    dishonest = cs["false"] + cs["no_inverse"] + cs["bad_edb"]
+    assert B > 256 and {0, 63, 64, 255, 256, B - 1} <= set(dishonest)
+    for group in (cs["false"], cs["no_inverse"], cs["bad_edb"], cs["tamper"]):
+        assert any(b < 256 for b in group) and any(b >= 256 for b in group)
+    assert [int(v) for v in st] == [MALFORMED if b in cs["no_inverse"] else 0 for b in range(B)]
+    assert [int(v) for v in vh] == [REJECT if b in cs["false"] + cs["no_inverse"] else ACCEPT for b in range(B)]      # (a panicked prove leaves zeros)
+    want = [MALFORMED if b in cs["bad_edb"] else REJECT if b in cs["false"] + cs["no_inverse"] + cs["tamper"] else ACCEPT for b in range(B)]
+    assert [int(v) for v in vt] == want
+
+
+def test_wide_mul_case_is_what_it_claims(oracle):
+    """CPU: status and verdicts of the 300-proof batch are ACCEPT, REJECT and MALFORMED exactly where the builder put each kind"""
+    cs, o, st, vh, t, vt = _mul_wide(oracle)
+    _check_mul_wide(cs, st, vh, vt)
+
+
+@pytest.mark.gpu
+def test_gpu_mul_proof_wide_batch(ctx, oracle):
+    """300 MulProofs under four 1024-bit keys: a second, partial 256-thread block in k_hash_list, k_modadd, k_mul_finish and
+    k_mul_verdict; a GROUPS_PER_BLOCK tail in the limb kernels; false statements, r_c = p and e_db = k p on both sides of the boundary"""
+    cs, o, st, vh, t, vt = _mul_wide(oracle)
+    bt, a = cs["bt"], cs["a"]
+    assert bt.B > 256
+    _check_mul_wide(cs, st, vh, vt)
+    g = tuple(SC.sentinel(v.shape) for v in o)
+    sg = SC.sentinel(bt.B, np.uint8)
+    ctx.mul_proof_prove(bt.n_bits, bt.B, bt.n_arr, bt.stride, *[a[k] for k in SC.MUL_IN], *g, sg)
+    SC.assert_same(st, sg, "status")
+    for name, x, y in zip(SC.MUL_OUT, o, g):
+        SC.assert_same(x, y, name)
+    for proof, want in ((g, vh), (t, vt)):
+        vg = SC.sentinel(bt.B, np.uint8)
+        ctx.mul_proof_verify(bt.n_bits, bt.B, bt.n_arr, bt.stride, a["e_a"], a["e_b"], a["e_c"], *proof, vg)
+        SC.assert_same(want, vg, "verdict")
+
+
+def _mul_edges(oracle, n_bits):
+    def build():
+        oracle.set_threads(min(8, oracle.max_threads()))
+        cs = SC.mul_edges(oracle, n_bits)
+        o, st, vh = _mul_prove_verify(oracle, cs)
+        ed, over, wide_ed = SC.mul_edits(cs, o)
+        ve = oracle.mul_proof_verify(*cs["bt"].key(), *[ed[k] for k in ("e_a", "e_b", "e_c") + SC.MUL_OUT])
+        return cs, o, st, vh, ed, over, wide_ed, ve
+    return SC.cached("mul-edges-%d" % n_bits, build)
+
+
+def _check_mul_edges(cs, o, st, vh, ed, over, wide_ed, ve):
+    """every honest proof of edge inputs is accepted; f reaches 0 and n - 1; at a = d = n - 1 the sum e a mod n + d mod n carries out of
+    the kw words (k_modadd's carry branch); z1 + n^2 and z2 + n^2 are ACCEPTED; an e_d >= n^2 is in the batch; the edited batch holds all
+    three verdicts"""
+    bt, a = cs["bt"], cs["a"]
+    b = cs["carry"]
+    e = pm.compute_digest([bt.ns[b]] + [SC.get_int(a[k], b) for k in ("e_a", "e_b", "e_c")] + [SC.get_int(o[3], b), SC.get_int(o[4], b)])
+    assert e * SC.get_int(a["a"], b) % bt.ns[b] + SC.get_int(a["d"], b) % bt.ns[b] >= 1 << bt.n_bits
+    assert [int(v) for v in st] == [0] * bt.B and [int(v) for v in vh] == [ACCEPT] * bt.B
+    assert SC.get_int(o[0], cs["f_zero"]) == 0 and SC.get_int(o[0], cs["f_top"]) == bt.ns[cs["f_top"]] - 1
+    assert len(over) == 2 and all(ve[b] == ACCEPT for b in over)
+    assert SC.get_int(ed["e_d"], wide_ed) >= bt.ns[wide_ed] ** 2
+    assert {ACCEPT, REJECT, MALFORMED} <= set(int(v) for v in ve)
+
+
+def test_mul_edge_cases_oracle_matches_python_model(oracle):
+    """CPU: the operand edges of tests/small_proof_cases.py (n = 1024) through the C oracle and through oracle/py_model.py.  The reference
+    decides: d b and r_d r_b enter Enc unreduced (multiplication_proof.rs:69-76), f = e a + d mod n (:87-88); the verifier hashes e_d and
+    e_db as they are (:107-114), uses them modulo n^2 (:131-134) and panics where e_db e_c^e has no inverse (:135)."""
+    cs, o, st, vh, ed, over, wide_ed, ve = _mul_edges(oracle, 1024)
+    bt, a = cs["bt"], cs["a"]
+    _check_mul_edges(cs, o, st, vh, ed, over, wide_ed, ve)
+    for b, n in enumerate(bt.ns):
+        assert tuple(SC.get_int(v, b) for v in o) == pm.mul_proof_prove(n, *[SC.get_int(a[k], b) for k in SC.MUL_IN]), b
+        try:
+            got = ACCEPT if pm.mul_proof_verify(n, *[SC.get_int(ed[k], b) for k in ("e_a", "e_b", "e_c") + SC.MUL_OUT]) else REJECT
+        except pm.Panic:
+            got = MALFORMED
+        assert got == ve[b], b
+    b = cs["short"]["mul"]
+    assert pm.compute_digest([bt.ns[b]] + [SC.get_int(a[k], b) for k in ("e_a", "e_b", "e_c")] + [SC.get_int(o[3], b), SC.get_int(o[4], b)]) >> 248 == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_bits", [1024, 2048])
+def test_gpu_mul_proof_operand_edges(ctx, oracle, n_bits):
+    """a, b, d in {0, 1, n - 1, 2^n_bits - 1}, r_* in {1, n - 1, 2^n_bits - 1}, f = 0 and n - 1, a sum that carries out of kw words (k_modadd);
+    z1, z2 >= n^2 (accepted), all ones, 0; e_d, e_db >= n^2, 0, 1, ragged, e_db = k p; a short challenge"""
+    cs, o, st, vh, ed, over, wide_ed, ve = _mul_edges(oracle, n_bits)
+    bt, a = cs["bt"], cs["a"]
+    _check_mul_edges(cs, o, st, vh, ed, over, wide_ed, ve)
+    g = tuple(SC.sentinel(v.shape) for v in o)
+    sg = SC.sentinel(bt.B, np.uint8)
+    ctx.mul_proof_prove(bt.n_bits, bt.B, bt.n_arr, bt.stride, *[a[k] for k in SC.MUL_IN], *g, sg)
+    SC.assert_same(st, sg, "status")
+    for name, x, y in zip(SC.MUL_OUT, o, g):
+        SC.assert_same(x, y, name)
+    if n_bits == 1024:
+        b = cs["short"]["mul"]
+        assert pm.compute_digest([bt.ns[b]] + [SC.get_int(a[k], b) for k in ("e_a", "e_b", "e_c")] + [SC.get_int(g[3], b), SC.get_int(g[4], b)]) >> 248 == 0
+    for stmt, proof, want in ((a, g, vh), (ed, [ed[k] for k in SC.MUL_OUT], ve)):
+        vg = SC.sentinel(bt.B, np.uint8)
+        ctx.mul_proof_verify(bt.n_bits, bt.B, bt.n_arr, bt.stride, stmt["e_a"], stmt["e_b"], stmt["e_c"], *proof, vg)
+        SC.assert_same(want, vg, "verdict")
+
+
+# ---- CorrectMessageProof
+def _cm_prove(oracle, cs):
+    bt, a = cs["bt"], cs["a"]
+    return oracle.correct_message_prove(bt.n_bits, cs["K"], bt.n_arr, bt.stride, a["valid"], a["msg"], a["r"], a["e_sim"], a["z_sim"], a["w"])
+
+
+def _cm_verify(oracle, cs, ct, ev, zv, av):
+    bt = cs["bt"]
+    return oracle.correct_message_verify(bt.n_bits, cs["K"], bt.n_arr, bt.stride, cs["a"]["valid"], ct, ev, zv, av)
+
+
+def _gpu_cm_prove(ctx, cs, like):
+    bt, a, K = cs["bt"], cs["a"], cs["K"]
+    g = tuple(SC.sentinel(v.shape) for v in like[:4])
+    sg = SC.sentinel(bt.B, np.uint8)
+    ctx.correct_message_prove(bt.n_bits, bt.B, K, bt.n_arr, bt.stride, a["valid"], a["msg"], a["r"], a["e_sim"], a["z_sim"], a["w"], *g, sg)
+    SC.assert_same(like[4], sg, "status")
+    for name, x, y in zip(("ciphertext", "e_vec", "z_vec", "a_vec"), like[:4], g):
+        SC.assert_same(x, y, name)
+    return g
+
+
+def _gpu_cm_verify(ctx, cs, proof, want):
+    bt = cs["bt"]
+    vg = SC.sentinel(bt.B, np.uint8)
+    ctx.correct_message_verify(bt.n_bits, bt.B, cs["K"], bt.n_arr, bt.stride, cs["a"]["valid"], *proof, vg)
+    SC.assert_same(want, vg, "verdict")
+
+
+def _cm_wide(oracle, K):
+    def build():
+        oracle.set_threads(min(8, oracle.max_threads()))
+        cs = SC.cm_wide(K)
+        o = _cm_prove(oracle, cs)
+        t = (o[0], SC.flip(o[1], cs["tamper_e"]), SC.flip(o[2], cs["tamper_z"]), o[3])
+        return cs, o, _cm_verify(oracle, cs, *o[:4]), t, _cm_verify(oracle, cs, *t)
+    return SC.cached("cm-wide-%d" % K, build)
+
+
+def _check_cm_wide(cs, o, vh, vt):
+    B, K = cs["bt"].B, cs["K"]
+    assert B * K > 256 and (K > 1 or B > 256)
+    panicked = cs["not_listed"] + cs["no_inverse"]
+    row_owners = {0, 63, 64, B - 1} | ({255, 256} if K == 1 else {255 // K, 256 // K})
+    assert row_owners <= set(panicked + cs["tamper_z"])
+    assert [int(v) for v in o[4]] == [MALFORMED if b in panicked else 0 for b in range(B)]
+    # a panicked prove leaves zeros: 0 != H(0 ...) mod 2^256, the assert_eq! of correct_message.rs:138
+    assert [int(v) for v in vh] == [MALFORMED if b in panicked else ACCEPT for b in range(B)]
+    assert [int(v) for v in vt] == [MALFORMED if b in panicked + cs["tamper_e"] else REJECT if b in cs["tamper_z"] else ACCEPT for b in range(B)]
+    assert {ACCEPT, REJECT, MALFORMED} <= set(int(v) for v in vt)
+
+
+@pytest.mark.parametrize("K", [3, 1])
+def test_wide_correct_message_case_is_what_it_claims(oracle, K):
+    """CPU: status and verdicts of the wide batches are ACCEPT, REJECT and MALFORMED exactly where the builder put each kind"""
+    cs, o, vh, t, vt = _cm_wide(oracle, K)
+    _check_cm_wide(cs, o, vh, vt)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [3, 1])
+def test_gpu_correct_message_wide_batch(ctx, oracle, K):
+    """K = 3: 130 proofs, 390 rows — the per-row kernels (k_repeat_rows, k_add_one, k_cm_gather, k_cm_scatter, k_square_words; rows
+    b * K + i and b * (K - 1) + j) cross the 256-thread block boundary.  K = 1: 300 proofs — the per-proof kernels (k_cm_plan, k_cm_ei,
+    k_cm_verdict) cross it, and no row is simulated."""
+    cs, o, vh, t, vt = _cm_wide(oracle, K)
+    assert cs["bt"].B * K > 256
+    _check_cm_wide(cs, o, vh, vt)
+    g = _gpu_cm_prove(ctx, cs, o)
+    _gpu_cm_verify(ctx, cs, g, vh)
+    _gpu_cm_verify(ctx, cs, t, vt)
+
+
+def _cm_edges(oracle, n_bits):
+    def build():
+        oracle.set_threads(min(8, oracle.max_threads()))
+        cs = SC.cm_edges(n_bits)
+        o = _cm_prove(oracle, cs)
+        vh = _cm_verify(oracle, cs, *o[:4])
+        ed, over, rebalanced = SC.cm_edits(cs, *o[:4])
+        proof = (ed["ct"], ed["e_vec"], ed["z_vec"], ed["a_vec"])
+        k1 = SC.cm_k1()
+        o1 = _cm_prove(oracle, k1)
+        return cs, o, vh, proof, over, rebalanced, _cm_verify(oracle, cs, *proof), k1, o1, _cm_verify(oracle, k1, *o1[:4])
+    return SC.cached("cm-edges-%d" % n_bits, build)
+
+
+def _check_cm_edges(cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1):
+    """honest proofs of edge inputs are accepted; a message listed twice proves without a panic, and the reference's own verifier then
+    panics on it (both rows take e_i, :95-106, the unused simulated e stays in the sum, :88: the sums differ, :138); an unlisted message
+    panics (:74), at K = 1 too; z + n and ciphertext + n^2 are ACCEPTED; a rebalanced e_vec passes the sum check and is REJECTED"""
+    B = cs["bt"].B
+    dup, nl = cs["duplicate"], cs["not_listed"]
+    assert [int(v) for v in o[4]] == [MALFORMED if b == nl else 0 for b in range(B)]
+    assert [int(v) for v in vh] == [MALFORMED if b in (dup, nl) else ACCEPT for b in range(B)]
+    assert len(over) == 2 and all(ve[b] == ACCEPT for b in over)
+    assert len(rebalanced) == 3 and all(ve[b] == REJECT for b in rebalanced)
+    assert {ACCEPT, REJECT, MALFORMED} <= set(int(v) for v in ve)
+    assert [int(v) for v in o1[4]] == [0, MALFORMED, 0, MALFORMED] and [int(v) for v in v1] == [ACCEPT, MALFORMED, ACCEPT, MALFORMED]
+
+
+def _model_cm_verify(n, valid, ct, ev, zv, av, b):
+    try:
+        ok = pm.correct_message_verify(n, valid, SC.get_int(ct, b), [SC.get_int(ev[b], k) for k in range(len(valid))],
+                                       [SC.get_int(zv[b], k) for k in range(len(valid))], [SC.get_int(av[b], k) for k in range(len(valid))])
+        return ACCEPT if ok else REJECT
+    except pm.Panic:
+        return MALFORMED
+
+
+def test_correct_message_edge_cases_oracle_matches_python_model(oracle):
+    """CPU: the operand edges of tests/small_proof_cases.py (n = 1024; K = 3, and K = 1) through the C oracle and through
+    oracle/py_model.py.  The reference decides: every valid message equal to the encrypted one takes the real branch (correct_message.rs:71,
+    98, 111), so a duplicate uses one simulated row less while e_i is still the challenge minus ALL K - 1 simulated e (:88-91); a message
+    in no row indexes zi_vec past its end (:74); e_i = chal - sum modulo 2^256 (:91); the verifier compares the sums modulo 2^256 (:135-138)
+    and raises each z to n modulo n^2 as it is (:151)."""
+    cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1 = _cm_edges(oracle, 1024)
+    _check_cm_edges(cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1)
+    for c, out, vv in ((cs, o, None), (k1, o1, v1)):
+        bt = c["bt"]
+        for b, (n, q) in enumerate(zip(bt.ns, c["rows"])):
+            try:
+                want = pm.correct_message_prove(n, q["valid"], q["msg"], q["r"], q["e_sim"], q["z_sim"], q["w"])
+            except pm.Panic:
+                assert out[4][b] == MALFORMED and not out[1][b].any() and not out[2][b].any() and not out[3][b].any(), b
+                assert SC.get_int(out[0], b) == pm.enc(n, q["msg"], q["r"])
+                continue
+            K = len(q["valid"])
+            got = (SC.get_int(out[0], b), [SC.get_int(out[1][b], k) for k in range(K)], [SC.get_int(out[2][b], k) for k in range(K)], [SC.get_int(out[3][b], k) for k in range(K)])
+            assert out[4][b] == 0 and got == want, b
+            if vv is not None:
+                assert _model_cm_verify(n, q["valid"], *out[:4], b) == vv[b], b
+    for b, (n, q) in enumerate(zip(cs["bt"].ns, cs["rows"])):
+        assert _model_cm_verify(n, q["valid"], *proof, b) == ve[b], b
+        assert _model_cm_verify(n, q["valid"], *o[:4], b) == vh[b], b
+    b = cs["short"]["cm"]
+    chal = pm.compute_digest([SC.get_int(o[3][b], k) for k in range(3)])
+    assert chal >> 248 == 0 and SC.get_int(o[1][b], cs["rows"][b]["valid"].index(cs["rows"][b]["msg"])) == chal
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_bits", [1024, 2048])
+def test_gpu_correct_message_operand_edges(ctx, oracle, n_bits):
+    """e_sim rows of 0 and 2^256 - 1 (k_cm_ei's borrow), r, w, z_sim at 0, 1, n - 1, 2^n_bits - 1, message 0, a message listed twice, an
+    unlisted one (K = 3 and K = 1); e_vec rebalanced through 2^256 (k_cm_verdict's carry: REJECT, not MALFORMED), z + n and
+    ciphertext + n^2 (accepted), a_vec >= n^2, 0, 1 and of ragged byte length (k_hash_list); a short challenge as the real row's exponent"""
+    cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1 = _cm_edges(oracle, n_bits)
+    _check_cm_edges(cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1)
+    g = _gpu_cm_prove(ctx, cs, o)
+    if n_bits == 1024:
+        b = cs["short"]["cm"]
+        assert pm.compute_digest([SC.get_int(g[3][b], k) for k in range(3)]) >> 248 == 0
+    _gpu_cm_verify(ctx, cs, g, vh)
+    _gpu_cm_verify(ctx, cs, proof, ve)
+    g1 = _gpu_cm_prove(ctx, k1, o1)
+    _gpu_cm_verify(ctx, k1, g1, v1)

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import small_proof_cases as SC
 from helpers import pm, L, zkp
 
 
@@ -58,3 +59,105 @@ def test_gpu_verlin_matches_oracle(ctx, oracle, n_bits, shared):
     vg = np.full(B, 9, np.uint8)
     ctx.verlin_proof_verify(n_bits, B, n_arr, stride, a["c"], a["cp"], a["phi_x"], g[0], zt, g[2], g[3], g[4], vg)
     assert np.array_equal(vo, vg) and list(vo) == [0, 1, 1, 0]
+
+
+# ================================================================== wide batch and operand edges (tests/small_proof_cases.py)
+def _io(cs):
+    a = cs["a"]
+    return tuple(a[k] for k in SC.VERLIN_WIT), tuple(a[k] for k in SC.VERLIN_NON)
+
+
+def _verlin_wide(oracle):
+    def build():
+        oracle.set_threads(min(8, oracle.max_threads()))
+        cs = SC.verlin_wide(oracle)
+        bt, a = cs["bt"], cs["a"]
+        wit, non = _io(cs)
+        o = oracle.verlin_proof_prove(*bt.key(), a["c"], a["cp"], a["phi_x"], wit, non)
+        third = -(-len(cs["tamper"]) // 3)
+        t = list(o)                                     # z, z', z'' tampered in different proofs
+        for k in range(3):
+            t[1 + k] = SC.flip(o[1 + k], cs["tamper"][k * third:(k + 1) * third], salt=k)
+        vh = oracle.verlin_proof_verify(*bt.key(), a["c"], a["cp"], a["phi_x"], *o)
+        vt = oracle.verlin_proof_verify(*bt.key(), a["c"], a["cp"], a["phi_x"], *t)
+        return cs, o, vh, tuple(t), vt
+    return SC.cached("verlin-wide", build)
+
+
+def test_wide_verlin_case_is_what_it_claims(oracle):
+    """CPU: the oracle rejects the 300-proof batch exactly at the false statements, and at the tampered responses as well"""
+    cs, o, vh, t, vt = _verlin_wide(oracle)
+    SC.check_wide_verdicts(cs, vh, vt)
+
+
+@pytest.mark.gpu
+def test_gpu_verlin_wide_batch(ctx, oracle):
+    """300 VerlinProofs under one 1024-bit key: a second, partial 256-thread block in k_verlin_hash / k_words_compare; a GROUPS_PER_BLOCK
+    tail in modexp_core (kw- and (kw + 16)-word per-item exponents), k_enc with m_words / r_words set, and k_modmul"""
+    cs, o, vh, t, vt = _verlin_wide(oracle)
+    bt, a = cs["bt"], cs["a"]
+    assert bt.B > 256
+    SC.check_wide_verdicts(cs, vh, vt)
+    wit, non = _io(cs)
+    g = tuple(SC.sentinel(v.shape) for v in o)
+    ctx.verlin_proof_prove(bt.n_bits, bt.B, bt.n_arr, bt.stride, a["c"], a["cp"], a["phi_x"], wit, non, g)
+    for name, vo, vg in zip(SC.VERLIN_OUT, o, g):
+        SC.assert_same(vo, vg, name)
+    for proof, want in ((g, vh), (t, vt)):
+        vg = SC.sentinel(bt.B, np.uint8)
+        ctx.verlin_proof_verify(bt.n_bits, bt.B, bt.n_arr, bt.stride, a["c"], a["cp"], a["phi_x"], *proof, vg)
+        SC.assert_same(want, vg, "verdict")
+
+
+def _verlin_edges(oracle, n_bits):
+    def build():
+        oracle.set_threads(min(8, oracle.max_threads()))
+        cs = SC.verlin_edges(oracle, n_bits)
+        bt, a = cs["bt"], cs["a"]
+        wit, non = _io(cs)
+        o = oracle.verlin_proof_prove(*bt.key(), a["c"], a["cp"], a["phi_x"], wit, non)
+        vh = oracle.verlin_proof_verify(*bt.key(), a["c"], a["cp"], a["phi_x"], *o)
+        ed, over = SC.verlin_edits(cs, o)
+        ve = oracle.verlin_proof_verify(*bt.key(), ed["c"], ed["cp"], ed["phi_x"], *[ed[k] for k in SC.VERLIN_OUT])
+        return cs, o, vh, ed, over, ve
+    return SC.cached("verlin-edges-%d" % n_bits, build)
+
+
+def test_verlin_edge_cases_oracle_matches_python_model(oracle):
+    """CPU: the operand edges of tests/small_proof_cases.py (n = 1024) through the C oracle and through oracle/py_model.py.  The reference
+    decides: z = x e + a over the integers for any x and a, r_z = r_x^e r_a mod n^2 (verlin_proof.rs:85-89); gen_phi raises c and c' to the
+    responses as they are and encrypts z'' under r_z (:138-165), so z'' + k n and r_z + n^2 give the same phi_z while z + k n does not;
+    the challenge hashes n, c, c', phi_x, phi_a as they are (:102-108)."""
+    cs, o, vh, ed, over, ve = _verlin_edges(oracle, 1024)
+    bt, a = cs["bt"], cs["a"]
+    SC.check_edge_verdicts(cs, vh, over, ve)
+    for b, n in enumerate(bt.ns):
+        st = [SC.get_int(a[k], b) for k in ("c", "cp", "phi_x")]
+        assert tuple(SC.get_int(v, b) for v in o) == pm.verlin_prove(n, *st, *[SC.get_int(a[k], b) for k in SC.VERLIN_WIT + SC.VERLIN_NON]), b
+        got = pm.verlin_verify(n, *[SC.get_int(ed[k], b) for k in ("c", "cp", "phi_x") + SC.VERLIN_OUT])
+        assert got == (ve[b] == SC.ACCEPT), b
+    b = cs["short"]["verlin"]
+    assert pm.compute_digest([bt.ns[b]] + [SC.get_int(a[k], b) for k in ("c", "cp", "phi_x")] + [SC.get_int(o[0], b)]) >> 248 == 0
+    assert all(SC.get_int(o[k], 9) >> (1024 + 248) != 0 for k in (1, 2, 3))      # witness and nonces at 2^n_bits - 1: the maximal honest responses
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_bits", [1024, 2048])
+def test_gpu_verlin_operand_edges(ctx, oracle, n_bits):
+    """witness and nonces in {0, 1, n - 1, 2^n_bits - 1}; z, z', z'' with all kw + 16 limbs set and k n higher (z'': accepted);
+    r_z >= n^2, all ones, 0; c, c', phi_x, phi_a >= n^2, 0, 1, of ragged byte length; a short challenge"""
+    cs, o, vh, ed, over, ve = _verlin_edges(oracle, n_bits)
+    bt, a = cs["bt"], cs["a"]
+    SC.check_edge_verdicts(cs, vh, over, ve)
+    wit, non = _io(cs)
+    g = tuple(SC.sentinel(v.shape) for v in o)
+    ctx.verlin_proof_prove(bt.n_bits, bt.B, bt.n_arr, bt.stride, a["c"], a["cp"], a["phi_x"], wit, non, g)
+    for name, vo, vg in zip(SC.VERLIN_OUT, o, g):
+        SC.assert_same(vo, vg, name)
+    if n_bits == 1024:
+        b = cs["short"]["verlin"]
+        assert pm.compute_digest([bt.ns[b]] + [SC.get_int(a[k], b) for k in ("c", "cp", "phi_x")] + [SC.get_int(g[0], b)]) >> 248 == 0
+    for st, proof, want in ((a, g, vh), (ed, [ed[k] for k in SC.VERLIN_OUT], ve)):
+        vg = SC.sentinel(bt.B, np.uint8)
+        ctx.verlin_proof_verify(bt.n_bits, bt.B, bt.n_arr, bt.stride, st["c"], st["cp"], st["phi_x"], *proof, vg)
+        SC.assert_same(want, vg, "verdict")
