@@ -42,6 +42,14 @@ pub const ZKP_JSON_DOC_RANGE_PROOF_NI: u32 = 2;
 pub const ZKP_JSON_DOC_CORRECT_KEY_PROOF: u32 = 3;
 pub const ZKP_JSON_DOC_DLOG_PROOF: u32 = 5;
 pub const ZKP_JSON_DOC_DLOG_STATEMENT: u32 = 6;
+pub const ZKP_JSON_DOC_ZERO_STATEMENT: u32 = 8;
+pub const ZKP_JSON_DOC_ZERO_PROOF: u32 = 9;
+pub const ZKP_JSON_DOC_CIPHERTEXT_STATEMENT: u32 = 10;
+pub const ZKP_JSON_DOC_CIPHERTEXT_PROOF: u32 = 11;
+pub const ZKP_JSON_DOC_VERLIN_STATEMENT: u32 = 12;
+pub const ZKP_JSON_DOC_VERLIN_PROOF: u32 = 13;
+pub const ZKP_JSON_DOC_MUL_STATEMENT: u32 = 14;
+pub const ZKP_JSON_DOC_MUL_PROOF: u32 = 15;
 pub const ZKP_GATHER_HOST: u32 = 0;
 pub const ZKP_GATHER_RCCL: u32 = 1;
 pub const ZKP_GATHER_COPY: u32 = 2;
@@ -97,6 +105,15 @@ pub struct zkp_dec_item {
     pub dst_off: u64,
     pub len: u32,
     pub words: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct zkp_sigma_fields {
+    pub f0: *mut u32,
+    pub f1: *mut u32,
+    pub f2: *mut u32,
+    pub f3: *mut u32,
+    pub f4: *mut u32,
 }
 
 // ---------------------------------------------------------------- entry points
@@ -161,6 +178,9 @@ extern "C" {
     pub fn zkp_json_write_dlog_statement_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, N: *const u32, g: *const u32, ni: *const u32, bare_form: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_write_dlog_proof_batch(ctx: *mut zkp_ctx, n_bits: u32, y_bits: u32, batch: u64, x: *const u32, y: *const u32, bare_form: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_dlog_verify_json_batch(ctx: *mut zkp_ctx, text: *const c_char, st_off: *const u64, st_len: *const u64, pf_off: *const u64, pf_len: *const u64, batch: u64, n_bits: u32, y_bits: u32, bare_form: u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_sigma_batch(ctx: *mut zkp_ctx, doc_kind: u32, text: *const c_char, doc_off: *const u64, doc_len: *const u64, n_bits: u32, batch: u64, bigint_forms: u32, out: *const zkp_sigma_fields, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_json_write_sigma_batch(ctx: *mut zkp_ctx, doc_kind: u32, n_bits: u32, batch: u64, in_: *const zkp_sigma_fields, bigint_forms: u32, out_text: *mut c_char, text_cap: u64, out_doc_off: *mut u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_sigma_verify_json_batch(ctx: *mut zkp_ctx, proof_kind: u32, text: *const c_char, st_off: *const u64, st_len: *const u64, pf_off: *const u64, pf_len: *const u64, batch: u64, n_bits: u32, bigint_forms: u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_multi_create(device_ids: *const i32, n_devices: u32, out: *mut *mut zkp_multi) -> i32;
     pub fn zkp_multi_destroy(m: *mut zkp_multi) -> i32;
     pub fn zkp_multi_size(m: *mut zkp_multi) -> u32;

@@ -474,6 +474,16 @@ int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* ctx, const char* text, con
 /* (4 is no kind, and stays none: zkp_json_doc_bound answers 0 for it, as callers written against the first four kinds expect) */
 #define ZKP_JSON_DOC_DLOG_PROOF 5u         /* bigint_forms = the bare form alone; error_factor is ignored; the bound is taken at y_bits == n_bits, */
 #define ZKP_JSON_DOC_DLOG_STATEMENT 6u     /* the widest y the entry points accept, so it holds for every y_bits */
+/* (7 is no kind either.)  The sigma-proof kinds, see "ZeroProof, CiphertextProof, VerlinProof and MulProof as documents" below: bigint_forms
+ * names both forms, error_factor is ignored. */
+#define ZKP_JSON_DOC_ZERO_STATEMENT 8u
+#define ZKP_JSON_DOC_ZERO_PROOF 9u
+#define ZKP_JSON_DOC_CIPHERTEXT_STATEMENT 10u
+#define ZKP_JSON_DOC_CIPHERTEXT_PROOF 11u
+#define ZKP_JSON_DOC_VERLIN_STATEMENT 12u
+#define ZKP_JSON_DOC_VERLIN_PROOF 13u
+#define ZKP_JSON_DOC_MUL_STATEMENT 14u
+#define ZKP_JSON_DOC_MUL_PROOF 15u
 uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms);
 int32_t zkp_json_write_encrypted_pairs_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
                                              uint8_t* out_status, uint32_t flags);
@@ -532,6 +542,53 @@ int32_t zkp_json_write_dlog_proof_batch(zkp_ctx* ctx, uint32_t n_bits, uint32_t 
 int32_t zkp_dlog_verify_json_batch(zkp_ctx* ctx, const char* text, const uint64_t* st_off, const uint64_t* st_len, const uint64_t* pf_off,
                                    const uint64_t* pf_len, uint64_t batch, uint32_t n_bits, uint32_t y_bits, uint32_t bare_form,
                                    uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */, uint32_t flags);
+
+/* ------------------------------------------------------------------ ZeroProof, CiphertextProof, VerlinProof and MulProof as documents
+ * zero_enc_proof.rs:26-41, correct_ciphertext.rs:22-39, verlin_proof.rs:34-57, multiplication_proof.rs:32-57: the serde defaults of the
+ * derives, fields in declaration order.  K = ek.n in the key form, every X an un-annotated curv BigInt in the bare form, both named by
+ * bigint_forms = ZKP_BIGINT_FORMS(key_form, bare_form) exactly as for a RangeProofNi document.  kw = n_bits/32, zw = kw + ZKP_Z1_EXTRA_LIMBS.
+ *   ZKP_JSON_DOC_ZERO_STATEMENT        {"ek":{"n":K},"c":X}                                      n [kw], c [2kw]
+ *   ZKP_JSON_DOC_ZERO_PROOF            {"z":X,"a":X}                                             z, a [2kw]
+ *   ZKP_JSON_DOC_CIPHERTEXT_STATEMENT  {"ek":{"n":K},"c":X}                                      n [kw], c [2kw]
+ *   ZKP_JSON_DOC_CIPHERTEXT_PROOF      {"z1":X,"z2":X,"c_prime":X}                               z1 [zw], z2, c_prime [2kw]
+ *   ZKP_JSON_DOC_VERLIN_STATEMENT      {"ek":{"n":K},"c":X,"c_prime":X,"phi_x":X}                n [kw], c, c_prime, phi_x [2kw]
+ *   ZKP_JSON_DOC_VERLIN_PROOF          {"phi_a":X,"z":X,"z_prime":X,"z_double_prime":X,"r_z":X}  phi_a, r_z [2kw]; z, z_prime, z_double_prime [zw]
+ *   ZKP_JSON_DOC_MUL_STATEMENT         {"ek":{"n":K},"e_a":X,"e_b":X,"e_c":X}                    n [kw], e_a, e_b, e_c [2kw]
+ *   ZKP_JSON_DOC_MUL_PROOF             {"f":X,"z1":X,"z2":X,"e_d":X,"e_db":X}                    f [kw]; z1, z2, e_d, e_db [2kw]
+ * zkp_sigma_fields: the arrays of one kind, [B][words] each, in the order of the table (a statement's f0 is the key); unused entries NULL.
+ * Its layout is that of `uint32_t* f[5]`, five pointers back to back, and may be filled as such; the members are spelled out one by one
+ * because the generated Rust bindings and their check carry scalar members only.
+ *
+ * zkp_json_sigma_batch, the reader: the contract of zkp_json_dlog_*_batch.  out_status[b]: ZKP_DOC_OK; ZKP_DOC_INVALID (a missing or duplicate
+ * field, "ek" without "n", a wrong JSON type, a string that is no integer of the named form; every field of the document is zero);
+ * ZKP_DOC_HOST_PATH (a negative field, or one wider than its array; THAT field is zero, the others are converted).  flags 0: host arrays, the
+ * tolerant host tokeniser (white space, any field order, unknown fields skipped — inside "ek" too —, escapes in names decoded).
+ * ZKP_F_DEVICE_PTRS: outputs and status in device memory; the text is uploaded once; a byte-for-byte canonical document is scanned on the
+ * device, any other falls back to the flags-0 path as a sub-batch and is merged in.  Arrays and statuses equal the flags-0 call's.
+ * zkp_json_write_sigma_batch, the writer: the contract of the writers above (sizing call with out_text == NULL, batch + 1 offsets of 64 bits,
+ * ZKP_EINVAL with no byte touched when text_cap is short, canonical text as the reader defines it); ZKP_F_DEVICE_PTRS applies to the limb
+ * arrays and out_status, so the output of a zkp_*_prove_batch call is serialised where it lies.
+ * n_bits in {1024, 2048, 4096}, batch 0 .. 2^24; zkp_json_doc_bound answers for the eight kinds. */
+typedef struct zkp_sigma_fields { uint32_t* f0; uint32_t* f1; uint32_t* f2; uint32_t* f3; uint32_t* f4; } zkp_sigma_fields;
+int32_t zkp_json_sigma_batch(zkp_ctx* ctx, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
+                             uint64_t batch, uint32_t bigint_forms, const zkp_sigma_fields* out, uint8_t* out_status, uint32_t flags);
+int32_t zkp_json_write_sigma_batch(zkp_ctx* ctx, uint32_t doc_kind, uint32_t n_bits, uint64_t batch, const zkp_sigma_fields* in,
+                                   uint32_t bigint_forms, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status,
+                                   uint32_t flags);
+/* The four verifies on documents.  proof_kind: one of the four ZKP_JSON_DOC_*_PROOF kinds; statement b is of the kind in front of it.
+ * Statement b and proof b are two spans of the same `text` (host memory, uploaded once); one status byte and one verdict byte per pair come
+ * out; ZKP_F_DEVICE_PTRS applies to out_status and out_verdict only.  = both readers (device route) into arrays the call owns, a domain
+ * check on the device, the type's zkp_*_verify_batch on those arrays with one key per pair, taken from its statement; no limb travels to
+ * the host.  out_status[b] starts as the worse of the two documents' statuses (ZKP_DOC_INVALID beats ZKP_DOC_HOST_PATH beats ZKP_DOC_OK).
+ * A pair still OK becomes ZKP_DOC_HOST_PATH when its key is even or below 2, when one of its 2kw-wide fields is >= n^2, or when MulProof.f
+ * is >= n.  Every honest value is inside this domain; outside it the reference still has a verdict (mod_pow, % and Paillier::add reduce,
+ * the challenge hashes the raw value) that the limb kernels were never specified to give, and reducing first would change the hash.
+ * out_verdict[b]: what the type's verify gives where the status is ZKP_DOC_OK (ZKP_VERDICT_MALFORMED where multiplication_proof.rs:133
+ * panics included), ZKP_VERDICT_REJECT everywhere else.  The whole batch is launched and the verdicts of unread pairs are masked
+ * afterwards: such a pair is zero rows, costs its share of the launch, changes no other verdict and never fails the call. */
+int32_t zkp_sigma_verify_json_batch(zkp_ctx* ctx, uint32_t proof_kind, const char* text, const uint64_t* st_off, const uint64_t* st_len,
+                                    const uint64_t* pf_off, const uint64_t* pf_len, uint64_t batch, uint32_t n_bits, uint32_t bigint_forms,
+                                    uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */, uint32_t flags);
 
 /* ------------------------------------------------------------------ several GPUs behind one caller
  * The reference spreads a proof's rows over a rayon pool (src/zkproofs/range_proof.rs:161-187,270-348); here a batch

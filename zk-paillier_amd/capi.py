@@ -130,6 +130,12 @@ EXPORTS = {
                                                     C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_dlog_verify_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_json_sigma_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_uint32]),
+    "zkp_json_write_sigma_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_uint32]),
+    "zkp_sigma_verify_json_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_correct_key_ni_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "zkp_dlog_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -204,6 +210,15 @@ DOC_OK, DOC_INVALID, DOC_HOST_PATH = 0, 2, 3
 GATHER_HOST, GATHER_RCCL, GATHER_COPY = 0, 1, 2
 JSON_DOC_ENCRYPTED_PAIRS, JSON_DOC_RANGE_PROOF, JSON_DOC_RANGE_PROOF_NI, JSON_DOC_CORRECT_KEY_PROOF = 0, 1, 2, 3
 JSON_DOC_DLOG_PROOF, JSON_DOC_DLOG_STATEMENT = 5, 6
+(JSON_DOC_ZERO_STATEMENT, JSON_DOC_ZERO_PROOF, JSON_DOC_CIPHERTEXT_STATEMENT, JSON_DOC_CIPHERTEXT_PROOF, JSON_DOC_VERLIN_STATEMENT, JSON_DOC_VERLIN_PROOF,
+ JSON_DOC_MUL_STATEMENT, JSON_DOC_MUL_PROOF) = range(8, 16)
+# fields per sigma-proof document kind, in declaration order (a statement's first one is the key)
+SIGMA_FIELDS = {8: 2, 9: 2, 10: 2, 11: 3, 12: 4, 13: 5, 14: 4, 15: 5}
+
+
+class SigmaFields(C.Structure):
+    """zkp_sigma_fields"""
+    _fields_ = [("f", C.c_void_p * 5)]
 
 
 def json_doc_bound(doc_kind: int, n_bits: int, error_factor: int = SECURITY_PARAMETER, forms: int = 0) -> int:
@@ -748,4 +763,46 @@ class Context:
         s_off, s_len, p_off, p_len = (np.ascontiguousarray(a) for a in (off[:B], ln[:B], off[B:], ln[B:]))
         self.check(self.lib.zkp_dlog_verify_json_batch(self.h, C.cast(buf, C.c_void_p), ptr(s_off), ptr(s_len), ptr(p_off), ptr(p_len), B, n_bits, y_bits, bare_form,
                                                        ptr(out_status), ptr(out_verdict), ZKP_F_DEVICE_PTRS if device else 0))
+        return out_status, out_verdict
+
+    # ---- ZeroProof / CiphertextProof / VerlinProof / MulProof documents and their statements (JSON_DOC_ZERO_STATEMENT .. JSON_DOC_MUL_PROOF)
+    @staticmethod
+    def _sigma_fields(kind, arrs):
+        if kind not in SIGMA_FIELDS or len(arrs) != SIGMA_FIELDS[kind]:
+            raise ValueError(f"document kind {kind} has {SIGMA_FIELDS.get(kind)} fields, {len(arrs)} given")
+        f = SigmaFields()
+        for i, a in enumerate(arrs):
+            f.f[i] = ptr(a)
+        return f
+
+    def json_sigma(self, kind: int, docs, n_bits: int, forms: int, out_fields, out_status):
+        """zkp_json_sigma_batch.  out_fields: one array per field of the kind, in declaration order, [len(docs)][words].  numpy outputs:
+        tokenised on the host; torch cuda tensors: scanned on the device (the documents stay host text)"""
+        buf, off, ln = self._json_docs(docs)
+        f = self._sigma_fields(kind, out_fields)
+        self.check(self.lib.zkp_json_sigma_batch(self.h, kind, C.cast(buf, C.c_void_p), ptr(off), ptr(ln), n_bits, len(docs), forms, C.byref(f), ptr(out_status),
+                                                 self._flags(*out_fields, out_status)))
+
+    def json_write_sigma(self, kind: int, n_bits: int, batch: int, fields, forms: int = 0, out_status=None):
+        """zkp_json_write_sigma_batch -> (text, offsets, status) as the other writers; fields: numpy arrays or torch cuda tensors"""
+        f = self._sigma_fields(kind, fields)
+        fl = self._flags(*fields, out_status)
+        return self._json_write(lambda t, cap, off: self.lib.zkp_json_write_sigma_batch(self.h, kind, n_bits, batch, C.byref(f), forms, t, cap, off, ptr(out_status), fl),
+                                batch, out_status)
+
+    def sigma_verify_json(self, kind: int, statements, proofs, n_bits: int, forms: int = 0, device: bool = False, out_status=None, out_verdict=None):
+        """zkp_sigma_verify_json_batch: kind is the PROOF kind; statement b and proof b (two lists of documents) -> (status, verdict) bytes.
+        device: the two outputs are torch cuda tensors (made here when not given)."""
+        assert len(statements) == len(proofs)
+        B = len(statements)
+        buf, off, ln = self._json_docs(list(statements) + list(proofs))
+        if out_status is None or out_verdict is None:
+            if device:
+                import torch
+                out_status = torch.zeros(B, dtype=torch.uint8, device="cuda"); out_verdict = torch.zeros(B, dtype=torch.uint8, device="cuda")
+            else:
+                out_status = np.zeros(B, np.uint8); out_verdict = np.zeros(B, np.uint8)
+        s_off, s_len, p_off, p_len = (np.ascontiguousarray(a) for a in (off[:B], ln[:B], off[B:], ln[B:]))
+        self.check(self.lib.zkp_sigma_verify_json_batch(self.h, kind, C.cast(buf, C.c_void_p), ptr(s_off), ptr(s_len), ptr(p_off), ptr(p_len), B, n_bits, forms,
+                                                        ptr(out_status), ptr(out_verdict), ZKP_F_DEVICE_PTRS if device else 0))
         return out_status, out_verdict

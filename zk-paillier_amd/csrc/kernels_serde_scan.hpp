@@ -12,13 +12,16 @@
 //   NiCorrectKeyProof  {"sigma_vec":["D",..11]}            one array instead of two
 //   CompositeDLogProof {"x":X,"y":X}                       heads only: the head phase, then `}` and the document's end
 //   DLogStatement      {"N":X,"g":X,"ni":X}
+//   ZeroStatement .. MulProof                              heads only, up to five of three widths, a statement's first one behind `{"ek":{"n":`
+// Which heads a kind has — literal, destination, limbs, digit bound, text form — is the table w_doc_spec() (kernels_serde_write.hpp); the host
+// copies the kind's rows into ScanJob::head, and the head phase below is a loop over them that knows no document kind.
 // A document that differs in ONE byte from this is marked `fall back` and nothing else: the host tokeniser (zkp_api_serde.inc) reads it and
 // decides its status.  So the scanner never has an opinion about a document it does not fully understand, and for one it understands the
 // only thing left open is whether every number fits its field — k_dec2bin's overflow status, the host reader's ZKP_DOC_HOST_PATH.
 //
 // Phases inside the wavefront (every loop is bounded by the document's length, no byte outside [doc_off, doc_off + doc_len) is read):
-//   head    (RangeProofNi and the two DLog kinds) the un-annotated integers: literal, value, literal ... — 64 bytes per step, the closing
-//           quote / bracket found by ballot; every value is bounded by ITS field's width (ScanJob::head_words, head_dig)
+//   head    (every kind with heads) the un-annotated integers: literal, value, literal ... — 64 bytes per step, the closing
+//           quote / bracket found by ballot; every value is bounded by ITS field's width (ScanHead::words, dig)
 //   mark    one pass over the rest, 64 bytes per step: a digit behind a quote opens a number, `{"O` / `{"M` opens a row; ballots and
 //           popcounts number both (the slot of a number depends on the kinds of the rows before it) and count the non-digit bytes in
 //           front of every number.  Positions go to LDS.
@@ -37,6 +40,14 @@ namespace zkp {
 constexpr int SCAN_MAX_EF = 256;
 constexpr int SCAN_MAX_TOK = 6 * SCAN_MAX_EF;
 constexpr int SCAN_MAX_BYTES = 1024;            // bytes of the widest head integer (ciphertext under a 4096-bit key; a DLog field has at most half)
+static_assert(4 * W_MAX_HEAD_WORDS <= SCAN_MAX_BYTES, "a 2 kw head under a 4096-bit key (c, z2, e_db ..) must fit ScanLds::bytes in the byte-array form");
+
+// one head of the job's kind: w_doc_spec()'s row with the widths and forms of this batch filled in
+struct ScanHead {
+  char lit[W_HEAD_LIT]; uint32_t lit_n;        // the literal in front of it, e.g. `{"ek":{"n":`, `},"c":`, `,"z_prime":`
+  uint32_t words, dig, form;                  // limbs of its array element, most decimal digits of a value that wide, ZKP_BIGINT_*
+  uint32_t* dst;                              // [B][words]
+};
 
 struct ScanJob {
   const char* text;            // the uploaded span: byte `a` of the caller's text is text[a - lo]
@@ -48,13 +59,12 @@ struct ScanJob {
   uint32_t doc_kind;           // W_DOC_*
   uint32_t ef, kw, key_form, bare_form;      // ef: entries per array and rows per document (NiCorrectKeyProof: the 11 of sigma_vec)
   uint32_t dig_n, dig_c;       // decimal digits of the widest kw- / 2kw-word value
-  uint32_t head_words[3], head_dig[3];       // limbs and most decimal digits of head integer i (w_heads(doc_kind) of them)
-  uint32_t* keys;              // [B][kw] ek.n                       head 0: also N of a DLogStatement, x of a CompositeDLogProof
-  uint32_t* range; uint32_t* ct;             // heads 1 and 2: also g, ni / y
+  uint32_t n_heads, heads_only;              // heads_only: `}` and the document's end follow the last head
+  ScanHead head[W_MAX_HEADS];
   uint8_t* kind; uint8_t* j;   // [B][EF], zero on entry
-  zkp_dec_item* items[W_ARRS]; // W_ARR_N, _RANGE, _CT: [B] (the heads, decimal forms only); W_ARR_C1 .. _R2: [B * EF]; sigma_vec is W_ARR_W1, as for the writer
+  zkp_dec_item* items[W_ARRS]; // head i: items[i] [B] (decimal form only, else null); W_ARR_C1 .. _R2: [B * EF]; sigma_vec is W_ARR_W1, as for the writer
   uint32_t* row_doc;           // [B * EF] item -> document, for k_mark_docs
-  uint32_t* head_doc;          // [B] (kinds with heads only, like keys, range, ct)
+  uint32_t* head_doc;          // [B] (kinds with heads only)
   uint8_t* fast;               // [B] 1 = scanned here, 0 = fall back
   uint8_t* status;             // [B] ZKP_DOC_OK | ZKP_DOC_INVALID (a fall-back document, until the host reader has spoken)
 };
@@ -179,7 +189,7 @@ struct ScanShape {
 __device__ __forceinline__ ScanShape sc_shape(const ScanJob& J, const ScanLds& L) {
   ScanShape S;
   const bool ck = J.doc_kind == W_DOC_CK;
-  S.arrs = ck ? 1u : J.doc_kind == W_DOC_PROOF || w_heads_only(J.doc_kind) ? 0u : 2u;
+  S.arrs = ck ? 1u : J.doc_kind == W_DOC_PROOF || J.heads_only ? 0u : 2u;
   S.cnt = J.ef;
   S.arr_words = ck ? J.kw : 2 * J.kw; S.arr_dig = ck ? J.dig_n : J.dig_c;
   S.arr_item = ck ? W_ARR_W1 : W_ARR_C1;
@@ -220,35 +230,17 @@ __device__ __forceinline__ const char* sc_row_after(const ScanShape& S, const Sc
   return S.close;
 }
 
-// the literal in front of head integer i
-__device__ __forceinline__ const char* sc_head_lit(uint32_t doc_kind, uint32_t i, uint32_t& n) {
-  if (doc_kind == W_DOC_NI) {
-    if (i == 0) { n = 11; return "{\"ek\":{\"n\":"; }
-    if (i == 1) { n = 10; return "},\"range\":"; }
-    n = 14; return ",\"ciphertext\":";
-  }
-  if (doc_kind == W_DOC_DLOG_PROOF) { n = 5; return i == 0 ? "{\"x\":" : ",\"y\":"; }
-  if (i == 2) { n = 6; return ",\"ni\":"; }
-  n = 5; return i == 0 ? "{\"N\":" : ",\"g\":";
-}
-
 // -> wave-uniform: document [t, t + len) is canonical.  On true: L holds its numbers and rows, head_* its head (already converted unless decimal)
 __device__ inline bool sc_scan_doc(const ScanJob& J, const ScanShape& S, uint64_t b, const char* t, uint32_t len, uint64_t text_at, ScanLds& L, uint32_t& ntok, int lane) {
   const uint32_t ef = J.ef, kw = J.kw;
   uint32_t pos = 0;
-  const uint32_t heads = w_heads(J.doc_kind);
-  for (uint32_t i = 0; i < heads; i++) {
-    uint32_t n;
-    const char* lit = sc_head_lit(J.doc_kind, i, n);
-    if (!sc_lit(t, len, pos, lit, n, lane)) return false;
-    pos += n;
-    const uint32_t words = J.head_words[i];
-    uint32_t* dst = i == 0 ? J.keys : i == 1 ? J.range : J.ct;
-    if (!sc_head_value(t, len, pos, i == 0 ? J.key_form : J.bare_form, words, J.head_dig[i], dst + b * words, J.items[i] ? J.items[i] + b : nullptr, text_at, b * words, L,
-                       lane))
-      return false;
+  for (uint32_t i = 0; i < J.n_heads; i++) {
+    const ScanHead& h = J.head[i];
+    if (!sc_lit(t, len, pos, h.lit, h.lit_n, lane)) return false;
+    pos += h.lit_n;
+    if (!sc_head_value(t, len, pos, h.form, h.words, h.dig, h.dst + b * h.words, J.items[i] ? J.items[i] + b : nullptr, text_at, b * h.words, L, lane)) return false;
   }
-  if (w_heads_only(J.doc_kind)) { ntok = 0; return sc_lit(t, len, pos, "}", 1, lane) && pos + 1 == len; }
+  if (J.heads_only) { ntok = 0; return sc_lit(t, len, pos, "}", 1, lane) && pos + 1 == len; }
   const uint32_t T = pos;
   if (!sc_lit(t, len, T, S.open, S.open_n, lane)) return false;
 
@@ -329,7 +321,7 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
   const uint32_t ef = J.ef, kw = J.kw;
   const uint64_t len64 = J.doc_len[b], off = J.doc_off[b];
   const bool ni = J.doc_kind == W_DOC_NI;
-  const uint32_t heads = w_heads(J.doc_kind);
+  const uint32_t heads = J.n_heads;
   if (ni && lane == 0) {
     // `"}}],"error_factor":N}`
     const char* head = "\"}}],\"error_factor\":";
@@ -356,7 +348,7 @@ __global__ void __launch_bounds__(64) k_json_scan(ScanJob J) {
     J.status[b] = ok ? ZKP_DOC_OK : ZKP_DOC_INVALID;
     if (heads) J.head_doc[b] = (uint32_t)b;
     for (uint32_t i = 0; i < heads && !ok; i++)
-      if (J.items[i]) J.items[i][b] = zkp_dec_item{J.zero_at, b * J.head_words[i], 1, J.head_words[i]};
+      if (J.items[i]) J.items[i][b] = zkp_dec_item{J.zero_at, b * J.head[i].words, 1, J.head[i].words};
   }
   for (uint32_t k = lane; k < S.arrs * S.cnt; k += 64) {
     const uint32_t which = k / S.cnt, i = k - which * S.cnt;
@@ -450,6 +442,47 @@ __global__ void __launch_bounds__(256) k_dlog_domain_check(uint32_t* __restrict_
   if (st == ZKP_DOC_OK) return;
   for (uint32_t w = lane; w < kw; w += 64) { N[b * kw + w] = 0; g[b * kw + w] = 0; ni[b * kw + w] = 0; x[b * kw + w] = 0; }
   for (uint32_t w = lane; w < yw; w += 64) y[b * yw + w] = 0;
+}
+
+
+// ---- ZeroProof / CiphertextProof / VerlinProof / MulProof::verify on documents: the same question for a (statement, proof) pair of those
+// types.  Up to SIGMA_MAX_ARR arrays: arr[0] is the key n [B][kw], the others the fields of both documents; rule[i] says what field i must
+// satisfy: SIGMA_LT_NN: < n^2 (nn [B][2 kw], squared on the device beforehand; words[i] == 2 kw), SIGMA_LT_N: < n (MulProof.f, words[i] == kw),
+// SIGMA_ANY: nothing (the z fields are integers, not residues).  A pair still OK becomes ZKP_DOC_HOST_PATH when its key is even or trivial
+// as k_setup defines it (no bits above the lowest), or a field breaks its rule: the reference reduces such a value (mod_pow, %,
+// Paillier::add) and hashes it raw, the limb kernels were never specified for it.  Every row of a pair that is not OK is zeroed: the key 0
+// is marked by k_setup (nothing is stored for it) and answered MALFORMED by the compare kernels, masked afterwards.  One wavefront per pair.
+constexpr int SIGMA_MAX_ARR = 10;
+enum { SIGMA_ANY = 0, SIGMA_LT_NN = 1, SIGMA_LT_N = 2 };
+struct SigmaDomainArgs {
+  uint32_t* arr[SIGMA_MAX_ARR]; uint32_t words[SIGMA_MAX_ARR]; uint32_t rule[SIGMA_MAX_ARR];
+  uint32_t n_arr, kw;
+  const uint32_t* nn;
+  uint64_t B;
+  const uint8_t* proof_status; uint8_t* status;
+};
+__global__ void __launch_bounds__(256) k_sigma_domain_check(SigmaDomainArgs a) {
+  const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= a.B) return;
+  const uint32_t kw = a.kw;
+  const uint8_t s1 = a.status[b], s2 = a.proof_status[b];
+  uint8_t st = (s1 == ZKP_DOC_INVALID || s2 == ZKP_DOC_INVALID) ? (uint8_t)ZKP_DOC_INVALID : (s1 != ZKP_DOC_OK || s2 != ZKP_DOC_OK) ? (uint8_t)ZKP_DOC_HOST_PATH : (uint8_t)ZKP_DOC_OK;
+  if (st == ZKP_DOC_OK) {
+    const uint32_t* n = a.arr[0] + b * kw;
+    bool above = false;                                   // a bit above the lowest: n >= 2
+    for (uint32_t w = lane; w < kw; w += 64) above = above || (w == 0 ? n[0] >> 1 : n[w]) != 0;
+    bool inside = (n[0] & 1u) != 0 && __any(above);
+    for (uint32_t i = 1; i < a.n_arr; i++) {
+      if (a.rule[i] == SIGMA_LT_NN) inside = sc_less(a.arr[i] + b * 2 * kw, a.nn + b * 2 * kw, 2 * kw, lane) && inside;
+      else if (a.rule[i] == SIGMA_LT_N) inside = sc_less(a.arr[i] + b * kw, n, kw, lane) && inside;
+    }
+    if (!inside) st = ZKP_DOC_HOST_PATH;
+  }
+  if (lane == 0) a.status[b] = st;
+  if (st == ZKP_DOC_OK) return;
+  for (uint32_t i = 0; i < a.n_arr; i++)
+    for (uint32_t w = lane; w < a.words[i]; w += 64) a.arr[i][b * a.words[i] + w] = 0;
 }
 
 }  // namespace zkp

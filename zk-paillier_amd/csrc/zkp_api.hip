@@ -159,7 +159,8 @@ static int32_t zkp_caught(zkp_ctx* c, int32_t st, const char* what) noexcept {
   X(zkp_ciphertext_proof_verify_batch) X(zkp_verlin_proof_prove_batch) X(zkp_verlin_proof_verify_batch)                          \
   X(zkp_mul_proof_prove_batch) X(zkp_mul_proof_verify_batch) X(zkp_correct_message_prove_batch) X(zkp_correct_message_verify_batch)           \
   X(zkp_diag_basen) X(zkp_diag_basen_last) X(zkp_diag_set_enc_form) X(zkp_diag_set_r2l) X(zkp_diag_r2l_last) X(zkp_diag_set_r2l_lanes) X(zkp_diag_r2l_lanes_last) X(zkp_diag_set_key_cache) X(zkp_diag_key_cache_state) \
-  X(zkp_diag_set_fuse_hash) X(zkp_diag_last_fused_hash)
+  X(zkp_diag_set_fuse_hash) X(zkp_diag_last_fused_hash)                                                                            \
+  X(zkp_json_sigma_batch) X(zkp_json_write_sigma_batch) X(zkp_sigma_verify_json_batch)
 
 struct LatEngine {
   void* handle = nullptr;

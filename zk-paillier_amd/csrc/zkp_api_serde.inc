@@ -277,11 +277,11 @@ namespace {
 // 16 bytes '0' follow the span
 struct ScanText { char* d; uint64_t lo, span; };
 int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits = 0, const ScanText* pre = nullptr);
+                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits = 0, const ScanText* pre = nullptr, uint32_t* const* head_dst = nullptr);
 int32_t json_scan_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                        const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* out_status, uint32_t y_bits = 0) {
+                        const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* out_status, uint32_t y_bits = 0, uint32_t* const* head_dst = nullptr) {
   Stage s(c, ZKP_F_DEVICE_PTRS);
-  int32_t st = json_scan(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, sigma, out_status, y_bits);
+  int32_t st = json_scan(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, sigma, out_status, y_bits, nullptr, head_dst);
   if (st && !s.st) s.st = st;
   const int32_t fin = s.finish();
   if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
@@ -603,8 +603,8 @@ template <class T> int32_t scan_merge(zkp_ctx* c, Stage& s, const std::vector<T>
 //   - RangeProofNi: the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader
 //     decides before it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH;
 //   - what was converted of a document that ends up unconverted is cleared where the host reader clears it: everywhere but in sigma.
-int32_t json_dlog_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t bare_form, uint32_t kw, uint32_t yw,
-                       uint32_t* const* out, uint8_t* out_status);
+int32_t json_heads_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t key_form, uint32_t bare_form, uint32_t kw,
+                        uint32_t yw, uint32_t* const* out, uint8_t* out_status);
 void scan_span(const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint64_t* lo, uint64_t* hi) {
   for (uint64_t b = 0; b < B; b++) if (doc_len[b]) { *lo = std::min(*lo, doc_off[b]); *hi = std::max(*hi, doc_off[b] + doc_len[b]); }
 }
@@ -617,16 +617,18 @@ int32_t scan_upload(zkp_ctx* c, Stage& s, const char* text, uint64_t lo, uint64_
   HIPCHK(c, hipMemsetAsync(o->d + o->span, '0', 16, c->stream));
   return ZKP_OK;
 }
-// The two DLog kinds (heads only): d.n, d.range, d.ciphertext are the destinations of N, g, ni / x, y (y: y_bits / 32 words), d.n_stride = kw, forms
-// is the bare form alone, and nothing is cleared afterwards: as with sigma, an over-wide field is zero and the others stay converted.
+// The heads-only kinds: head_dst[i] is the destination of head i of w_doc_spec(doc_kind) (the two DLog kinds may name N, g, ni / x, y as d.n, d.range,
+// d.ciphertext instead; y: y_bits / 32 words), d.n_stride = kw, forms is ZKP_BIGINT_FORMS(key, bare) (the DLog kinds have no key: the bare form
+// alone), and nothing is cleared afterwards: as with sigma, an over-wide field is zero and the others stay converted.
 // pre: the text is already on the device (the caller also keeps the diagnostics: events and counters of BOTH scans of its call).
 int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits, const ScanText* pre) {
+                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits, const ScanText* pre, uint32_t* const* head_dst) {
   const bool ni = doc_kind == W_DOC_NI, ck = doc_kind == W_DOC_CK, has_pairs = ni || doc_kind == W_DOC_PAIRS, has_rows = ni || doc_kind == W_DOC_PROOF;
-  const bool dl = w_heads_only(doc_kind), heads = ni || dl;
+  const WDocSpec& spec = w_doc_spec(doc_kind);
+  const bool dl = spec.heads_only, heads = spec.n_heads != 0;
   const uint64_t B = d.batch, EF = ck ? ZKP_CORRECT_KEY_M2 : dl ? 0 : d.error_factor, rows = B * EF;
   const uint32_t kw = d.n_bits / 32, yw = y_bits / 32;
-  const uint32_t key_form = dl ? forms & 15u : (forms >> 4) & 15u, bare_form = forms & 15u;
+  const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
   const bool per_key = d.n_stride != 0;
   int32_t st = ZKP_OK;
   ScanText up{};
@@ -646,22 +648,27 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
   J.max_len = zkp_json_doc_bound(doc_kind, d.n_bits, d.error_factor, forms);
   J.doc_kind = doc_kind; J.ef = (uint32_t)EF; J.kw = kw; J.key_form = key_form; J.bare_form = bare_form;
   J.dig_n = zkp_decimal_pitch(kw) - 1; J.dig_c = zkp_decimal_pitch(2 * kw) - 1;      // (max_digits below)
-  const uint32_t head_words[3] = {kw, doc_kind == W_DOC_DLOG_PROOF ? yw : kw, ni ? 2 * kw : kw};
-  for (int i = 0; i < 3; i++) { J.head_words[i] = head_words[i]; J.head_dig[i] = zkp_decimal_pitch(head_words[i]) - 1; }
-  uint32_t* const out_range = const_cast<uint32_t*>(d.range);
-  uint32_t* const out_ct = const_cast<uint32_t*>(d.ciphertext);
-  if (heads) { J.keys = per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4); J.range = out_range; J.ct = out_ct; }
-  if (has_rows) { J.kind = d.resp_kind; J.j = d.resp_j; }
-  struct Target { int arr; uint32_t* dst; uint32_t words; };      // arr < W_ARR_C1: one number per document, else EF
+  // the heads: the table's rows with this batch's widths, forms and destinations
+  uint32_t* const legacy_dst[3] = {heads ? (per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4)) : nullptr, const_cast<uint32_t*>(d.range),
+                                   const_cast<uint32_t*>(d.ciphertext)};
+  if (!head_dst) head_dst = legacy_dst;
+  J.n_heads = spec.n_heads; J.heads_only = spec.heads_only;
+  struct Target { int arr; uint32_t* dst; uint32_t words; };      // arr < W_ARR_C1: head `arr`, one number per document; else EF
   std::vector<Target> targets;
-  if (heads) targets.insert(targets.end(), {{W_ARR_N, J.keys, head_words[0]}, {W_ARR_RANGE, out_range, head_words[1]}});
-  if (w_heads(doc_kind) == 3) targets.push_back({W_ARR_CT, out_ct, head_words[2]});
+  for (uint32_t i = 0; i < spec.n_heads; i++) {
+    ScanHead& h = J.head[i];
+    w_head_lit(h, spec.h[i]);
+    h.words = w_head_words(spec.h[i], kw, yw); h.dig = zkp_decimal_pitch(h.words) - 1;
+    h.form = spec.h[i].key ? key_form : bare_form; h.dst = head_dst[i];
+    targets.push_back({(int)i, h.dst, h.words});
+  }
+  if (has_rows) { J.kind = d.resp_kind; J.j = d.resp_j; }
   if (has_pairs) targets.insert(targets.end(), {{W_ARR_C1, d.c1, 2 * kw}, {W_ARR_C2, d.c2, 2 * kw}});
   if (has_rows) targets.insert(targets.end(), {{W_ARR_W1, d.resp_w1, kw}, {W_ARR_R1, d.resp_r1, kw}, {W_ARR_W2, d.resp_w2, kw}, {W_ARR_R2, d.resp_r2, kw}});
   if (ck) targets.push_back({W_ARR_W1, sigma, kw});
   for (const Target& t : targets) {
     const bool head = t.arr < W_ARR_C1;
-    if (head && (t.arr == W_ARR_N ? key_form : bare_form) != ZKP_BIGINT_DEC) continue;
+    if (head && J.head[t.arr].form != ZKP_BIGINT_DEC) continue;
     J.items[t.arr] = (zkp_dec_item*)s.take((head ? B : rows) * sizeof(zkp_dec_item));
   }
   J.row_doc = (uint32_t*)s.take(rows * 4);
@@ -691,7 +698,7 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
   for (const Target& t : targets) if (t.arr < W_ARR_C1 && !st) st = convert(t);
   if (st) return st;
   if (ni && !per_key) {
-    hipLaunchKernelGGL(k_scan_key_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)J.keys, d.n, kw, B, (const uint8_t*)J.fast, dstat);
+    hipLaunchKernelGGL(k_scan_key_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)J.head[0].dst, d.n, kw, B, (const uint8_t*)J.fast, dstat);
     HIPCHK(c, hipGetLastError());
   }
   for (const Target& t : targets) if (t.arr >= W_ARR_C1 && !st) st = convert(t);
@@ -723,8 +730,9 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     hp.batch = nf; hp.n = h[W_ARR_N].data(); hp.range = h[W_ARR_RANGE].data(); hp.ciphertext = h[W_ARR_CT].data(); hp.c1 = h[W_ARR_C1].data(); hp.c2 = h[W_ARR_C2].data();
     hp.resp_kind = hkind.data(); hp.resp_j = hj.data();
     hp.resp_w1 = h[W_ARR_W1].data(); hp.resp_r1 = h[W_ARR_R1].data(); hp.resp_w2 = h[W_ARR_W2].data(); hp.resp_r2 = h[W_ARR_R2].data();
-    uint32_t* const hdl[3] = {h[W_ARR_N].data(), h[W_ARR_RANGE].data(), h[W_ARR_CT].data()};
-    st = dl              ? json_dlog_host(text, foff.data(), flen.data(), nf, doc_kind, bare_form, kw, yw, hdl, hst.data())
+    uint32_t* hdl[W_MAX_HEADS];
+    for (int i = 0; i < W_MAX_HEADS; i++) hdl[i] = h[i].data();
+    st = dl              ? json_heads_host(text, foff.data(), flen.data(), nf, doc_kind, key_form, bare_form, kw, yw, hdl, hst.data())
          : ni            ? zkp_json_range_proof_ni_batch(c, text, foff.data(), flen.data(), forms, &hp, hst.data(), 0)
          : ck            ? zkp_json_correct_key_proof_batch(c, text, foff.data(), flen.data(), d.n_bits, nf, h[W_ARR_W1].data(), hst.data(), 0)
          : has_pairs     ? zkp_json_encrypted_pairs_batch(c, text, foff.data(), flen.data(), &hp, hst.data(), 0)
@@ -946,14 +954,20 @@ constexpr uint64_t cstrlen(const char* s) { return *s ? 1 + cstrlen(s + 1) : 0; 
 
 extern "C" uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms) {
   const uint32_t key_form = (bigint_forms >> 4) & 15u, bare_form = bigint_forms & 15u;
-  const bool dl = doc_kind == ZKP_JSON_DOC_DLOG_PROOF || doc_kind == ZKP_JSON_DOC_DLOG_STATEMENT;
+  const WDocSpec& spec = w_doc_spec(doc_kind);
+  const bool dl = spec.heads_only;
   if ((n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || (doc_kind > ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl) || (bigint_forms >> 8) ||
       key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (doc_kind != ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl && error_factor == 0))
     return 0;
   const uint32_t kw = n_bits / 32;
-  // (the proof's y at its widest, y_bits == n_bits)
-  if (doc_kind == ZKP_JSON_DOC_DLOG_PROOF) return cstrlen("{\"x\":,\"y\":}") + 4 + 2 * max_form_len(kw, bare_form);
-  if (doc_kind == ZKP_JSON_DOC_DLOG_STATEMENT) return cstrlen("{\"N\":,\"g\":,\"ni\":}") + 6 + 3 * max_form_len(kw, bare_form);
+  if (dl) {
+    // a heads-only kind: the table's literals, every number at its widest between its quotes or brackets, `}` (a CompositeDLogProof's y at
+    // y_bits == n_bits)
+    uint64_t bound = 1;
+    for (uint32_t i = 0; i < spec.n_heads; i++)
+      bound += strlen(spec.h[i].lit) + 2 + max_form_len(w_head_words(spec.h[i], kw, kw), spec.h[i].key ? key_form : bare_form);
+    return bound;
+  }
   const uint64_t EF = error_factor, dn = max_digits(kw), dc = max_digits(2 * kw);
   if (doc_kind == ZKP_JSON_DOC_CORRECT_KEY_PROOF) return cstrlen("{\"sigma_vec\":[") + ZKP_CORRECT_KEY_M2 * (dn + 3) - 1 + cstrlen("]}");
   // {"c1":["..",".."],"c2":[..]}
@@ -969,14 +983,15 @@ extern "C" uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint3
 }
 
 // the fields of a heads-only document (the two DLog kinds): field i is one number of words[i] limbs per document
-struct WHeads { const uint32_t* a[3]; uint32_t words[3]; };
+struct WHeads { const uint32_t* a[W_MAX_HEADS]; uint32_t words[W_MAX_HEADS]; };
 static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, const zkp_range_ni_proofs* p, uint32_t n_bits, uint64_t B, uint64_t EF,
                                const uint32_t* sigma, uint32_t forms, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags,
                                const WHeads* hd = nullptr) {
   if (!c) return ZKP_EINVAL;
   const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
   const bool ck = doc_kind == W_DOC_CK, ni = doc_kind == W_DOC_NI, has_pairs = doc_kind == W_DOC_PAIRS || ni, has_proof = doc_kind == W_DOC_PROOF || ni;
-  const bool dl = w_heads_only(doc_kind);
+  const WDocSpec& spec = w_doc_spec(doc_kind);
+  const bool dl = spec.heads_only;
   const uint32_t kw = n_bits / 32;
   bool bad = !out_doc_off || (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24) ||
              (forms >> 8) || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (!ck && !dl && !p) || (!ck && !dl && (EF == 0 || EF > 256));
@@ -993,8 +1008,10 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
   Stage s(c, flags);
   WJob J{};
   J.B = B; J.ef = (uint32_t)EF; J.doc_kind = doc_kind; J.key_form = key_form; J.bare_form = bare_form;
-  J.per_proof_keys = ni && p->n_stride != 0;
-  J.slots = ck ? ZKP_CORRECT_KEY_M2 : dl ? w_heads(doc_kind) : (uint32_t)((ni ? 3 : 0) + (has_pairs ? 2 * EF : 0) + (has_proof ? 4 * EF : 0));
+  J.per_proof_keys = ni ? p->n_stride != 0 : 1;
+  J.n_heads = spec.n_heads; J.heads_only = spec.heads_only;
+  for (uint32_t i = 0; i < spec.n_heads; i++) { w_head_lit(J.head[i], spec.h[i]); J.head[i].key = spec.h[i].key; }
+  J.slots = ck ? ZKP_CORRECT_KEY_M2 : (uint32_t)(spec.n_heads + (has_pairs ? 2 * EF : 0) + (has_proof ? 4 * EF : 0));
   struct Todo { int arr; uint64_t count; uint32_t form; };
   std::vector<Todo> todo;
   auto add = [&](int arr, const uint32_t* src, uint64_t count, uint32_t words, uint32_t form) {
@@ -1007,7 +1024,7 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
   };
   const uint64_t rows = B * EF;
   if (ck) add(W_ARR_W1, sigma, B * ZKP_CORRECT_KEY_M2, kw, ZKP_BIGINT_DEC);
-  if (dl) for (uint32_t i = 0; i < w_heads(doc_kind); i++) add(W_ARR_N + (int)i, hd->a[i], B, hd->words[i], bare_form);
+  if (dl) for (uint32_t i = 0; i < spec.n_heads; i++) add((int)i, hd->a[i], B, hd->words[i], spec.h[i].key ? key_form : bare_form);
   if (ni) {
     add(W_ARR_N, p->n, p->n_stride ? B : 1, kw, key_form);
     add(W_ARR_RANGE, p->range, B, kw, bare_form);
@@ -1116,16 +1133,16 @@ extern "C" int32_t zkp_json_write_correct_key_proof_batch(zkp_ctx* c, uint32_t n
 // ---- CompositeDLogProof and DLogStatement (wi_dlog_proof.rs:32-43): {"x":X,"y":X} and {"N":X,"g":X,"ni":X}, every X an un-annotated curv BigInt
 // in the one form the caller names.
 namespace {
-// The flags-0 reader: the tolerant tokeniser, every number converted on the host (parse_bigint_value, as for the head of a RangeProofNi
-// document).  out[i]: [B][words of field i].  An invalid document leaves zero rows; an over-wide or negative field is zero, the others converted.
-int32_t json_dlog_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t bare_form, uint32_t kw, uint32_t yw,
-                       uint32_t* const* out, uint8_t* out_status) {
-  const bool pf = doc_kind == W_DOC_DLOG_PROOF;
-  const unsigned nf = w_heads(doc_kind);
-  static const char* const pf_names[2] = {"x", "y"};
-  static const char* const st_names[3] = {"N", "g", "ni"};
-  const char* const* names = pf ? pf_names : st_names;
-  const uint32_t words[3] = {kw, pf ? yw : kw, kw};
+// The flags-0 reader of every heads-only kind: the tolerant tokeniser, every number converted on the host (parse_bigint_value, as for the head
+// of a RangeProofNi document).  The fields are the rows of w_doc_spec(doc_kind); a key row is the object "ek" with a field "n" (its other
+// fields are skipped, as for a RangeProofNi).  out[i]: [B][words of field i].  An invalid document leaves zero rows; an over-wide or negative
+// field is zero, the others converted.
+int32_t json_heads_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t key_form, uint32_t bare_form, uint32_t kw,
+                        uint32_t yw, uint32_t* const* out, uint8_t* out_status) {
+  const WDocSpec& spec = w_doc_spec(doc_kind);
+  const unsigned nf = spec.n_heads;
+  uint32_t words[W_MAX_HEADS] = {};
+  for (unsigned f = 0; f < nf; f++) words[f] = w_head_words(spec.h[f], kw, yw);
   for (unsigned f = 0; f < nf; f++) memset(out[f], 0, (size_t)B * words[f] * 4);
   for_docs(B, [&](uint64_t b, unsigned) {
     JCur j{text, doc_off[b], doc_off[b] + doc_len[b]};
@@ -1133,11 +1150,20 @@ int32_t json_dlog_host(const char* text, const uint64_t* doc_off, const uint64_t
     bool host = false;
     j.object([&](const std::string& nm) {
       int f = -1;
-      for (unsigned q = 0; q < nf; q++) if (nm == names[q]) f = (int)q;
+      for (unsigned q = 0; q < nf; q++) if (nm == spec.h[q].name) f = (int)q;
       if (f < 0) return false;
       if (seen & (1u << f)) { j.ok = false; return true; }                      // duplicate field
       seen |= 1u << f;
-      host |= parse_bigint_value(j, bare_form, out[f] + b * words[f], words[f]) == ZKP_DOC_HOST_PATH;
+      if (!spec.h[f].key) { host |= parse_bigint_value(j, bare_form, out[f] + b * words[f], words[f]) == ZKP_DOC_HOST_PATH; return true; }
+      bool has_n = false;
+      j.object([&](const std::string& k) {
+        if (k != "n") return false;
+        if (has_n) { j.ok = false; return true; }
+        has_n = true;
+        host |= parse_bigint_value(j, key_form, out[f] + b * words[f], words[f]) == ZKP_DOC_HOST_PATH;
+        return true;
+      });
+      if (!has_n) j.ok = false;
       return true;
     });
     if (seen != (1u << nf) - 1) j.ok = false;                                   // missing field
@@ -1156,7 +1182,7 @@ int32_t json_dlog_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const c
   for (unsigned f = 0; f < w_heads(doc_kind); f++) bad = bad || !out[f];
   if (bad) { c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL; }
   const uint32_t kw = n_bits / 32;
-  if (!(flags & ZKP_F_DEVICE_PTRS)) return json_dlog_host(text, doc_off, doc_len, B, doc_kind, bare_form, kw, y_bits / 32, out, out_status);
+  if (!(flags & ZKP_F_DEVICE_PTRS)) return json_heads_host(text, doc_off, doc_len, B, doc_kind, 0, bare_form, kw, y_bits / 32, out, out_status);
   HIPCHK(c, hipSetDevice(c->device));
   zkp_range_ni_proofs d{};
   d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
@@ -1245,6 +1271,130 @@ extern "C" int32_t zkp_dlog_verify_json_batch(zkp_ctx* c, const char* text, cons
     if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_dlog_domain_check launch"; }
   }
   if (!st) st = zkp_dlog_verify_batch(c, n_bits, y_bits, B, arr[0], arr[1], arr[2], arr[3], dy, dv, ZKP_F_DEVICE_PTRS);
+  if (!st) {
+    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
+  }
+  if (!st) st = scan_event(c, 4);
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
+// ---- ZeroProof, CiphertextProof, VerlinProof, MulProof and their statements (zero_enc_proof.rs:26-41, correct_ciphertext.rs:22-39,
+// verlin_proof.rs:34-57, multiplication_proof.rs:32-57): heads-only documents of up to five integers, the rows of w_doc_spec().
+namespace {
+static_assert(sizeof(zkp_sigma_fields) == 5 * sizeof(uint32_t*), "zkp_sigma_fields is five pointers back to back");
+struct SigmaFieldList {
+  uint32_t* f[W_MAX_HEADS] = {};
+  explicit SigmaFieldList(const zkp_sigma_fields* p) { if (p) { f[0] = p->f0; f[1] = p->f1; f[2] = p->f2; f[3] = p->f3; f[4] = p->f4; } }
+};
+bool sigma_json_args_ok(uint32_t doc_kind, uint32_t n_bits, uint64_t B, uint32_t forms) {
+  return w_sigma_kind(doc_kind) && (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && B <= (1ull << 24) && !(forms >> 8) && ((forms >> 4) & 15u) <= ZKP_BIGINT_BYTES &&
+         (forms & 15u) <= ZKP_BIGINT_BYTES;
+}
+}  // namespace
+
+extern "C" int32_t zkp_json_sigma_batch(zkp_ctx* c, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits, uint64_t B,
+                                        uint32_t bigint_forms, const zkp_sigma_fields* out, uint8_t* out_status, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  bool bad = (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !text || !doc_off || !doc_len || !out || !out_status || !sigma_json_args_ok(doc_kind, n_bits, B, bigint_forms);
+  const SigmaFieldList o(out);
+  for (unsigned f = 0; !bad && f < w_heads(doc_kind); f++) bad = !o.f[f];
+  if (bad) { c->err = "zkp_json_sigma_batch: invalid argument"; return ZKP_EINVAL; }
+  const uint32_t kw = n_bits / 32;
+  if (!(flags & ZKP_F_DEVICE_PTRS)) return json_heads_host(text, doc_off, doc_len, B, doc_kind, (bigint_forms >> 4) & 15u, bigint_forms & 15u, kw, 0, o.f, out_status);
+  HIPCHK(c, hipSetDevice(c->device));
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
+  return json_scan_entry(c, "zkp_json_sigma_batch", doc_kind, text, doc_off, doc_len, bigint_forms, d, nullptr, out_status, 0, o.f);
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_json_write_sigma_batch(zkp_ctx* c, uint32_t doc_kind, uint32_t n_bits, uint64_t batch, const zkp_sigma_fields* in, uint32_t bigint_forms, char* out_text,
+                                              uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (!w_sigma_kind(doc_kind) || (batch && !in)) { c->err = "zkp_json_write_sigma_batch: invalid argument"; return ZKP_EINVAL; }
+  const WDocSpec& spec = w_doc_spec(doc_kind);
+  const SigmaFieldList f(in);
+  WHeads hd{};
+  for (uint32_t i = 0; i < spec.n_heads; i++) { hd.a[i] = f.f[i]; hd.words[i] = w_head_words(spec.h[i], n_bits / 32, 0); }
+  return json_write_impl(c, "zkp_json_write_sigma_batch", doc_kind, nullptr, n_bits, batch, 0, nullptr, bigint_forms, out_text, text_cap, out_doc_off, out_status, flags, &hd);
+} ZKP_CATCH(c)
+
+// The four verifies on documents: statement b and proof b are two spans of one text, uploaded once.  Both are read by the device route into arrays the
+// call owns; n^2 is squared on the device and k_sigma_domain_check folds the two statuses and keeps every pair outside the limb kernels' domain (key
+// even or trivial, a 2 kw field >= n^2, MulProof.f >= n) away from them; then the type's zkp_*_verify_batch on the whole batch with one key per pair
+// — it routes itself by its own work measure, on the same stream — and the verdicts of unread pairs masked afterwards.  An unread pair is zero rows
+// under the key 0, which k_setup marks before any arithmetic: nothing is stored for it and the compare kernels answer MALFORMED.
+// The events of zkp_diag_last_json_scan_ms are: upload | statements read | proofs read | domain check and verify.
+extern "C" int32_t zkp_sigma_verify_json_batch(zkp_ctx* c, uint32_t proof_kind, const char* text, const uint64_t* st_off, const uint64_t* st_len, const uint64_t* pf_off,
+                                               const uint64_t* pf_len, uint64_t B, uint32_t n_bits, uint32_t bigint_forms, uint8_t* out_status, uint8_t* out_verdict,
+                                               uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  const bool is_proof = proof_kind == W_DOC_ZERO_PROOF || proof_kind == W_DOC_CT_PROOF || proof_kind == W_DOC_VERLIN_PROOF || proof_kind == W_DOC_MUL_PROOF;
+  if ((flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !is_proof || !text || !st_off || !st_len || !pf_off || !pf_len || !out_status || !out_verdict ||
+      !sigma_json_args_ok(proof_kind, n_bits, B, bigint_forms)) {
+    c->err = "zkp_sigma_verify_json_batch: invalid argument"; return ZKP_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const char* name = "zkp_sigma_verify_json_batch";
+  const uint32_t st_kind = proof_kind - 1;
+  const WDocSpec &ss = w_doc_spec(st_kind), &ps = w_doc_spec(proof_kind);
+  const uint64_t kw = n_bits / 32;
+  Stage s(c, flags);
+  uint8_t* dstat = s.out(out_status, B);
+  uint8_t* dv = s.out(out_verdict, B);
+  // S[i]: field i of the statement (S[0] the key), P[i]: field i of the proof
+  uint32_t *S[W_MAX_HEADS] = {}, *P[W_MAX_HEADS] = {};
+  SigmaDomainArgs dom{};
+  auto own = [&](const WDocSpec& spec, uint32_t** arr) {
+    for (uint32_t i = 0; i < spec.n_heads; i++) {
+      const uint32_t w = w_head_words(spec.h[i], (uint32_t)kw, 0);
+      arr[i] = (uint32_t*)s.take(B * w * 4);
+      dom.arr[dom.n_arr] = arr[i]; dom.words[dom.n_arr] = w;
+      dom.rule[dom.n_arr] = spec.h[i].key ? SIGMA_ANY : spec.h[i].width == W_WID_NN ? SIGMA_LT_NN : spec.h[i].width == W_WID_N ? SIGMA_LT_N : SIGMA_ANY;
+      dom.n_arr++;
+    }
+  };
+  static_assert(2 * W_MAX_HEADS - 2 <= SIGMA_MAX_ARR, "a statement (key and three fields) and a proof of five fields");
+  own(ss, S); own(ps, P);
+  uint32_t* nn = (uint32_t*)s.take(B * 2 * kw * 4);
+  uint8_t* dstat2 = (uint8_t*)s.take(B);
+  int32_t st = s.st;
+  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
+  if (!st) st = scan_event(c, 0);
+  ScanText up{};
+  if (!st) {
+    uint64_t lo = ~0ull, hi = 0;
+    scan_span(st_off, st_len, B, &lo, &hi);
+    scan_span(pf_off, pf_len, B, &lo, &hi);
+    st = scan_upload(c, s, text, lo, hi, &up);
+  }
+  if (!st) st = scan_event(c, 1);
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
+  if (!st) st = json_scan(c, s, name, st_kind, text, st_off, st_len, bigint_forms, d, nullptr, dstat, 0, &up, S);
+  if (!st) st = scan_event(c, 2);
+  if (!st) st = json_scan(c, s, name, proof_kind, text, pf_off, pf_len, bigint_forms, d, nullptr, dstat2, 0, &up, P);
+  if (!st) st = scan_event(c, 3);
+  if (!st) {
+    hipLaunchKernelGGL(k_square_words, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, c->stream, (const uint32_t*)S[0], kw, (int)kw, B, nn);
+    dom.kw = (uint32_t)kw; dom.nn = nn; dom.B = B; dom.proof_status = dstat2; dom.status = dstat;
+    hipLaunchKernelGGL(k_sigma_domain_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, dom);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_sigma_domain_check launch"; }
+  }
+  const uint32_t F = ZKP_F_DEVICE_PTRS;
+  if (!st) {
+    switch (proof_kind) {
+      case W_DOC_ZERO_PROOF: st = zkp_zero_proof_verify_batch(c, n_bits, B, S[0], kw, S[1], P[0], P[1], dv, F); break;
+      case W_DOC_CT_PROOF: st = zkp_ciphertext_proof_verify_batch(c, n_bits, B, S[0], kw, S[1], P[0], P[1], P[2], dv, F); break;
+      case W_DOC_VERLIN_PROOF: st = zkp_verlin_proof_verify_batch(c, n_bits, B, S[0], kw, S[1], S[2], S[3], P[0], P[1], P[2], P[3], P[4], dv, F); break;
+      default: st = zkp_mul_proof_verify_batch(c, n_bits, B, S[0], kw, S[1], S[2], S[3], P[0], P[1], P[2], P[3], P[4], dv, F); break;
+    }
+  }
   if (!st) {
     hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
     if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }

@@ -1046,6 +1046,10 @@ class ZeroProof {
     e.check(zkp_zero_proof_verify_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), zz.data(), aa.data(), &v, 0), "zkp_zero_proof_verify_batch");
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
+  // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
+  // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
+  // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
+  static std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms = 0);
 };
 
 // ------------------------------------------------------------------ CiphertextProof (src/zkproofs/correct_ciphertext.rs:23-98)
@@ -1074,6 +1078,10 @@ class CiphertextProof {
     e.check(zkp_ciphertext_proof_verify_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), a1.data(), a2.data(), ac.data(), &v, 0), "zkp_ciphertext_proof_verify_batch");
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
+  // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
+  // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
+  // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
+  static std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms = 0);
 };
 
 // ------------------------------------------------------------------ VerlinProof (src/zkproofs/verlin_proof.rs:35-165)
@@ -1119,6 +1127,10 @@ class VerlinProof {
                                           vrz.data(), &v, 0), "zkp_verlin_proof_verify_batch");
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
+  // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
+  // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
+  // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
+  static std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms = 0);
 };
 
 // ------------------------------------------------------------------ BigInt::mod_inv (batched on the GPU)
@@ -1179,6 +1191,10 @@ class MulProof {
     if (v == ZKP_VERDICT_MALFORMED) throw Panic("called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:135)");
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
+  // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
+  // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
+  // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
+  static std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms = 0);
 };
 
 // ------------------------------------------------------------------ CorrectMessageProof (src/zkproofs/correct_message.rs)
@@ -1592,6 +1608,111 @@ inline DLogStatement dlog_statement_from_str(const std::string& doc, BigintText 
   return s;
 }
 
+// ZeroProof, CiphertextProof, VerlinProof, MulProof and their statements (zero_enc_proof.rs:26-41, correct_ciphertext.rs:22-39, verlin_proof.rs:34-57,
+// multiplication_proof.rs:32-57): the serde defaults of the derives.  A statement's key is the object "ek" with the field "n" in the key form;
+// every other field is a bare BigInt.  One table per type, in declaration order, serves to_string, from_str, to_string_batch and verify_json_batch.
+namespace detail_json {
+enum class SigmaWidth { N, NN, Z };          // kw | 2 kw | kw + ZKP_Z1_EXTRA_LIMBS words in the batch layout
+struct SigmaField { const char* name; BigInt* v; SigmaWidth w; bool key; };
+template <class T> struct SigmaDoc;
+#define ZKP_SIGMA_DOC(T, KIND, ...)                                                                             \
+  template <> struct SigmaDoc<T> {                                                                              \
+    static constexpr uint32_t kind = KIND;                                                                      \
+    static constexpr const char* type = #T;                                                                     \
+    static std::vector<SigmaField> fields(T& d) { return __VA_ARGS__; }                                         \
+  };
+ZKP_SIGMA_DOC(ZeroStatement, ZKP_JSON_DOC_ZERO_STATEMENT, {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(ZeroProof, ZKP_JSON_DOC_ZERO_PROOF, {{"z", &d.z, SigmaWidth::NN, false}, {"a", &d.a, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(CiphertextStatement, ZKP_JSON_DOC_CIPHERTEXT_STATEMENT, {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(CiphertextProof, ZKP_JSON_DOC_CIPHERTEXT_PROOF,
+              {{"z1", &d.z1, SigmaWidth::Z, false}, {"z2", &d.z2, SigmaWidth::NN, false}, {"c_prime", &d.c_prime, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(VerlinStatement, ZKP_JSON_DOC_VERLIN_STATEMENT,
+              {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}, {"c_prime", &d.c_prime, SigmaWidth::NN, false}, {"phi_x", &d.phi_x, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(VerlinProof, ZKP_JSON_DOC_VERLIN_PROOF,
+              {{"phi_a", &d.phi_a, SigmaWidth::NN, false}, {"z", &d.z, SigmaWidth::Z, false}, {"z_prime", &d.z_prime, SigmaWidth::Z, false},
+               {"z_double_prime", &d.z_double_prime, SigmaWidth::Z, false}, {"r_z", &d.r_z, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(MulStatement, ZKP_JSON_DOC_MUL_STATEMENT,
+              {{"ek", &d.ek.n, SigmaWidth::N, true}, {"e_a", &d.e_a, SigmaWidth::NN, false}, {"e_b", &d.e_b, SigmaWidth::NN, false}, {"e_c", &d.e_c, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(MulProof, ZKP_JSON_DOC_MUL_PROOF,
+              {{"f", &d.f, SigmaWidth::N, false}, {"z1", &d.z1, SigmaWidth::NN, false}, {"z2", &d.z2, SigmaWidth::NN, false}, {"e_d", &d.e_d, SigmaWidth::NN, false},
+               {"e_db", &d.e_db, SigmaWidth::NN, false}})
+#undef ZKP_SIGMA_DOC
+// MinimalEncryptionKey -> EncryptionKey { n, nn = n * n } for the types that carry a key [upstream kzen-paillier]
+template <class T> auto set_nn(T& d, int) -> decltype(d.ek.nn, void()) { d.ek.nn = d.ek.n * d.ek.n; }
+template <class T> void set_nn(T&, long) {}
+inline size_t sigma_words(SigmaWidth w, uint32_t kw) { return w == SigmaWidth::N ? kw : w == SigmaWidth::NN ? 2 * kw : kw + ZKP_Z1_EXTRA_LIMBS; }
+}  // namespace detail_json
+
+template <class T, class D = detail_json::SigmaDoc<T>> std::string to_string(const T& doc, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
+  std::string s = "{";
+  bool after_key = false;
+  for (const detail_json::SigmaField& f : D::fields(const_cast<T&>(doc))) {
+    if (s.size() > 1) s += after_key ? "}," : ",";
+    s += std::string("\"") + f.name + "\":" + (f.key ? "{\"n\":" : "") + bigint_text(*f.v, f.key ? key_form : bare_form);
+    after_key = f.key;
+  }
+  return s + (after_key ? "}}" : "}");
+}
+// serde_json::from_str::<T>: throws (std::runtime_error) where serde reports an error
+template <class T, class D = detail_json::SigmaDoc<T>> T sigma_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
+  T out;
+  const std::vector<detail_json::SigmaField> fields = D::fields(out);
+  detail_json::Cur j{doc};
+  unsigned seen = 0;
+  j.object([&](const std::string& nm) {
+    for (size_t f = 0; f < fields.size(); f++) {
+      if (nm != fields[f].name) continue;
+      if (seen & (1u << f)) j.fail("duplicate field");
+      seen |= 1u << f;
+      if (!fields[f].key) { *fields[f].v = j.bigint(bare_form); return true; }
+      bool has_n = false;
+      j.object([&](const std::string& k) { if (k != "n") return false; if (has_n) j.fail("duplicate field"); has_n = true; *fields[f].v = j.bigint(key_form); return true; });
+      if (!has_n) j.fail("missing field `n`");
+      return true;
+    }
+    return false;
+  });
+  if (seen != (1u << fields.size()) - 1) j.fail((std::string("missing field of ") + D::type).c_str());
+  j.ws();
+  if (j.p != doc.size()) j.fail("trailing characters");
+  detail_json::set_nn(out, 0);
+  return out;
+}
+// whole batches through zkp_json_write_sigma_batch: one key width per batch — the smallest in which every value fits its array
+template <class T, class D = detail_json::SigmaDoc<T>>
+std::vector<std::string> to_string_batch(const std::vector<T>& v, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
+  const size_t B = v.size();
+  if (B == 0) return {};
+  std::vector<std::vector<detail_json::SigmaField>> rows;
+  for (const T& d : v) rows.push_back(D::fields(const_cast<T&>(d)));
+  uint32_t nb = 0;
+  for (uint32_t cand : {1024u, 2048u, 4096u}) {
+    bool fits = true;
+    for (auto& r : rows) for (auto& f : r) fits = fits && !f.v->is_negative() && f.v->bit_length() <= 32 * detail_json::sigma_words(f.w, cand / 32);
+    if (fits) { nb = cand; break; }
+  }
+  if (!nb) throw std::invalid_argument(std::string("to_string_batch: a ") + D::type + " with a negative value or one wider than the 4096-bit layout");
+  const size_t nf = rows[0].size();
+  std::vector<std::vector<uint32_t>> arr(nf);
+  uint32_t* ptrs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (size_t f = 0; f < nf; f++) {
+    const size_t w = detail_json::sigma_words(rows[0][f].w, nb / 32);
+    arr[f].resize(B * w);
+    for (size_t b = 0; b < B; b++) rows[b][f].v->to_limbs(&arr[f][b * w], w);
+    ptrs[f] = arr[f].data();
+  }
+  const zkp_sigma_fields in{ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4]};
+  const uint32_t forms = ZKP_BIGINT_FORMS((uint32_t)key_form, (uint32_t)bare_form);
+  Engine& e = Engine::instance();
+  std::vector<uint64_t> off(B + 1);
+  e.check(zkp_json_write_sigma_batch(e.ctx(), D::kind, nb, B, &in, forms, nullptr, 0, off.data(), nullptr, 0), "zkp_json_write_sigma_batch");
+  std::string text(off[B], '\0');
+  e.check(zkp_json_write_sigma_batch(e.ctx(), D::kind, nb, B, &in, forms, &text[0], text.size(), off.data(), nullptr, 0), "zkp_json_write_sigma_batch");
+  std::vector<std::string> out(B);
+  for (size_t b = 0; b < B; b++) out[b] = text.substr(off[b], off[b + 1] - off[b]);
+  return out;
+}
+
 inline RangeProofNi range_proof_ni_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
   detail_json::Cur j{doc};
   RangeProofNi out;
@@ -1772,6 +1893,82 @@ inline std::vector<Result> NiCorrectKeyProof::verify_json_batch(const std::vecto
     out[k] = verify_batch({{items[k].first, &q}}, salt, salt_len)[0];
   }
   return out;
+}
+
+// The four sigma proofs on documents.  Why a pair the GPU handed back (ZKP_DOC_HOST_PATH) is unsupported: the host mirror has no evaluator for
+// these types outside the limb kernels' domain — a negative or over-wide value, an even or trivial key, a residue not reduced mod n^2 (f: mod n).
+namespace detail_json_sigma {
+template <class Proof, class Statement>
+std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms) {
+  using PD = serde_json::detail_json::SigmaDoc<Proof>;
+  using SD = serde_json::detail_json::SigmaDoc<Statement>;
+  using serde_json::detail_json::SigmaWidth;
+  const std::string name = std::string(PD::type) + "::verify_json_batch";
+  const size_t B = statements.size();
+  if (proofs.size() != B) throw std::invalid_argument(name + ": one proof per statement");
+  const uint32_t kf = (forms >> 4) & 15u, bf = forms & 15u;
+  if ((forms >> 8) || kf > ZKP_BIGINT_BYTES || bf > ZKP_BIGINT_BYTES) throw std::invalid_argument(name + ": unknown text form");
+  const auto key_form = (serde_json::BigintText)kf, bare_form = (serde_json::BigintText)bf;
+  auto carried = [](const BigInt& n) { return !n.is_negative() && n.is_odd() && n.bit_length() >= 2 && n.bit_length() <= 4096; };
+  std::vector<Result> out(B, Result(false));
+  std::vector<uint8_t> status(B, ZKP_DOC_HOST_PATH), verdict(B, ZKP_VERDICT_REJECT);
+  // one key width per call: that of the first statement that parses and has a key the engine carries
+  uint32_t nb = 0;
+  for (size_t b = 0; b < B && nb == 0; b++) {
+    try { const Statement s = serde_json::sigma_from_str<Statement>(statements[b], key_form, bare_form); if (carried(s.ek.n)) nb = width_for(s.ek.n); } catch (const std::exception&) {}
+  }
+  if (nb) {
+    std::string text;
+    std::vector<uint64_t> so(B), sl(B), po(B), pl(B);
+    for (size_t b = 0; b < B; b++) { so[b] = text.size(); sl[b] = statements[b].size(); text += statements[b]; }
+    for (size_t b = 0; b < B; b++) { po[b] = text.size(); pl[b] = proofs[b].size(); text += proofs[b]; }
+    Engine& e = Engine::instance();
+    if (zkp_sigma_verify_json_batch(e.ctx(), PD::kind, text.data(), so.data(), sl.data(), po.data(), pl.data(), B, nb, forms, status.data(), verdict.data(), 0) != ZKP_OK)
+      throw std::runtime_error(std::string("zkp_sigma_verify_json_batch: ") + zkp_last_error_string(e.ctx()));
+  }
+  for (size_t b = 0; b < B; b++) {
+    if (status[b] == ZKP_DOC_OK) {
+      out[b] = verdict[b] == ZKP_VERDICT_MALFORMED ? Result::panicked("called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:135)")
+                                                   : Result(verdict[b] == ZKP_VERDICT_ACCEPT);
+      continue;
+    }
+    Statement s; Proof p;
+    try { s = serde_json::sigma_from_str<Statement>(statements[b], key_form, bare_form); p = serde_json::sigma_from_str<Proof>(proofs[b], key_form, bare_form); }
+    catch (const std::exception& err) { out[b] = Result::panicked(std::string("called `Result::unwrap()` on an `Err` value: ") + err.what()); continue; }
+    std::string why;
+    if (!carried(s.ek.n)) why = "the key is not a positive odd integer of 2 to 4096 bits";
+    else {
+      const BigInt nn = s.ek.n * s.ek.n;
+      const uint32_t kw = width_for(s.ek.n) / 32;
+      auto look = [&](const std::vector<serde_json::detail_json::SigmaField>& fields) {
+        for (const auto& f : fields) {
+          if (f.key || !why.empty()) continue;
+          if (f.v->is_negative()) why = std::string(f.name) + " is negative";
+          else if (f.w == SigmaWidth::Z && f.v->bit_length() > 32 * serde_json::detail_json::sigma_words(f.w, kw)) why = std::string(f.name) + " is wider than n by more than 512 bits";
+          else if (f.w == SigmaWidth::NN && !(*f.v < nn)) why = std::string(f.name) + " is not below n^2";
+          else if (f.w == SigmaWidth::N && !(*f.v < s.ek.n)) why = std::string(f.name) + " is not below n";
+        }
+      };
+      look(SD::fields(s)); look(PD::fields(p));
+    }
+    if (!why.empty()) { out[b] = Result::unsupported(std::string(PD::type) + "::verify: " + why + ": outside the domain of the GPU kernels, and the host mirror has no evaluator for it"); continue; }
+    // inside the domain under a key of another width than the batch's: the single-proof path
+    try { out[b] = p.verify(s); } catch (const Panic& panic) { out[b] = Result::panicked(panic.what()); }
+  }
+  return out;
+}
+}  // namespace detail_json_sigma
+inline std::vector<Result> ZeroProof::verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms) {
+  return detail_json_sigma::verify_json_batch<ZeroProof, ZeroStatement>(statements, proofs, forms);
+}
+inline std::vector<Result> CiphertextProof::verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms) {
+  return detail_json_sigma::verify_json_batch<CiphertextProof, CiphertextStatement>(statements, proofs, forms);
+}
+inline std::vector<Result> VerlinProof::verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms) {
+  return detail_json_sigma::verify_json_batch<VerlinProof, VerlinStatement>(statements, proofs, forms);
+}
+inline std::vector<Result> MulProof::verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms) {
+  return detail_json_sigma::verify_json_batch<MulProof, MulStatement>(statements, proofs, forms);
 }
 
 }  // namespace zkproofs
