@@ -343,6 +343,71 @@ int32_t zkp_correct_message_verify_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t
                                          uint64_t n_stride, const uint32_t* valid_messages, const uint32_t* ciphertext, const uint32_t* e_vec,
                                          const uint32_t* z_vec, const uint32_t* a_vec, uint8_t* out_verdict, uint32_t flags);
 
+/* ------------------------------------------------------------------ seeded proving: ZeroProof, CiphertextProof, CorrectMessageProof, CompositeDLogProof
+ * The four proves above take the nonces the reference draws itself (zero_enc_proof.rs:45, correct_ciphertext.rs:43-44,
+ * correct_message.rs:42, 59-66, wi_dlog_proof.rs:53-54) as inputs.  The calls below take what the reference's prove takes: a 32-byte seed is
+ * expanded ON THE DEVICE into those nonces, by the construction of the RangeProofNi stream above on streams of its own (DESIGN.md section 4
+ * has the definition, tests/seeded_nonce_model.py restates it):
+ *   ChaCha20 block function of RFC 8439 (20 rounds, 32-bit block counter in state word 12); key = seed as 8 little-endian words;
+ *   state words 13, 14 = (index & 0xffffffff, index >> 32), index = first_index + b for proof b of the call;
+ *   state word 15 = 0x80000000 | kind << 20 | slot << 4 | field, slot < 65536, field < 16.  Bit 31 separates these streams from every
+ *   RangeProofNi stream, whose word 15 is row << 2 | field < 1024.
+ *   sample_below(n) is the rule of the range sampler, word for word: bits = bit_length(n), nw = ceil(bits / 32), nb = ceil(nw / 16);
+ *   attempt t takes the first nw keystream words of blocks [t nb, (t + 1) nb) as limbs 0 .. nw - 1, clears the bits of the top limb above
+ *   `bits`, and is accepted when the value is < n; at most 128 attempts.
+ *     kind                 slot                   field  value      draw
+ *     1 Zero               0                      0      r_prime    sample_below(n)
+ *     2 Ciphertext         0                      0      x_prime    sample_below(n)
+ *     2 Ciphertext         0                      1      r_prime    sample_below(n)
+ *     3 CorrectMessage     0                      0      r          sample_below(n)
+ *     3 CorrectMessage     0                      1      w          sample_below(n)
+ *     3 CorrectMessage     j + 1, j < K - 1       2      e_sim[j]   words 0 .. 7 of block 0, no rejection (BigInt::sample(256))
+ *     3 CorrectMessage     j + 1, j < K - 1       3      z_sim[j]   sample_below(n)
+ *     4 DLog               0                      0      r          words 0 .. 15 of block 0: uniform on [0, 2^512), as sample_below(2^512) is
+ * OUR rule for n == 0 and for 128 rejected attempts in a row is the range sampler's: all of that proof's nonces are zero and its status
+ * is ZKP_VERDICT_MALFORMED; its outputs are what the nonce-input call writes for zero nonces; the other proofs of the batch are unaffected.
+ * VerlinProof and MulProof have no seeded prove: they redraw a nonce until it is coprime to n (verlin_proof.rs:64-67,
+ * multiplication_proof.rs:148-154), which is a GCD loop and not a plain draw.
+ *
+ * SECURITY CONTRACT.  The seed is worth every nonce of the call: whoever learns it learns the witness from any response (r from
+ * z = r' r^e, x from z1 = x' + x e, the DLog secret from y = r + e s).  A (seed, index) pair must never be used for two different
+ * statements: two responses over one r_prime under two challenges give away r.  Callers draw a fresh seed per call from the operating
+ * system and wipe it afterwards.  `seed` is always a HOST pointer, also under ZKP_F_DEVICE_PTRS.  A caller who splits a batch passes
+ * first_index + lo for the part that starts at proof lo: split calls equal one call. */
+#define ZKP_SEEDED_KIND_ZERO 1u
+#define ZKP_SEEDED_KIND_CIPHERTEXT 2u
+#define ZKP_SEEDED_KIND_CORRECT_MESSAGE 3u
+#define ZKP_SEEDED_KIND_DLOG 4u
+
+/* The nonces of proofs first_index .. first_index + batch - 1 of one kind, by field id: out_field is an array of four pointers (read, not
+ * written), out_field[f] is null where the kind has no field f
+ * (and may be null where it has no slots: e_sim, z_sim at num_messages == 1).  Shapes: [B][kw] for the slot-0 fields, [B][K-1][8] for
+ * e_sim, [B][K-1][kw] for z_sim, [B][16] for the DLog r.  num_messages = K is read for CorrectMessage only (1 <= K <= 65536); n and n_stride
+ * are not read for DLog.  out_status [B], nullable.  Device-pointer calls: the output arrays are 16-byte aligned. */
+int32_t zkp_nonce_sample_batch(zkp_ctx* ctx, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, uint32_t num_messages, const uint32_t* n,
+                               uint64_t n_stride, const uint8_t* seed, uint64_t first_index, uint32_t** out_field /* [4], by field id */,
+                               uint8_t* out_status, uint32_t flags);
+
+/* The nonce-input proves with their nonce pointers replaced by (seed, first_index): the nonces are sampled into blocks of the context,
+ * the nonce-input call runs on them unchanged, and they are zeroed on the device — as are the seed and the staged copies of r / x / message /
+ * secret of a host-pointer call — before the call's blocks are given back, on error returns too.  out_status [B], nullable for Zero,
+ * Ciphertext and DLog: the sampler's status (for CorrectMessage: the prove's status with the sampler's OR-ed in).  A seeded CorrectMessage
+ * call accepts the num_messages zkp_correct_message_prove_batch accepts; beyond 65536 the stream itself has no slots. */
+int32_t zkp_zero_proof_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                          const uint32_t* c, const uint32_t* r, const uint8_t* seed, uint64_t first_index, uint32_t* out_z,
+                                          uint32_t* out_a, uint8_t* out_status, uint32_t flags);
+int32_t zkp_ciphertext_proof_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                                const uint32_t* c, const uint32_t* x, const uint32_t* r, const uint8_t* seed,
+                                                uint64_t first_index, uint32_t* out_z1, uint32_t* out_z2, uint32_t* out_c_prime,
+                                                uint8_t* out_status, uint32_t flags);
+int32_t zkp_correct_message_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, uint32_t num_messages, const uint32_t* n,
+                                               uint64_t n_stride, const uint32_t* valid_messages, const uint32_t* message, const uint8_t* seed,
+                                               uint64_t first_index, uint32_t* out_ciphertext, uint32_t* out_e_vec, uint32_t* out_z_vec,
+                                               uint32_t* out_a_vec, uint8_t* out_status, uint32_t flags);
+int32_t zkp_dlog_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* N, const uint32_t* g,
+                                    const uint32_t* ni, const uint32_t* secret, const uint8_t* seed, uint64_t first_index, uint32_t* out_x,
+                                    uint32_t* out_y, uint8_t* out_status, uint32_t flags);
+
 /* ------------------------------------------------------------------ wire format
  * The reference serialises big integers as DECIMAL strings (src/serialize.rs:1-31 `bigint`, :33-78 `vecbigint`:
  * BigInt::to_str_radix(10) / from_str_radix(s, 10) = GMP mpz_get_str / mpz_set_str).  The two L1 entry points below

@@ -150,6 +150,16 @@ EXPORTS = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_ciphertext_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_nonce_sample_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64,
+                                           C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32]),
+    "zkp_zero_proof_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_ciphertext_proof_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_correct_message_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                           C.c_char_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint32]),
+    "zkp_dlog_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
+                                                C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_verlin_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_verlin_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
     "zkp_multi_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -173,6 +183,7 @@ EXPORTS = {
 }
 
 Z1_EXTRA_LIMBS = 16
+SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KIND_DLOG = 1, 2, 3, 4
 _lib = None
 
 
@@ -548,6 +559,32 @@ class Context:
     def ciphertext_proof_verify(self, n_bits, batch, n, n_stride, c, z1, z2, c_prime, out_verdict):
         self.check(self.lib.zkp_ciphertext_proof_verify_batch(self.h, n_bits, batch, ptr(n), n_stride, ptr(c), ptr(z1), ptr(z2), ptr(c_prime),
                                                               ptr(out_verdict), self._flags(n, c, z1, z2, c_prime, out_verdict)))
+
+    # ---- seeded proving of the sigma proofs and CompositeDLogProof: the nonces are expanded from a 32-byte seed (always host bytes) on the GPU
+    def nonce_sample(self, kind, n_bits, batch, K, n, n_stride, seed: bytes, first_index: int, out_fields, out_status):
+        """zkp_nonce_sample_batch: out_fields = the four arrays by field id (None where the kind has none)"""
+        arr = (C.c_void_p * 4)(*[ptr(a) for a in out_fields])
+        self.check(self.lib.zkp_nonce_sample_batch(self.h, kind, n_bits, batch, K, ptr(n), n_stride, _seed(seed), first_index, arr, ptr(out_status),
+                                                   self._flags(n, *out_fields, out_status)))
+
+    def zero_proof_prove_seeded(self, n_bits, batch, n, n_stride, c, r, seed: bytes, first_index: int, out_z, out_a, out_status=None):
+        self.check(self.lib.zkp_zero_proof_prove_seeded_batch(self.h, n_bits, batch, ptr(n), n_stride, ptr(c), ptr(r), _seed(seed), first_index, ptr(out_z),
+                                                              ptr(out_a), ptr(out_status), self._flags(n, c, r, out_z, out_a, out_status)))
+
+    def ciphertext_proof_prove_seeded(self, n_bits, batch, n, n_stride, c, x, r, seed: bytes, first_index: int, out_z1, out_z2, out_c_prime, out_status=None):
+        self.check(self.lib.zkp_ciphertext_proof_prove_seeded_batch(self.h, n_bits, batch, ptr(n), n_stride, ptr(c), ptr(x), ptr(r), _seed(seed), first_index,
+                                                                    ptr(out_z1), ptr(out_z2), ptr(out_c_prime), ptr(out_status),
+                                                                    self._flags(n, c, x, r, out_z1, out_z2, out_c_prime, out_status)))
+
+    def correct_message_prove_seeded(self, n_bits, batch, K, n, n_stride, valid, message, seed: bytes, first_index: int, out_ct, out_e_vec, out_z_vec,
+                                     out_a_vec, out_status):
+        arrs = (valid, message, out_ct, out_e_vec, out_z_vec, out_a_vec, out_status)
+        self.check(self.lib.zkp_correct_message_prove_seeded_batch(self.h, n_bits, batch, K, ptr(n), n_stride, ptr(valid), ptr(message), _seed(seed), first_index,
+                                                                   *[ptr(x) for x in arrs[2:]], self._flags(n, *arrs)))
+
+    def dlog_prove_seeded(self, n_bits, y_bits, batch, N, g, ni, secret, seed: bytes, first_index: int, out_x, out_y, out_status=None):
+        self.check(self.lib.zkp_dlog_prove_seeded_batch(self.h, n_bits, y_bits, batch, ptr(N), ptr(g), ptr(ni), ptr(secret), _seed(seed), first_index,
+                                                        ptr(out_x), ptr(out_y), ptr(out_status), self._flags(N, g, ni, secret, out_x, out_y, out_status)))
 
     def verlin_proof_prove(self, n_bits, batch, n, n_stride, c, c_prime, phi_x, witness, nonces, outs):
         """witness = (x, x', x'', r_x); nonces = (a, a', a'', r_a); outs = (phi_a, z, z', z'', r_z)"""

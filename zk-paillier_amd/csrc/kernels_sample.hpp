@@ -1,5 +1,6 @@
 // kernels_sample.hpp — the witness of RangeProofNi::prove expanded on the device from a 32-byte seed (include/zkp_hip.h:
-// zkp_range_sample_witness_batch; the stream is defined in DESIGN.md section 4 and restated by tests/seeded_model.py).
+// zkp_range_sample_witness_batch; the stream is defined in DESIGN.md section 4 and restated by tests/seeded_model.py), and below it the
+// nonces of the sigma proofs and of CompositeDLogProof (zkp_nonce_sample_batch, tests/seeded_nonce_model.py).
 //
 // Per row the reference draws w1, w2, a coin, r1 and r2 (range_proof.rs:133-159).  Here every (proof, row, field) has a ChaCha20
 // stream of its own — key = the seed, nonce = (index lo, index hi, row << 2 | field) — and sample_below(u) reads WHOLE blocks per
@@ -144,6 +145,136 @@ __global__ void __launch_bounds__(256) k_range_sample_fixup(RangeSampleArgs a) {
   uint32_t* const arrays[4] = {a.w1, a.w2, a.r1, a.r2};
   for (int k = 0; k < 4; k++)
     for (int i = 0; i < 4; i++) ((uint4*)(arrays[k] + off))[i] = z;
+}
+
+// ---- the nonces of ZeroProof, CiphertextProof, CorrectMessageProof and CompositeDLogProof (include/zkp_hip.h: zkp_nonce_sample_batch) ----
+// The same construction on streams of their own: state word 15 = 0x80000000 | kind << 20 | slot << 4 | field (bit 31 keeps them apart from
+// every range stream, whose word 15 is below 1024).  A proof has up to three sample_below(n) fields — slot 0, or slots 1 .. K - 1 of a
+// CorrectMessageProof — and at most one field that is the first 8 or 16 words of block 0 as they come (e_sim, the DLog r).
+struct NonceSampleArgs {
+  const uint32_t* key;        // the seed as 8 little-endian words (device memory)
+  const uint32_t* n; uint64_t n_stride;      // (null for a kind without sample_below fields)
+  uint32_t* meta;             // [B] bit_length(n)                 (written by k_nonce_prep)
+  uint32_t* below[3];         // the sample_below fields: [B][below_per][kw], 16-byte aligned
+  uint32_t* raw;              // the power-of-two field: [B][raw_per][raw_words], 16-byte aligned
+  uint8_t* status;            // [B] 0 | ZKP_VERDICT_MALFORMED
+  uint64_t first_index, batch;
+  uint32_t kw, kind, max_attempts;
+  uint32_t nbelow, below_field[3], below_per[3], below_slot0[3];
+  uint32_t raw_field, raw_per, raw_slot0, raw_words;      // raw_words = 0: the kind has no such field
+};
+
+__device__ __forceinline__ uint32_t nonce_word15(uint32_t kind, uint32_t slot, uint32_t field) { return 0x80000000u | (kind << 20) | (slot << 4) | field; }
+
+// one thread per proof: the bit length of n, status = MALFORMED for n == 0
+__global__ void __launch_bounds__(256) k_nonce_prep(NonceSampleArgs a) {
+  const uint64_t b = blockIdx.x * 256ull + threadIdx.x;
+  if (b >= a.batch) return;
+  uint32_t nbits = 1;
+  if (a.n) {
+    const uint32_t* n = a.n + b * a.n_stride;
+    nbits = 0;
+    for (int i = (int)a.kw - 1; i >= 0 && !nbits; i--) {
+      const uint32_t nv = n[i];
+      if (nv) nbits = 32u * (uint32_t)i + 32u - (uint32_t)__clz((int)nv);
+    }
+  }
+  a.meta[b] = nbits;
+  a.status[b] = nbits == 0 ? 2 : 0;
+}
+
+// G lanes per (proof, slot, sample_below field), numbered field-major; the attempt loop is k_range_sample's
+template <int G>
+__global__ void __launch_bounds__(256) k_nonce_sample(NonceSampleArgs a) {
+  static_assert(G == 2 || G == 4 || G == 8, "kw = 32, 64 or 128 words");
+  constexpr uint64_t GM = (1ull << G) - 1;
+  const uint64_t gid = blockIdx.x * 256ull + threadIdx.x;
+  uint64_t task = gid / G;
+  const uint32_t l = (uint32_t)(gid % G);
+  uint32_t field = 0, per = 1, slot0 = 0;
+  uint32_t* out = nullptr;
+  bool found = false;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    if (!found && (uint32_t)k < a.nbelow) {
+      const uint64_t count = a.batch * a.below_per[k];
+      if (task < count) { found = true; field = a.below_field[k]; per = a.below_per[k]; slot0 = a.below_slot0[k]; out = a.below[k]; }
+      else task -= count;
+    }
+  }
+  if (!found) return;                                            // (whole groups leave together: 256 and 64 are multiples of G)
+  const uint64_t b = task / per;
+  const uint32_t slot = slot0 + (uint32_t)(task - b * per);
+  const uint32_t bits = a.meta[b];
+  if (bits == 0) return;                                         // n == 0: k_nonce_fixup zeroes the proof's nonces
+  const uint32_t g0 = (threadIdx.x & 63u) - l;                   // the group's first bit in a ballot
+  const uint32_t nw = (bits + 31) / 32, nb = (nw + 15) / 16;
+  const uint32_t topmask = (bits & 31u) ? (1u << (bits & 31u)) - 1u : 0xffffffffu;
+  const uint32_t* u = a.n + b * a.n_stride;
+  uint32_t uw[16], key[8], v[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) { const uint32_t wi = 16 * l + i; uw[i] = wi < nw ? u[wi] : 0u; v[i] = 0u; }
+#pragma unroll
+  for (int i = 0; i < 8; i++) key[i] = a.key[i];
+  const uint64_t index = a.first_index + b;
+  const uint32_t n0 = (uint32_t)index, n1 = (uint32_t)(index >> 32), n2 = nonce_word15(a.kind, slot, field);
+
+  bool active = true, ok = false;
+  for (uint32_t t = 0; t < a.max_attempts; t++) {
+    int c = 0;
+    if (active) {
+      if (l < nb) {
+        chacha20_block(key, t * nb + l, n0, n1, n2, v);
+#pragma unroll
+        for (int i = 0; i < 16; i++) { const uint32_t wi = 16 * l + i; if (wi >= nw) v[i] = 0u; else if (wi == nw - 1) v[i] &= topmask; }
+      }
+#pragma unroll
+      for (int i = 15; i >= 0; i--) if (c == 0 && v[i] != uw[i]) c = v[i] < uw[i] ? -1 : 1;
+    }
+    const uint64_t ne = __ballot(active && c != 0), lt = __ballot(active && c < 0);
+    if (active) {
+      const uint32_t m = (uint32_t)((ne >> g0) & GM);
+      if (m) ok = ((lt >> (g0 + (31u - (uint32_t)__clz((int)m)))) & 1ull) != 0;      // the most significant lane that differs decides
+      if (ok) active = false;
+    }
+    if (__ballot(active) == 0) break;
+  }
+  if (!ok) {                     // max_attempts rejections in a row: every nonce of the proof is zeroed by k_nonce_fixup
+    if (l == 0) a.status[b] = 2;
+    return;
+  }
+  uint4* o = (uint4*)(out + task * a.kw + 16 * l);
+#pragma unroll
+  for (int i = 0; i < 4; i++) o[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+}
+
+// one lane per (proof, slot) of the power-of-two field: words [0, raw_words) of block 0, no comparison
+__global__ void __launch_bounds__(256) k_nonce_raw(NonceSampleArgs a) {
+  const uint64_t task = blockIdx.x * 256ull + threadIdx.x;
+  if (task >= a.batch * a.raw_per) return;
+  const uint64_t b = task / a.raw_per;
+  const uint32_t slot = a.raw_slot0 + (uint32_t)(task - b * a.raw_per);
+  uint32_t key[8], v[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) key[i] = a.key[i];
+  const uint64_t index = a.first_index + b;
+  chacha20_block(key, 0u, (uint32_t)index, (uint32_t)(index >> 32), nonce_word15(a.kind, slot, a.raw_field), v);
+  uint4* o = (uint4*)(a.raw + task * a.raw_words);
+#pragma unroll
+  for (int i = 0; i < 4; i++) if (4u * (uint32_t)i < a.raw_words) o[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+}
+
+// four words per thread: every nonce of a MALFORMED proof becomes zero
+__global__ void __launch_bounds__(256) k_nonce_fixup(NonceSampleArgs a) {
+  const uint64_t gid = blockIdx.x * 256ull + threadIdx.x;
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    uint32_t* out = k < 3 ? a.below[k] : a.raw;
+    const bool present = k < 3 ? (uint32_t)k < a.nbelow : a.raw_words != 0;
+    const uint64_t quads = k < 3 ? (uint64_t)a.below_per[k] * a.kw / 4 : (uint64_t)a.raw_per * a.raw_words / 4;      // per proof
+    if (present && quads && gid < a.batch * quads && a.status[gid / quads]) ((uint4*)out)[gid] = z;
+  }
 }
 
 // non-zero words of a device region (zkp_diag_witness_residue)

@@ -1497,6 +1497,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 
 #include "zkp_api_proofs.inc"
 #include "zkp_api_mul.inc"
+#include "zkp_api_seeded.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE
 #include "zkp_api_multi.inc"

@@ -957,6 +957,36 @@ struct CorrectKey {
   static Result verify(const CorrectKeyProof& proof, const VerificationAid& va) { return Result(proof.s_digest == va.s_digest); }
 };
 
+// ------------------------------------------------------------------ seeded proving of the sigma proofs (zkp_*_prove_seeded_batch)
+// What the prove_batch_seeded functions below share: one fresh 32-byte seed from the operating system per call (RangeProofNi::SeedGuard wipes
+// it on every path out), expanded into the proofs' nonces ON THE GPU — the stream is defined in include/zkp_hip.h.  No nonce is sampled,
+// flattened or kept on the host; the buffers that carry the caller's secrets to the GPU are wiped when they are released.
+namespace detail {
+// the keys of a batch as one array: [1][kw] with stride 0 when every statement names the same n, else [B][kw]; every key takes one kernel width
+struct BatchKeys {
+  uint32_t nb = 0, kw = 0;
+  uint64_t stride = 0;
+  std::vector<uint32_t> n;
+  template <class It, class GetN> BatchKeys(It first, It last, GetN get) {
+    bool shared = true;
+    for (It it = first; it != last; ++it) {
+      const uint32_t w = width_for(get(*it));
+      if (nb && w != nb) throw std::invalid_argument("prove_batch_seeded: the keys of one batch must share a kernel width");
+      nb = w;
+      shared = shared && get(*it) == get(*first);
+    }
+    kw = nb / 32;
+    const size_t rows = shared ? 1 : (size_t)(last - first);
+    stride = shared ? 0 : kw;
+    n.resize(rows * kw);
+    for (size_t i = 0; i < rows; i++) get(first[i]).to_limbs(&n[i * kw], kw);
+  }
+};
+inline void seeded_status_ok(const std::vector<uint8_t>& status, const char* what) {
+  for (uint8_t s : status) if (s != 0) throw Panic(what);
+}
+}  // namespace detail
+
 // ------------------------------------------------------------------ CompositeDLogProof
 struct DLogStatement { BigInt N, g, ni; };   // wi_dlog_proof.rs:38-43
 
@@ -973,6 +1003,26 @@ class CompositeDLogProof {
     st.N.to_limbs(N.data(), kw); st.g.to_limbs(g.data(), kw); st.ni.to_limbs(ni.data(), kw); secret.to_limbs(s.data(), 8); r.to_limbs(rr.data(), 16);
     e.check(zkp_dlog_prove_batch(e.ctx(), nb, Y_BITS, 1, N.data(), g.data(), ni.data(), s.data(), rr.data(), x.data(), y.data(), 0), "zkp_dlog_prove_batch");
     return CompositeDLogProof{BigInt::from_limbs(x.data(), kw), BigInt::from_limbs(y.data(), Y_BITS / 32)};
+  }
+  // prove for a whole batch from what the reference's prove takes: the 512-bit nonces come from one OS seed, expanded on the GPU
+  static std::vector<CompositeDLogProof> prove_batch_seeded(const std::vector<DLogStatement>& st, const std::vector<BigInt>& secrets) {
+    if (st.size() != secrets.size()) throw std::invalid_argument("CompositeDLogProof::prove_batch_seeded: one secret per statement");
+    const size_t B = st.size();
+    if (B == 0) return {};
+    Engine& e = Engine::instance();
+    RangeProofNi::SeedGuard seed(true);
+    const detail::BatchKeys keys(st.begin(), st.end(), [](const DLogStatement& q) -> const BigInt& { return q.N; });
+    const uint32_t nb = keys.nb, kw = keys.kw, yw = Y_BITS / 32;
+    std::vector<uint32_t> N(B * kw), g(B * kw), ni(B * kw), x(B * kw), y(B * yw);
+    RawBuf<uint32_t> s(B * 8, true);
+    for (size_t b = 0; b < B; b++) {
+      st[b].N.to_limbs(&N[b * kw], kw); st[b].g.to_limbs(&g[b * kw], kw); st[b].ni.to_limbs(&ni[b * kw], kw); secrets[b].to_limbs(s.data() + b * 8, 8);
+    }
+    e.check(zkp_dlog_prove_seeded_batch(e.ctx(), nb, Y_BITS, B, N.data(), g.data(), ni.data(), s.data(), seed.bytes, 0, x.data(), y.data(), nullptr, 0),
+            "zkp_dlog_prove_seeded_batch");
+    std::vector<CompositeDLogProof> out;
+    for (size_t b = 0; b < B; b++) out.push_back(CompositeDLogProof{BigInt::from_limbs(&x[b * kw], kw), BigInt::from_limbs(&y[b * yw], yw)});
+    return out;
   }
   // base^exp mod N for a non-negative exponent of ANY length (a prover-chosen y is not bounded): exponents wider than the modulus
   // width go through the GPU in chunks, acc = acc^(2^c) * base^chunk, most significant chunk first
@@ -1037,6 +1087,26 @@ class ZeroProof {
     e.check(zkp_zero_proof_prove_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), r.data(), rp.data(), z.data(), a.data(), 0), "zkp_zero_proof_prove_batch");
     return ZeroProof{BigInt::from_limbs(z.data(), 2 * kw), BigInt::from_limbs(a.data(), 2 * kw)};
   }
+  // prove for a whole batch from what the reference's prove takes: every r' comes from one OS seed, expanded on the GPU
+  static std::vector<ZeroProof> prove_batch_seeded(const std::vector<ZeroWitness>& w, const std::vector<ZeroStatement>& st) {
+    if (w.size() != st.size()) throw std::invalid_argument("ZeroProof::prove_batch_seeded: one witness per statement");
+    const size_t B = st.size();
+    if (B == 0) return {};
+    Engine& e = Engine::instance();
+    RangeProofNi::SeedGuard seed(true);
+    const detail::BatchKeys keys(st.begin(), st.end(), [](const ZeroStatement& q) -> const BigInt& { return q.ek.n; });
+    const uint32_t nb = keys.nb, kw = keys.kw;
+    std::vector<uint32_t> c(B * 2 * kw), z(B * 2 * kw), a(B * 2 * kw);
+    std::vector<uint8_t> status(B, 9);
+    RawBuf<uint32_t> r(B * kw, true);
+    for (size_t b = 0; b < B; b++) { st[b].c.to_limbs(&c[b * 2 * kw], 2 * kw); (w[b].r % st[b].ek.nn).to_limbs(r.data() + b * kw, kw); }
+    e.check(zkp_zero_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, c.data(), r.data(), seed.bytes, 0, z.data(), a.data(), status.data(), 0),
+            "zkp_zero_proof_prove_seeded_batch");
+    detail::seeded_status_ok(status, "BigInt::sample_below(0) (zero_enc_proof.rs:45)");
+    std::vector<ZeroProof> out;
+    for (size_t b = 0; b < B; b++) out.push_back(ZeroProof{BigInt::from_limbs(&z[b * 2 * kw], 2 * kw), BigInt::from_limbs(&a[b * 2 * kw], 2 * kw)});
+    return out;
+  }
   Result verify(const ZeroStatement& st) const {                             // :66-94
     Engine& e = Engine::instance();
     const uint32_t nb = width_for(st.ek.n), kw = nb / 32;
@@ -1068,6 +1138,27 @@ class CiphertextProof {
     e.check(zkp_ciphertext_proof_prove_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), x.data(), r.data(), xp.data(), rp.data(), o1.data(), o2.data(), oc.data(), 0),
             "zkp_ciphertext_proof_prove_batch");
     return CiphertextProof{BigInt::from_limbs(o1.data(), z1w), BigInt::from_limbs(o2.data(), 2 * kw), BigInt::from_limbs(oc.data(), 2 * kw)};
+  }
+  // prove for a whole batch from what the reference's prove takes: every (x', r') comes from one OS seed, expanded on the GPU
+  static std::vector<CiphertextProof> prove_batch_seeded(const std::vector<CiphertextWitness>& w, const std::vector<CiphertextStatement>& st) {
+    if (w.size() != st.size()) throw std::invalid_argument("CiphertextProof::prove_batch_seeded: one witness per statement");
+    const size_t B = st.size();
+    if (B == 0) return {};
+    Engine& e = Engine::instance();
+    RangeProofNi::SeedGuard seed(true);
+    const detail::BatchKeys keys(st.begin(), st.end(), [](const CiphertextStatement& q) -> const BigInt& { return q.ek.n; });
+    const uint32_t nb = keys.nb, kw = keys.kw, z1w = kw + ZKP_Z1_EXTRA_LIMBS;
+    std::vector<uint32_t> c(B * 2 * kw), o1(B * z1w), o2(B * 2 * kw), oc(B * 2 * kw);
+    std::vector<uint8_t> status(B, 9);
+    RawBuf<uint32_t> x(B * kw, true), r(B * kw, true);
+    for (size_t b = 0; b < B; b++) { st[b].c.to_limbs(&c[b * 2 * kw], 2 * kw); w[b].x.to_limbs(x.data() + b * kw, kw); w[b].r.to_limbs(r.data() + b * kw, kw); }
+    e.check(zkp_ciphertext_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, c.data(), x.data(), r.data(), seed.bytes, 0, o1.data(), o2.data(),
+                                                    oc.data(), status.data(), 0), "zkp_ciphertext_proof_prove_seeded_batch");
+    detail::seeded_status_ok(status, "BigInt::sample_below(0) (correct_ciphertext.rs:43)");
+    std::vector<CiphertextProof> out;
+    for (size_t b = 0; b < B; b++)
+      out.push_back(CiphertextProof{BigInt::from_limbs(&o1[b * z1w], z1w), BigInt::from_limbs(&o2[b * 2 * kw], 2 * kw), BigInt::from_limbs(&oc[b * 2 * kw], 2 * kw)});
+    return out;
   }
   Result verify(const CiphertextStatement& st) const {                                        // :66-97
     Engine& e = Engine::instance();
@@ -1230,6 +1321,41 @@ class CorrectMessageProof {
       p.a_vec.push_back(BigInt::from_limbs(&av[i * 2 * kw], 2 * kw));
     }
     return p;
+  }
+  // prove for a whole batch under one key from what the reference's prove takes: r, w and the simulated (e_j, z_j) of every proof come from
+  // one OS seed, expanded on the GPU.  Every proof of the batch has the same number of valid messages.
+  static std::vector<CorrectMessageProof> prove_batch_seeded(const EncryptionKey& ek, const std::vector<std::vector<BigInt>>& valid_messages,
+                                                             const std::vector<BigInt>& messages_to_encrypt) {
+    if (valid_messages.size() != messages_to_encrypt.size()) throw std::invalid_argument("CorrectMessageProof::prove_batch_seeded: one message per list");
+    const size_t Bn = valid_messages.size();
+    if (Bn == 0) return {};
+    const size_t K = valid_messages[0].size();
+    if (K == 0) throw Panic("attempt to subtract with overflow (num_of_message - 1, correct_message.rs:58)");
+    for (auto& v : valid_messages) if (v.size() != K) throw std::invalid_argument("CorrectMessageProof::prove_batch_seeded: lists of one length per batch");
+    Engine& e = Engine::instance();
+    RangeProofNi::SeedGuard seed(true);
+    const uint32_t nb = width_for(ek.n), kw = nb / 32;
+    std::vector<uint32_t> n(kw), valid(Bn * K * kw), ct(Bn * 2 * kw), ev(Bn * K * 8), zv(Bn * K * kw), av(Bn * K * 2 * kw);
+    std::vector<uint8_t> status(Bn, 9);
+    RawBuf<uint32_t> msg(Bn * kw, true);
+    ek.n.to_limbs(n.data(), kw);
+    for (size_t b = 0; b < Bn; b++) {
+      messages_to_encrypt[b].to_limbs(msg.data() + b * kw, kw);
+      for (size_t i = 0; i < K; i++) valid_messages[b][i].to_limbs(&valid[(b * K + i) * kw], kw);
+    }
+    e.check(zkp_correct_message_prove_seeded_batch(e.ctx(), nb, Bn, (uint32_t)K, n.data(), 0, valid.data(), msg.data(), seed.bytes, 0, ct.data(), ev.data(), zv.data(),
+                                                   av.data(), status.data(), 0), "zkp_correct_message_prove_seeded_batch");
+    detail::seeded_status_ok(status, "index out of bounds (correct_message.rs:72: no valid message equals the encrypted one)");
+    std::vector<CorrectMessageProof> out(Bn);
+    for (size_t b = 0; b < Bn; b++) {
+      CorrectMessageProof& p = out[b];
+      p.ciphertext = BigInt::from_limbs(&ct[b * 2 * kw], 2 * kw); p.valid_messages = valid_messages[b]; p.ek = ek;
+      for (size_t i = 0; i < K; i++) {
+        p.e_vec.push_back(BigInt::from_limbs(&ev[(b * K + i) * 8], 8)); p.z_vec.push_back(BigInt::from_limbs(&zv[(b * K + i) * kw], kw));
+        p.a_vec.push_back(BigInt::from_limbs(&av[(b * K + i) * 2 * kw], 2 * kw));
+      }
+    }
+    return out;
   }
   Result verify() const {                                                 // :124-162
     Engine& e = Engine::instance();
