@@ -106,6 +106,25 @@ def test_a_bound_of_the_form_2_to_the_k_plus_1_rejects_about_half():
     assert 150 <= total <= 370, total
 
 
+def test_sample_below_rejects_a_candidate_equal_to_the_bound_and_takes_the_next_attempt():
+    """a crafted bound: u IS the candidate of attempt 0 (1019 bits, two blocks per attempt, a masked top limb; the first row whose candidate
+    has its top bit set, so that bit_length(u) is the 1019 the candidate was cut to).  `v < u` is strict: attempt 0 is rejected."""
+    bits, nw, index = 1019, 32, 9
+
+    def cand(row, t):
+        words = M.block(SC.SEED, 2 * t, index, row, M.FIELD_R1) + M.block(SC.SEED, 2 * t + 1, index, row, M.FIELD_R1)
+        return sum(x << (32 * i) for i, x in enumerate(words[:nw])) & ((1 << bits) - 1)
+
+    row = next(r for r in range(64) if cand(r, 0) >> (bits - 1))
+    u = cand(row, 0)
+    assert u.bit_length() == bits
+    v, rejected = M.sample_below(SC.SEED, index, row, M.FIELD_R1, u)
+    assert rejected >= 1 and v == cand(row, rejected) < u and all(cand(row, t) >= u for t in range(rejected))
+    assert M.sample_below(SC.SEED, index, row, M.FIELD_R1, u + 1) == (u, 0)          # one more, and attempt 0 is taken
+    vals, rej = M.sample_below_rows(SC.SEED, index, [row], M.FIELD_R1, u)
+    assert (vals[row], rej[row]) == (v, rejected)
+
+
 # rejected attempts of the sampler cases of the GPU tests, counted once and pinned: the retry path is exercised by them for certain
 REJECTED = {"n1024-shared-ef40-host": 205, "n2048-perkey-ef128-device": 722, "n2048-shared-ef256-host": 808, "n1024-perkey-ef128-device": 464}
 

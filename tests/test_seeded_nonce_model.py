@@ -58,6 +58,23 @@ def test_sample_below_is_the_range_samplers_rule(n):
     assert R.sample_below(SEED, index, w15 >> 2, w15 & 3, n) == (v, rejected)
 
 
+def test_sample_below_rejects_a_candidate_equal_to_the_bound_and_takes_the_next_attempt():
+    """a crafted bound: n IS the candidate of attempt 0 (2043 bits, four blocks per attempt, a masked top limb; the first z_sim slot whose
+    candidate has its top bit set, so that bit_length(n) is the 2043 the candidate was cut to).  `v < n` is strict: attempt 0 is rejected."""
+    bits, nw, index, kind, field = 2043, 64, SC.BIG + 5, M.KIND_CORRECT_MESSAGE, 3
+
+    def cand(slot, t):
+        words = sum((M.block(SEED, 4 * t + k, index, kind, slot, field) for k in range(4)), [])
+        return sum(x << (32 * i) for i, x in enumerate(words[:nw])) & ((1 << bits) - 1)
+
+    slot = next(j for j in range(1, 64) if cand(j, 0) >> (bits - 1))
+    n = cand(slot, 0)
+    assert n.bit_length() == bits
+    v, rejected = M.sample_below(SEED, index, kind, slot, field, n)
+    assert rejected >= 1 and v == cand(slot, rejected) < n and all(cand(slot, t) >= n for t in range(rejected))
+    assert M.sample_below(SEED, index, kind, slot, field, n + 1) == (n, 0)          # one more, and attempt 0 is taken
+
+
 def test_values_are_below_n_and_streams_are_per_index_slot_and_field():
     n = H.test_key(1024)[2]
     out, status, _ = M.nonces(M.KIND_CORRECT_MESSAGE, SEED, 11, [n], 3, K=4)
