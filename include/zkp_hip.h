@@ -366,8 +366,8 @@ int32_t zkp_correct_message_verify_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t
  *     4 DLog               0                      0      r          words 0 .. 15 of block 0: uniform on [0, 2^512), as sample_below(2^512) is
  * OUR rule for n == 0 and for 128 rejected attempts in a row is the range sampler's: all of that proof's nonces are zero and its status
  * is ZKP_VERDICT_MALFORMED; its outputs are what the nonce-input call writes for zero nonces; the other proofs of the batch are unaffected.
- * VerlinProof and MulProof have no seeded prove: they redraw a nonce until it is coprime to n (verlin_proof.rs:64-67,
- * multiplication_proof.rs:148-154), which is a GCD loop and not a plain draw.
+ * VerlinProof and MulProof redraw a nonce until it is coprime to n (verlin_proof.rs:64-67, multiplication_proof.rs:148-154): a GCD loop and
+ * not a plain draw.  Their seeded proves, kinds 5 and 6 of the same construction, follow below this section's entry points.
  *
  * SECURITY CONTRACT.  The seed is worth every nonce of the call: whoever learns it learns the witness from any response (r from
  * z = r' r^e, x from z1 = x' + x e, the DLog secret from y = r + e s).  A (seed, index) pair must never be used for two different
@@ -407,6 +407,50 @@ int32_t zkp_correct_message_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, ui
 int32_t zkp_dlog_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* N, const uint32_t* g,
                                     const uint32_t* ni, const uint32_t* secret, const uint8_t* seed, uint64_t first_index, uint32_t* out_x,
                                     uint32_t* out_y, uint8_t* out_status, uint32_t flags);
+
+/* ------------------------------------------------------------------ seeded proving: VerlinProof, MulProof (nonces coprime to n)
+ * VerlinProof::prove redraws r_a until gcd(r_a, n) == 1 (verlin_proof.rs:61-67), MulProof::prove does the same for r_d
+ * (multiplication_proof.rs:61-62, sample_paillier_random :148-154).  The construction is that of the nonce streams above, unchanged: the
+ * ChaCha20 block function of RFC 8439, key = the seed as 8 little-endian words, state words 13, 14 = (index & 0xffffffff, index >> 32),
+ * state word 15 = 0x80000000 | kind << 20 | slot << 4 | field, with two more kinds:
+ *     kind                 slot                   field  value            draw
+ *     5 Verlin             0                      0      a                sample_below(n)
+ *     5 Verlin             0                      1      a_prime          sample_below(n)
+ *     5 Verlin             0                      2      a_double_prime   sample_below(n)
+ *     5 Verlin             0                      3      r_a              sample_coprime_below(n)
+ *     6 Mul                0                      0      d                sample_below(n)
+ *     6 Mul                0                      1      r_d              sample_coprime_below(n)
+ * sample_coprime_below(n): attempts t = 0, 1, ... produce exactly the candidates of sample_below(n) — the nw first words of blocks
+ * [t nb, (t + 1) nb), the top limb masked to bit_length(n); candidate t is accepted when it is < n AND gcd(candidate, n) == 1; at most 128
+ * attempts in all, rejections of both sorts share the one counter t.  Candidate 0 is rejected by the gcd test unless n == 1.
+ * OUR rule for n == 0, for an even n (outside the limb kernels' domain, as it is for the sigma documents) and for 128 rejected attempts in a
+ * row in any field of the proof: every nonce of that proof is zero and its status is ZKP_VERDICT_MALFORMED; its outputs are what the
+ * nonce-input call writes for zero nonces; the other proofs of the batch are unaffected.  Chunked calls with first_index + lo equal one call.
+ * The SECURITY CONTRACT above holds word for word: `seed` is always a HOST pointer, fresh per call, never reused for another statement. */
+#define ZKP_SEEDED_KIND_VERLIN 5u
+#define ZKP_SEEDED_KIND_MUL 6u
+
+/* The nonces of proofs first_index .. first_index + batch - 1 of kind 5 or 6 (every other kind: ZKP_EINVAL — zkp_nonce_sample_batch keeps
+ * kinds 1 .. 4), by field id: out_field is an array of four pointers (read, not written), each [B][kw]; entries 2 and 3 are not read
+ * for Mul.  out_status [B], nullable.  Device-pointer calls: the output arrays are 16-byte aligned. */
+int32_t zkp_nonce_sample_coprime_batch(zkp_ctx* ctx, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, const uint32_t* n,
+                                       uint64_t n_stride, const uint8_t* seed, uint64_t first_index, uint32_t** out_field /* [4], by field id */,
+                                       uint8_t* out_status, uint32_t flags);
+
+/* zkp_verlin_proof_prove_batch and zkp_mul_proof_prove_batch with their nonce pointers replaced by (seed, first_index): the nonces are
+ * sampled into blocks of the context, the nonce-input call runs on them unchanged, and they are zeroed on the device — as are the seed
+ * and the staged copies of the witness of a host-pointer call — before the call's blocks are given back, on error returns too.
+ * Verlin: out_status [B], nullable, is the sampler's status.  Mul: out_status [B] is the prove's status with the sampler's OR-ed in. */
+int32_t zkp_verlin_proof_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                            const uint32_t* c, const uint32_t* c_prime, const uint32_t* phi_x, const uint32_t* x,
+                                            const uint32_t* x_prime, const uint32_t* x_double_prime, const uint32_t* r_x, const uint8_t* seed,
+                                            uint64_t first_index, uint32_t* out_phi_a, uint32_t* out_z, uint32_t* out_z_prime,
+                                            uint32_t* out_z_double_prime, uint32_t* out_r_z, uint8_t* out_status, uint32_t flags);
+int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                         const uint32_t* e_a, const uint32_t* e_b, const uint32_t* e_c, const uint32_t* a, const uint32_t* b,
+                                         const uint32_t* r_a, const uint32_t* r_b, const uint32_t* r_c, const uint8_t* seed,
+                                         uint64_t first_index, uint32_t* out_f, uint32_t* out_z1, uint32_t* out_z2, uint32_t* out_e_d,
+                                         uint32_t* out_e_db, uint8_t* out_status, uint32_t flags);
 
 /* ------------------------------------------------------------------ wire format
  * The reference serialises big integers as DECIMAL strings (src/serialize.rs:1-31 `bigint`, :33-78 `vecbigint`:

@@ -160,6 +160,12 @@ EXPORTS = {
                                                            C.c_char_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint32]),
     "zkp_dlog_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_nonce_sample_coprime_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64,
+                                                   C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32]),
+    "zkp_verlin_proof_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 7 + [C.c_char_p, C.c_uint64] +
+                                            [C.c_void_p] * 6 + [C.c_uint32]),
+    "zkp_mul_proof_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 8 + [C.c_char_p, C.c_uint64] +
+                                         [C.c_void_p] * 6 + [C.c_uint32]),
     "zkp_verlin_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_verlin_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
     "zkp_multi_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -184,6 +190,7 @@ EXPORTS = {
 
 Z1_EXTRA_LIMBS = 16
 SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KIND_DLOG = 1, 2, 3, 4
+SEEDED_KIND_VERLIN, SEEDED_KIND_MUL = 5, 6
 _lib = None
 
 
@@ -585,6 +592,25 @@ class Context:
     def dlog_prove_seeded(self, n_bits, y_bits, batch, N, g, ni, secret, seed: bytes, first_index: int, out_x, out_y, out_status=None):
         self.check(self.lib.zkp_dlog_prove_seeded_batch(self.h, n_bits, y_bits, batch, ptr(N), ptr(g), ptr(ni), ptr(secret), _seed(seed), first_index,
                                                         ptr(out_x), ptr(out_y), ptr(out_status), self._flags(N, g, ni, secret, out_x, out_y, out_status)))
+
+    # ---- seeded proving of VerlinProof and MulProof: r_a / r_d are redrawn on the GPU until they are coprime to n
+    def nonce_sample_coprime(self, kind, n_bits, batch, n, n_stride, seed: bytes, first_index: int, out_fields, out_status):
+        """zkp_nonce_sample_coprime_batch: out_fields = the four arrays by field id (None for fields 2 and 3 of Mul)"""
+        arr = (C.c_void_p * 4)(*[ptr(a) for a in out_fields])
+        self.check(self.lib.zkp_nonce_sample_coprime_batch(self.h, kind, n_bits, batch, ptr(n), n_stride, _seed(seed), first_index, arr, ptr(out_status),
+                                                           self._flags(n, *out_fields, out_status)))
+
+    def verlin_proof_prove_seeded(self, n_bits, batch, n, n_stride, c, c_prime, phi_x, witness, seed: bytes, first_index: int, outs, out_status=None):
+        """witness = (x, x', x'', r_x); outs = (phi_a, z, z', z'', r_z)"""
+        arrs = [c, c_prime, phi_x, *witness]
+        self.check(self.lib.zkp_verlin_proof_prove_seeded_batch(self.h, n_bits, batch, ptr(n), n_stride, *[ptr(a) for a in arrs], _seed(seed), first_index,
+                                                                *[ptr(a) for a in outs], ptr(out_status), self._flags(n, *arrs, *outs, out_status)))
+
+    def mul_proof_prove_seeded(self, n_bits, batch, n, n_stride, e_a, e_b, e_c, a, b, r_a, r_b, r_c, seed: bytes, first_index: int, out_f, out_z1, out_z2,
+                               out_e_d, out_e_db, out_status):
+        ins, outs = (e_a, e_b, e_c, a, b, r_a, r_b, r_c), (out_f, out_z1, out_z2, out_e_d, out_e_db, out_status)
+        self.check(self.lib.zkp_mul_proof_prove_seeded_batch(self.h, n_bits, batch, ptr(n), n_stride, *[ptr(x) for x in ins], _seed(seed), first_index,
+                                                             *[ptr(x) for x in outs], self._flags(n, *ins, *outs)))
 
     def verlin_proof_prove(self, n_bits, batch, n, n_stride, c, c_prime, phi_x, witness, nonces, outs):
         """witness = (x, x', x'', r_x); nonces = (a, a', a'', r_a); outs = (phi_a, z, z', z'', r_z)"""

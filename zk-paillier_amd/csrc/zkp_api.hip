@@ -24,6 +24,7 @@
 #include "kernels_serde_write.hpp"
 #include "kernels_serde_scan.hpp"
 #include "kernels_sample.hpp"
+#include "kernels_coprime.hpp"
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
 #include "kernels_basen.hpp"
@@ -1498,6 +1499,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 #include "zkp_api_proofs.inc"
 #include "zkp_api_mul.inc"
 #include "zkp_api_seeded.inc"
+#include "zkp_api_seeded_coprime.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE
 #include "zkp_api_multi.inc"

@@ -1207,6 +1207,34 @@ class VerlinProof {
     return VerlinProof{BigInt::from_limbs(pa.data(), 2 * kw), BigInt::from_limbs(z.data(), zw), BigInt::from_limbs(zp.data(), zw),
                        BigInt::from_limbs(zpp.data(), zw), BigInt::from_limbs(rz.data(), 2 * kw)};
   }
+  // prove for a whole batch from what the reference's prove takes: every (a, a', a'', r_a) comes from one OS seed, expanded on the GPU — r_a
+  // redrawn there until gcd(r_a, n) == 1 (:64-67; the rule is sample_coprime_below of include/zkp_hip.h)
+  static std::vector<VerlinProof> prove_batch_seeded(const std::vector<VerlinWitness>& w, const std::vector<VerlinStatement>& st) {
+    if (w.size() != st.size()) throw std::invalid_argument("VerlinProof::prove_batch_seeded: one witness per statement");
+    const size_t B = st.size();
+    if (B == 0) return {};
+    Engine& e = Engine::instance();
+    RangeProofNi::SeedGuard seed(true);
+    const detail::BatchKeys keys(st.begin(), st.end(), [](const VerlinStatement& q) -> const BigInt& { return q.ek.n; });
+    const uint32_t nb = keys.nb, kw = keys.kw, zw = kw + ZKP_Z1_EXTRA_LIMBS;
+    std::vector<uint32_t> c(B * 2 * kw), cp(B * 2 * kw), phx(B * 2 * kw), pa(B * 2 * kw), z(B * zw), zp(B * zw), zpp(B * zw), rz(B * 2 * kw);
+    std::vector<uint8_t> status(B, 9);
+    RawBuf<uint32_t> x(B * kw, true), xp(B * kw, true), xpp(B * kw, true), rx(B * kw, true);
+    for (size_t b = 0; b < B; b++) {
+      st[b].c.to_limbs(&c[b * 2 * kw], 2 * kw); st[b].c_prime.to_limbs(&cp[b * 2 * kw], 2 * kw); st[b].phi_x.to_limbs(&phx[b * 2 * kw], 2 * kw);
+      w[b].x.to_limbs(x.data() + b * kw, kw); w[b].x_prime.to_limbs(xp.data() + b * kw, kw); w[b].x_double_prime.to_limbs(xpp.data() + b * kw, kw);
+      w[b].r_x.to_limbs(rx.data() + b * kw, kw);
+    }
+    e.check(zkp_verlin_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, c.data(), cp.data(), phx.data(), x.data(), xp.data(), xpp.data(),
+                                                rx.data(), seed.bytes, 0, pa.data(), z.data(), zp.data(), zpp.data(), rz.data(), status.data(), 0),
+            "zkp_verlin_proof_prove_seeded_batch");
+    detail::seeded_status_ok(status, "BigInt::sample_below(0), or no r_a coprime to n (verlin_proof.rs:61-67)");
+    std::vector<VerlinProof> out;
+    for (size_t b = 0; b < B; b++)
+      out.push_back(VerlinProof{BigInt::from_limbs(&pa[b * 2 * kw], 2 * kw), BigInt::from_limbs(&z[b * zw], zw), BigInt::from_limbs(&zp[b * zw], zw),
+                                BigInt::from_limbs(&zpp[b * zw], zw), BigInt::from_limbs(&rz[b * 2 * kw], 2 * kw)});
+    return out;
+  }
   Result verify(const VerlinStatement& st) const {                                // :101-135
     Engine& e = Engine::instance();
     const uint32_t nb = width_for(st.ek.n), kw = nb / 32, zw = kw + ZKP_Z1_EXTRA_LIMBS;
@@ -1269,6 +1297,34 @@ class MulProof {
     if (status != 0) throw Panic("called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:95)");
     return MulProof{BigInt::from_limbs(f.data(), kw), BigInt::from_limbs(z1.data(), 2 * kw), BigInt::from_limbs(z2.data(), 2 * kw),
                     BigInt::from_limbs(ed.data(), 2 * kw), BigInt::from_limbs(edb.data(), 2 * kw)};
+  }
+  // prove for a whole batch from what the reference's prove takes: every (d, r_d) comes from one OS seed, expanded on the GPU — r_d
+  // redrawn there until gcd(r_d, n) == 1 (sample_paillier_random, :148-154; the rule is sample_coprime_below of include/zkp_hip.h)
+  static std::vector<MulProof> prove_batch_seeded(const std::vector<MulWitness>& w, const std::vector<MulStatement>& st) {
+    if (w.size() != st.size()) throw std::invalid_argument("MulProof::prove_batch_seeded: one witness per statement");
+    const size_t B = st.size();
+    if (B == 0) return {};
+    Engine& e = Engine::instance();
+    RangeProofNi::SeedGuard seed(true);
+    const detail::BatchKeys keys(st.begin(), st.end(), [](const MulStatement& q) -> const BigInt& { return q.ek.n; });
+    const uint32_t nb = keys.nb, kw = keys.kw;
+    std::vector<uint32_t> ea(B * 2 * kw), eb(B * 2 * kw), ec(B * 2 * kw), f(B * kw), z1(B * 2 * kw), z2(B * 2 * kw), ed(B * 2 * kw), edb(B * 2 * kw);
+    std::vector<uint8_t> status(B, 9);
+    RawBuf<uint32_t> a(B * kw, true), bb(B * kw, true), ra(B * kw, true), rb(B * kw, true), rc(B * kw, true);
+    for (size_t b = 0; b < B; b++) {
+      st[b].e_a.to_limbs(&ea[b * 2 * kw], 2 * kw); st[b].e_b.to_limbs(&eb[b * 2 * kw], 2 * kw); st[b].e_c.to_limbs(&ec[b * 2 * kw], 2 * kw);
+      w[b].a.to_limbs(a.data() + b * kw, kw); w[b].b.to_limbs(bb.data() + b * kw, kw);
+      w[b].r_a.to_limbs(ra.data() + b * kw, kw); w[b].r_b.to_limbs(rb.data() + b * kw, kw); w[b].r_c.to_limbs(rc.data() + b * kw, kw);
+    }
+    e.check(zkp_mul_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, ea.data(), eb.data(), ec.data(), a.data(), bb.data(), ra.data(), rb.data(),
+                                             rc.data(), seed.bytes, 0, f.data(), z1.data(), z2.data(), ed.data(), edb.data(), status.data(), 0),
+            "zkp_mul_proof_prove_seeded_batch");
+    detail::seeded_status_ok(status, "called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:95), or no r_d coprime to n (:148-154)");
+    std::vector<MulProof> out;
+    for (size_t b = 0; b < B; b++)
+      out.push_back(MulProof{BigInt::from_limbs(&f[b * kw], kw), BigInt::from_limbs(&z1[b * 2 * kw], 2 * kw), BigInt::from_limbs(&z2[b * 2 * kw], 2 * kw),
+                             BigInt::from_limbs(&ed[b * 2 * kw], 2 * kw), BigInt::from_limbs(&edb[b * 2 * kw], 2 * kw)});
+    return out;
   }
   Result verify(const MulStatement& st) const {                         // :106-146
     Engine& e = Engine::instance();
