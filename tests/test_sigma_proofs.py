@@ -119,7 +119,7 @@ def test_wide_sigma_cases_are_what_they_claim(oracle, shared):
 @pytest.mark.parametrize("shared", [False, True], ids=["per-proof-keys", "shared-key"])
 def test_gpu_zero_proof_wide_batch(ctx, oracle, shared):
     """300 ZeroProofs at n = 1024: a second, partial 256-thread block in k_sigma_hash / k_words_compare, a GROUPS_PER_BLOCK tail in k_enc,
-    modexp_core (256-bit per-item exponents) and k_modmul.  shared-key: the sliding-window schedule path of sigma_enc."""
+    modexp_core (256-bit per-item exponents) and k_modmul.  shared-key: the sliding-window schedule path of enc_launch."""
     cs, zo, ao, vh, zt, vt = _zero_wide(oracle, shared)
     bt, a = cs["bt"], cs["a"]
     assert bt.B > 256

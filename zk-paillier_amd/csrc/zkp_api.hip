@@ -13,6 +13,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zkp_hip.h"
@@ -52,6 +53,38 @@ struct DevBuf {
 // staging blocks kept by the ctx between calls (host-pointer mode): a call takes the best-fitting cached block or
 // allocates one, and hands everything back when it returns; zkp_ctx_release_staging / zkp_ctx_destroy free them
 struct StageBlock { void* p; size_t cap; };
+
+// The ctx's scratch buffers (zkp_ctx::scratch), each grown on demand (ensure).  A slot that several proof families use has ONE name: the
+// calls of a ctx are ordered on its stream and a family's buffers are dead when its call returns, so a slot only has to be private within
+// one call.  Two names that one call holds at the same time must stay two slots; the comments say which.
+enum ScratchSlot : int {
+  S_E = 0,                // the challenges of a call: RangeProofNi, Zero / Ciphertext / Verlin, Mul / CorrectMessage (shared: one family per call)
+  S_ELEN = 1,
+  S_T1 = 2, S_T2 = 3,     // RangeProofNi: range / 3 and 2 * range / 3 per proof
+  S_IPROOF = 4, S_IROW = 5, S_COUNTER = 6,      // the work list of a RangeProofNi verify and its length
+  S_STATUS = 7,
+  S_MGF = 8, S_PRIMES = 9,                      // NiCorrectKeyProof (S_PRIMES is filled once per ctx and kept)
+  S_DLOG_E = 10,
+  // n^2-sized temporaries of CompositeDLogProof verify, Zero / Ciphertext verify and VerlinProof (shared: one family per call).  Verlin holds
+  // all five while it calls enc_launch and modexp_core, so they stay apart from S_SCHED and S_WORK_COUNTER — as do S_MP_T0 ... and S_CM_T0 ...
+  S_TMP1 = 11, S_TMP2 = 12, S_TMP3 = 13,
+  // (14 is free)
+  S_SCHED = 15,           // build_schedule: the sliding-window script of the launch in hand
+  S_TMP4 = 16, S_TMP5 = 17,                     // VerlinProof only
+  S_WORK_COUNTER = 18,    // fresh_work_counter: the claim counters of the launch in hand
+  S_ENCV = 19,            // Enc-check verdicts of a two-stream verify call
+  S_MP_NN = 20, S_MP_INVST = 21,                // MulProof and CorrectMessageProof: n^2 as words, the inverse kernel's status
+  S_MP_T0 = 22,           // ... S_MP_T0 + 9 (mul_bufs); CorrectMessageProof holds them beside S_CM_*
+  S_MP_END = 32,          // (32 and 33 are free)
+  S_CM_SUM = 34, S_CM_FLAGS = 35,
+  S_CM_T0 = 36,           // ... S_CM_T0 + 7
+  S_CM_END = 44,
+  S_SAMPLE_THIRD = 44, S_SAMPLE_META = 45, S_SAMPLE_STATUS = 46,      // the seeded samplers; they run in front of a prove of any family
+  S_RESIDUE = 47,         // zkp_diag_witness_residue
+  S_COUNT = 48
+};
+static_assert(S_MP_T0 + 9 < S_MP_END && S_MP_END <= S_CM_SUM && S_CM_T0 + 7 < S_CM_END && S_CM_END <= S_SAMPLE_THIRD && S_RESIDUE < S_COUNT,
+              "scratch slot runs overlap");
 
 struct zkp_ctx {
   std::vector<StageBlock> stage_free;
@@ -98,7 +131,7 @@ struct zkp_ctx {
   int key_cache = 1;             // keep the constants of the ONE key of a shared-key call across calls (setup_tag below); $ZKP_KEY_CACHE=0 at zkp_ctx_create or zkp_diag_set_key_cache turn it off
   int host_chunks = -1;          // $ZKP_HOST_CHUNKS at zkp_ctx_create: unset (-1) or 1 = a host-pointer call is one block, N = N equal blocks, 0 = uneven blocks (host_blocks)
   std::string err;
-  DevBuf consts, consts2, table, scratch[48];
+  DevBuf consts, consts2, table, scratch[S_COUNT];
   DevBuf bn_ncst, bn_consts, bn_table, bn_expected, bn_raw, bn_left;
   int enc_form = ZKP_ENC_FORM_AUTO;    // which Paillier launches take the base-n form (zkp_diag_set_enc_form; $ZKP_BASEN is read ONCE, at zkp_ctx_create)
   int bn_occ[2][2] = {{0, 0}, {0, 0}}; // resident workgroups per CU of k_enc_basen<G> / k_enc_basen_keys<G> ([per-key][n = 4096]; 0: not asked yet)
@@ -525,6 +558,14 @@ extern template __global__ void zkp::k_ck_check<GA, false>(CkCheckArgs);
 extern template __global__ void zkp::k_ck_check<GB, false>(CkCheckArgs);
 #endif
 static int group_for_bits(uint32_t mod_bits) { return mod_bits <= 2048 ? GA : mod_bits <= 4096 ? GB : mod_bits <= 8192 ? GC : 0; }
+// The run-time group `g` as a compile-time one: f(std::integral_constant<int, G>) for the candidate G == g, for the last candidate otherwise.
+// The candidates are the instantiations: <GA, GB, GC> for n^2-sized integers (group_for_bits(2 * n_bits)), <GA, GB> for n-sized ones.
+template <int G0, int... Gs, class F> static int32_t with_group(int g, F&& f) {
+  if constexpr (sizeof...(Gs) == 0) { (void)g; return f(std::integral_constant<int, G0>()); }
+  else return g == G0 ? f(std::integral_constant<int, G0>()) : with_group<Gs...>(g, f);
+}
+// the group of the n-sized integers of a proof whose n^2-sized ones take G
+template <int G> constexpr int N_GROUP = G == GC ? GB : GA;
 
 template <int G, class K> static int resident_blocks(zkp_ctx* c, K kernel) {
   int per_cu = 0;
@@ -575,9 +616,9 @@ static int32_t read_setup_flag(zkp_ctx* c, bool* any_bad) {
   return ZKP_OK;
 }
 
-// sliding-window schedule for a launch-uniform exponent (device resident, ctx scratch slot 15)
+// sliding-window schedule for a launch-uniform exponent (device resident, ctx scratch S_SCHED)
 static int32_t build_schedule(zkp_ctx* c, const uint32_t* exp_words, uint32_t exp_bits, const uint8_t** out) {
-  DevBuf& b = c->scratch[15];
+  DevBuf& b = c->scratch[S_SCHED];
   int32_t st = ensure(c, b, sched_buffer_bytes((int)exp_bits));
   if (st) return st;
   hipLaunchKernelGGL(k_sliding_schedule, dim3(1), dim3(64), 0, c->stream, exp_words, (int)exp_bits, (uint8_t*)b.p);
@@ -586,10 +627,10 @@ static int32_t build_schedule(zkp_ctx* c, const uint32_t* exp_words, uint32_t ex
   return ZKP_OK;
 }
 
-// zeroed work counter for the next k_enc launch (ctx scratch slot 18; one 8-byte slot per launch in flight is enough
+// zeroed work counter for the next k_enc launch (ctx scratch S_WORK_COUNTER; one 8-byte slot per launch in flight is enough
 // because launches of one ctx are ordered on its stream)
 static int32_t fresh_work_counter(zkp_ctx* c, unsigned long long** out) {
-  DevBuf& b = c->scratch[18];
+  DevBuf& b = c->scratch[S_WORK_COUNTER];
   int32_t st = ensure(c, b, 64);
   if (st) return st;
   HIPCHK(c, hipMemsetAsync(b.p, 0, 64, c->stream));
@@ -1007,10 +1048,10 @@ extern "C" int32_t zkp_diag_table_traffic(zkp_ctx* c, int32_t mode, int32_t pass
   unsigned blocks = 0;
   int32_t st = table_for<G>(c, k_enc<G, true>, ~0ull >> 8, &blocks);      // the resident grid of the Paillier kernels and its table
   if (st) return st;
-  if ((st = ensure(c, c->scratch[18], 64))) return st;
+  if ((st = ensure(c, c->scratch[S_WORK_COUNTER], 64))) return st;
   {
     TimedRegion tr(c, 0);
-    hipLaunchKernelGGL(k_table_traffic<G>, dim3(blocks), dim3(256), 0, c->stream, (uint32_t*)c->table.p, (int)mode, (int)passes, (uint32_t*)c->scratch[18].p);
+    hipLaunchKernelGGL(k_table_traffic<G>, dim3(blocks), dim3(256), 0, c->stream, (uint32_t*)c->table.p, (int)mode, (int)passes, (uint32_t*)c->scratch[S_WORK_COUNTER].p);
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1334,30 +1375,32 @@ extern "C" int32_t zkp_modexp_batch(zkp_ctx* c, uint32_t mod_bits, uint32_t exp_
   const uint32_t* dmod = s.in(mod, mod_stride ? count * mod_stride : L);
   uint32_t* dout = s.out(out, count * L);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(mod_bits)) {
-      case GA: st = modexp_impl<GA>(c, exp_bits, count, dbase, dexp, exp_stride, dmod, mod_stride, dout); break;
-      case GB: st = modexp_impl<GB>(c, exp_bits, count, dbase, dexp, exp_stride, dmod, mod_stride, dout); break;
-      default: st = modexp_impl<GC>(c, exp_bits, count, dbase, dexp, exp_stride, dmod, mod_stride, dout); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(mod_bits), [&](auto G) { return modexp_impl<G()>(c, exp_bits, count, dbase, dexp, exp_stride, dmod, mod_stride, dout); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
 
+// THE launch of k_modmul<G>: out = a * b mod M under the constants in `consts` (one record, or one per item); a_words / b_words = 0: as out_words
+template <int G>
+static int32_t modmul_ctx(zkp_ctx* c, const DevBuf& consts, bool per_item, uint64_t batch, const uint32_t* a, int a_words, const uint32_t* b, int b_words,
+                          uint32_t* out, int out_words) {
+  using CL = ConstLayout<G>;
+  using LL = LdsLayout<G>;
+  ModmulArgs m{a, b, (const uint32_t*)consts.p, per_item ? (uint64_t)CL::WORDS : 0, out, batch, out_words, a_words, b_words};
+  hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+
 template <int G>
 static int32_t modmul_impl(zkp_ctx* c, uint64_t count, const uint32_t* a, const uint32_t* b, const uint32_t* mod, uint64_t mod_stride, uint32_t* out) {
-  using CL = ConstLayout<G>;
   using LL = LdsLayout<G>;
   const uint64_t nmod = mod_stride ? count : 1;
   int32_t st = clear_setup_flag(c);
   if (st) return st;
   if ((st = run_setup<G>(c, mod, mod_stride, LL::NW, 0, nmod, c->consts))) return st;
   bool bad = false;
-  ModmulArgs args{a, b, (const uint32_t*)c->consts.p, mod_stride ? (uint64_t)CL::WORDS : 0, out, count, LL::NW};
-  const unsigned blocks = (unsigned)((count + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK);
-  hipLaunchKernelGGL(k_modmul<G>, dim3(blocks), dim3(256), LL::BYTES_PER_BLOCK, c->stream, args);
-  HIPCHK(c, hipGetLastError());
+  if ((st = modmul_ctx<G>(c, c->consts, mod_stride != 0, count, a, 0, b, 0, out, LL::NW))) return st;
   if ((st = read_setup_flag(c, &bad))) return st;
   if (bad) { c->err = "even or trivial modulus in batch"; return ZKP_ENONCANONICAL; }
   return ZKP_OK;
@@ -1376,13 +1419,7 @@ extern "C" int32_t zkp_modmul_batch(zkp_ctx* c, uint32_t mod_bits, uint64_t coun
   const uint32_t* dm = s.in(mod, mod_stride ? count * mod_stride : L);
   uint32_t* dout = s.out(out, count * L);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(mod_bits)) {
-      case GA: st = modmul_impl<GA>(c, count, da, db, dm, mod_stride, dout); break;
-      case GB: st = modmul_impl<GB>(c, count, da, db, dm, mod_stride, dout); break;
-      default: st = modmul_impl<GC>(c, count, da, db, dm, mod_stride, dout); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(mod_bits), [&](auto G) { return modmul_impl<G()>(c, count, da, db, dm, mod_stride, dout); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -1393,20 +1430,22 @@ static int32_t enc_setup(zkp_ctx* c, uint32_t n_bits, const uint32_t* n, uint64_
   return run_setup<G>(c, n, n_stride, (int)(n_bits / 32), 1, nkeys, c->consts);
 }
 
+// THE launch of k_enc in its flat modes, under the constants already set up in c->consts: Enc(m, r) -> out (mode 0), or, with out == nullptr,
+// Enc(m, r) compared with c1 [* cipher_x] -> verdict (mode 2).  m_words / r_words: words per element (0 = n_bits / 32; m_words < 0: m = 0).
 template <int G>
-static int32_t enc_impl(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint32_t* n, uint64_t n_stride, const uint32_t* m, const uint32_t* r,
-                        uint32_t* out) {
+static int32_t enc_launch(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint32_t* n, uint64_t n_stride, const uint32_t* m, int m_words,
+                          const uint32_t* r, int r_words, uint32_t* out, const uint32_t* c1 = nullptr, const uint32_t* cipher_x = nullptr,
+                          uint8_t* verdict = nullptr) {
   using CL = ConstLayout<G>;
-  const uint64_t nkeys = n_stride ? count : 1;
-  int32_t st = enc_setup<G>(c, n_bits, n, n_stride, nkeys);
-  if (st) return st;
   unsigned blocks = 0;
+  int32_t st;
   if ((st = table_for<G>(c, k_enc<G, true>, count, &blocks))) return st;
   EncArgs a{};
   a.n = n; a.n_stride = n_stride; a.consts = (const uint32_t*)c->consts.p; a.const_stride = n_stride ? (uint64_t)CL::WORDS : 0;
-  a.table = (uint32_t*)c->table.p; a.count = count; a.n_bits = (int)n_bits; a.mode = 0;
-  a.m = m; a.r = r; a.out = out; a.items_per_key = n_stride ? 1 : count;
-  if (n_stride == 0 && !pair_ladder<G>(c, a.count) && (st = build_schedule(c, n, n_bits, &a.sched))) return st;
+  a.table = (uint32_t*)c->table.p; a.count = count; a.n_bits = (int)n_bits; a.mode = out ? 0 : 2;
+  a.m = m; a.r = r; a.out = out; a.items_per_key = n_stride ? 1 : count; a.m_words = m_words; a.r_words = r_words;
+  a.c1 = c1; a.cipher_x = cipher_x; a.verdict = verdict;
+  if (n_stride == 0 && !pair_ladder<G>(c, a.count) && (st = build_schedule(c, n, n_bits, &a.sched))) return st;   // (the pair ladder reads n itself)
   if ((st = fresh_work_counter(c, &a.work_counter))) return st;
   {
     TimedRegion tr(c, count);
@@ -1414,6 +1453,13 @@ static int32_t enc_impl(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint3
   }
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
+}
+
+template <int G>
+static int32_t enc_impl(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint32_t* n, uint64_t n_stride, const uint32_t* m, const uint32_t* r,
+                        uint32_t* out) {
+  const int32_t st = enc_setup<G>(c, n_bits, n, n_stride, n_stride ? count : 1);
+  return st ? st : enc_launch<G>(c, n_bits, count, n, n_stride, m, 0, r, 0, out);
 }
 
 extern "C" int32_t zkp_paillier_enc_batch(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint32_t* n, uint64_t n_stride, const uint32_t* m,
@@ -1430,13 +1476,7 @@ extern "C" int32_t zkp_paillier_enc_batch(zkp_ctx* c, uint32_t n_bits, uint64_t 
   const uint32_t* dr = s.in(r, count * kw);
   uint32_t* dout = s.out(out_c, count * 2 * kw);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = enc_impl<GA>(c, n_bits, count, dn, n_stride, dm, dr, dout); break;
-      case GB: st = enc_impl<GB>(c, n_bits, count, dn, n_stride, dm, dr, dout); break;
-      default: st = enc_impl<GC>(c, n_bits, count, dn, n_stride, dm, dr, dout); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return enc_impl<G()>(c, n_bits, count, dn, n_stride, dm, dr, dout); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -1445,25 +1485,8 @@ extern "C" int32_t zkp_paillier_enc_batch(zkp_ctx* c, uint32_t n_bits, uint64_t 
 template <int G>
 static int32_t enc_check_impl(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint32_t* n, uint64_t n_stride, const uint32_t* m, const uint32_t* r,
                               const uint32_t* exp_or_a, const uint32_t* mulc_b, uint8_t* out_ok) {
-  using CL = ConstLayout<G>;
-  const uint64_t nkeys = n_stride ? count : 1;
-  int32_t st = enc_setup<G>(c, n_bits, n, n_stride, nkeys);
-  if (st) return st;
-  unsigned blocks = 0;
-  if ((st = table_for<G>(c, k_enc<G, true>, count, &blocks))) return st;
-  EncArgs a{};
-  a.n = n; a.n_stride = n_stride; a.consts = (const uint32_t*)c->consts.p; a.const_stride = n_stride ? (uint64_t)CL::WORDS : 0;
-  a.table = (uint32_t*)c->table.p; a.count = count; a.n_bits = (int)n_bits; a.mode = 2;
-  a.m = m; a.r = r; a.items_per_key = n_stride ? 1 : count;
-  a.c1 = exp_or_a; a.cipher_x = mulc_b; a.verdict = out_ok;
-  if (n_stride == 0 && !pair_ladder<G>(c, a.count) && (st = build_schedule(c, n, n_bits, &a.sched))) return st;
-  if ((st = fresh_work_counter(c, &a.work_counter))) return st;
-  {
-    TimedRegion tr(c, count);
-    launch_k_enc<G>(c, blocks, a);
-  }
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  const int32_t st = enc_setup<G>(c, n_bits, n, n_stride, n_stride ? count : 1);
+  return st ? st : enc_launch<G>(c, n_bits, count, n, n_stride, m, 0, r, 0, nullptr, exp_or_a, mulc_b, out_ok);
 }
 
 extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uint32_t* n, uint64_t n_stride, const uint32_t* m,
@@ -1485,13 +1508,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
   const uint32_t* db = s.in(mulc_b, count * 2 * kw);
   uint8_t* dok = s.out(out_ok, count);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = enc_check_impl<GA>(c, n_bits, count, dn, n_stride, dm, dr, da, db, dok); break;
-      case GB: st = enc_check_impl<GB>(c, n_bits, count, dn, n_stride, dm, dr, da, db, dok); break;
-      default: st = enc_check_impl<GC>(c, n_bits, count, dn, n_stride, dm, dr, da, db, dok); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return enc_check_impl<G()>(c, n_bits, count, dn, n_stride, dm, dr, da, db, dok); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -1499,7 +1516,6 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 #include "zkp_api_proofs.inc"
 #include "zkp_api_mul.inc"
 #include "zkp_api_seeded.inc"
-#include "zkp_api_seeded_coprime.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE
 #include "zkp_api_multi.inc"

@@ -1,8 +1,6 @@
 // zkp_api_mul.inc — host side of zkp_modinv_batch, MulProof and CorrectMessageProof (SURVEY §8(f) rank 4);
 // included by zkp_api.hip.  Compositions of k_enc / k_modexp / k_modmul with the kernels of kernels_inv.hpp.
 
-enum { S_MP_E = 0, S_MP_NN = 20, S_MP_INVST = 21, S_MP_T0 = 22 /* .. S_MP_T0 + 9 */, S_CM_SUM = 34, S_CM_FLAGS = 35, S_CM_T0 = 36 /* .. +7 */ };
-
 static int32_t launch_modinv(zkp_ctx* c, uint64_t count, int kw, const uint32_t* a, uint64_t a_stride, const uint32_t* mod, uint64_t mod_stride,
                              uint32_t* out, uint64_t out_stride, uint8_t* status) {
   // The kernel is latency bound (dependent LDS / carry chains, data-dependent branches): small blocks of `lanes` items
@@ -45,17 +43,6 @@ static int32_t square_words(zkp_ctx* c, const uint32_t* n, uint64_t n_stride, in
   return ZKP_OK;
 }
 
-template <int G>
-static int32_t modmul_ctx(zkp_ctx* c, const DevBuf& consts, bool per_item, uint64_t batch, const uint32_t* a, int a_words, const uint32_t* b, int b_words,
-                          uint32_t* out, int out_words) {
-  using CL = ConstLayout<G>;
-  using LL = LdsLayout<G>;
-  ModmulArgs m{a, b, (const uint32_t*)consts.p, per_item ? (uint64_t)CL::WORDS : 0, out, batch, out_words, a_words, b_words ? b_words : out_words};
-  hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
-}
-
 static int32_t hash_list(zkp_ctx* c, uint64_t batch, std::initializer_list<HashOp> ops, uint32_t* e) {
   HashListArgs h{};
   for (const HashOp& o : ops) h.op[h.nops++] = o;
@@ -70,17 +57,18 @@ static int32_t mul_bufs(zkp_ctx* c, uint64_t batch, uint32_t kw, MulBufs* b) {
   int32_t st;
   for (int k = 0; k < 10; k++) { if ((st = ensure(c, c->scratch[S_MP_T0 + k], batch * 2 * kw * 4))) return st; b->t[k] = (uint32_t*)c->scratch[S_MP_T0 + k].p; }
   if ((st = ensure(c, c->scratch[S_MP_INVST], batch))) return st;
-  if ((st = ensure(c, c->scratch[S_MP_E], batch * 32))) return st;
-  b->invst = (uint8_t*)c->scratch[S_MP_INVST].p; b->e = (uint32_t*)c->scratch[S_MP_E].p;
+  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
+  b->invst = (uint8_t*)c->scratch[S_MP_INVST].p; b->e = (uint32_t*)c->scratch[S_E].p;
   return ZKP_OK;
 }
 
 // multiplication_proof.rs:60-104
-template <int G, int GN>
+template <int G>
 static int32_t mul_prove_impl(zkp_ctx* c, uint32_t n_bits, uint64_t B, const uint32_t* n, uint64_t n_stride, const uint32_t* e_a, const uint32_t* e_b,
                               const uint32_t* e_c, const uint32_t* a, const uint32_t* b, const uint32_t* r_a, const uint32_t* r_b, const uint32_t* r_c,
                               const uint32_t* d, const uint32_t* r_d, uint32_t* f, uint32_t* z1, uint32_t* z2, uint32_t* e_d, uint32_t* e_db, uint8_t* status) {
   using CL = ConstLayout<G>;
+  constexpr int GN = N_GROUP<G>;
   const uint32_t kw = n_bits / 32;
   const uint64_t nkeys = n_stride ? B : 1;
   const bool per = n_stride != 0;
@@ -92,14 +80,14 @@ static int32_t mul_prove_impl(zkp_ctx* c, uint32_t n_bits, uint64_t B, const uin
   const uint32_t* nn = nullptr;
   if ((st = square_words(c, n, n_stride, (int)kw, nkeys, &nn))) return st;
   uint32_t *rdb = q.t[0], *db = q.t[1], *t2 = q.t[2], *t3 = q.t[3], *t4 = q.t[4], *t5 = q.t[5], *ea = q.t[6], *dred = q.t[7];
-  if ((st = sigma_enc<G>(c, n_bits, B, n, n_stride, d, (int)kw, r_d, (int)kw, e_d))) return st;                       // e_d = Enc(d, r_d) :63-68
+  if ((st = enc_launch<G>(c, n_bits, B, n, n_stride, d, (int)kw, r_d, (int)kw, e_d))) return st;                       // e_d = Enc(d, r_d) :63-68
   if ((st = modmul_ctx<G>(c, c->consts, per, B, r_d, (int)kw, r_b, (int)kw, rdb, (int)(2 * kw)))) return st;          // r_db = r_d * r_b :69 (< n^2: exact)
   if ((st = modmul_ctx<G>(c, c->consts, per, B, d, (int)kw, b, (int)kw, db, (int)(2 * kw)))) return st;               // db = d * b :70
-  if ((st = sigma_enc<G>(c, n_bits, B, n, n_stride, db, (int)(2 * kw), rdb, (int)(2 * kw), e_db))) return st;         // e_db :71-76
+  if ((st = enc_launch<G>(c, n_bits, B, n, n_stride, db, (int)(2 * kw), rdb, (int)(2 * kw), e_db))) return st;         // e_db :71-76
   if ((st = hash_list(c, B, {{n, n_stride, 0, kw, 1}, {e_a, 2 * kw, 0, 2 * kw, 1}, {e_b, 2 * kw, 0, 2 * kw, 1}, {e_c, 2 * kw, 0, 2 * kw, 1},
                              {e_d, 2 * kw, 0, 2 * kw, 1}, {e_db, 2 * kw, 0, 2 * kw, 1}}, q.e))) return st;              // e :77-84
   if ((st = modmul_ctx<GN>(c, c->consts2, per, B, q.e, 8, a, (int)kw, ea, (int)kw))) return st;                       // e*a mod n :87
-  if ((st = modmul_ctx<GN>(c, c->consts2, per, B, d, (int)kw, nullptr, 0, dred, (int)kw))) return st;                 // d mod n
+  if ((st = modmul_ctx<GN>(c, c->consts2, per, B, d, (int)kw, nullptr, (int)kw, dred, (int)kw))) return st;                 // d mod n
   hipLaunchKernelGGL(k_modadd, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, ea, dred, n, n_stride, (int)kw, B, f);   // f :88
   HIPCHK(c, hipGetLastError());
   // r_a^e (:89), r_c^e (:92) and r_b^f (:91) are independent of each other: one launch, their chains side by side
@@ -133,8 +121,8 @@ static int32_t mul_verify_impl(zkp_ctx* c, uint32_t n_bits, uint64_t B, const ui
   uint32_t *c1 = q.t[0], *c2 = q.t[1], *l1 = q.t[2], *t3 = q.t[3], *t4 = q.t[4], *l2 = q.t[5];
   if ((st = hash_list(c, B, {{n, n_stride, 0, kw, 1}, {e_a, 2 * kw, 0, 2 * kw, 1}, {e_b, 2 * kw, 0, 2 * kw, 1}, {e_c, 2 * kw, 0, 2 * kw, 1},
                              {e_d, 2 * kw, 0, 2 * kw, 1}, {e_db, 2 * kw, 0, 2 * kw, 1}}, q.e))) return st;              // e :107-114
-  if ((st = sigma_enc<G>(c, n_bits, B, n, n_stride, f, (int)kw, z1, (int)(2 * kw), c1))) return st;                   // Enc(f, z1) :116-122
-  if ((st = sigma_enc<G>(c, n_bits, B, n, n_stride, nullptr, -1, z2, (int)(2 * kw), c2))) return st;                  // Enc(0, z2) :123-129
+  if ((st = enc_launch<G>(c, n_bits, B, n, n_stride, f, (int)kw, z1, (int)(2 * kw), c1))) return st;                   // Enc(f, z1) :116-122
+  if ((st = enc_launch<G>(c, n_bits, B, n, n_stride, nullptr, -1, z2, (int)(2 * kw), c2))) return st;                  // Enc(0, z2) :123-129
   // e_a^e (:131), e_c^e (:133) and e_b^f (:136): one launch
   if ((st = modexp_multi<G>(c, B, per, {{256, e_a, q.e, 8, l1, (int)(2 * kw), 0}, {256, e_c, q.e, 8, t3, (int)(2 * kw), 0},
                                         {n_bits, e_b, f, kw, l2, (int)(2 * kw), 0}}))) return st;
@@ -168,13 +156,7 @@ extern "C" int32_t zkp_mul_proof_prove_batch(zkp_ctx* c, uint32_t n_bits, uint64
   uint32_t *dz1 = s.out(out_z1, batch * 2 * kw), *dz2 = s.out(out_z2, batch * 2 * kw), *ded = s.out(out_e_d, batch * 2 * kw), *dedb = s.out(out_e_db, batch * 2 * kw);
   uint8_t* dst = s.out(out_status, batch);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = mul_prove_impl<GA, GA>(c, n_bits, batch, dn, n_stride, dea, deb, dec, da, db, dra, drb, drc, dd, drd, df, dz1, dz2, ded, dedb, dst); break;
-      case GB: st = mul_prove_impl<GB, GA>(c, n_bits, batch, dn, n_stride, dea, deb, dec, da, db, dra, drb, drc, dd, drd, df, dz1, dz2, ded, dedb, dst); break;
-      default: st = mul_prove_impl<GC, GB>(c, n_bits, batch, dn, n_stride, dea, deb, dec, da, db, dra, drb, drc, dd, drd, df, dz1, dz2, ded, dedb, dst); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return mul_prove_impl<G()>(c, n_bits, batch, dn, n_stride, dea, deb, dec, da, db, dra, drb, drc, dd, drd, df, dz1, dz2, ded, dedb, dst); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -197,13 +179,7 @@ extern "C" int32_t zkp_mul_proof_verify_batch(zkp_ctx* c, uint32_t n_bits, uint6
   const uint32_t *dz1 = s.in(z1, batch * 2 * kw), *dz2 = s.in(z2, batch * 2 * kw), *ded = s.in(e_d, batch * 2 * kw), *dedb = s.in(e_db, batch * 2 * kw);
   uint8_t* dv = s.out(out_verdict, batch);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = mul_verify_impl<GA>(c, n_bits, batch, dn, n_stride, dea, deb, dec, df, dz1, dz2, ded, dedb, dv); break;
-      case GB: st = mul_verify_impl<GB>(c, n_bits, batch, dn, n_stride, dea, deb, dec, df, dz1, dz2, ded, dedb, dv); break;
-      default: st = mul_verify_impl<GC>(c, n_bits, batch, dn, n_stride, dea, deb, dec, df, dz1, dz2, ded, dedb, dv); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return mul_verify_impl<G()>(c, n_bits, batch, dn, n_stride, dea, deb, dec, df, dz1, dz2, ded, dedb, dv); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -249,17 +225,18 @@ static int32_t cm_common(zkp_ctx* c, uint32_t n_bits, uint64_t B, uint32_t K, co
   return modmul_ctx<G>(c, c->consts, o->per, R, ct_rows, (int)(2 * kw), gi, (int)(2 * kw), o->u, (int)(2 * kw));           // u_i
 }
 
-template <int G, int GN>
+template <int G>
 static int32_t cm_prove_impl(zkp_ctx* c, uint32_t n_bits, uint64_t B, uint32_t K, const uint32_t* n, uint64_t n_stride, const uint32_t* valid,
                              const uint32_t* message, const uint32_t* r, const uint32_t* e_sim, const uint32_t* z_sim, const uint32_t* w, uint32_t* ct,
                              uint32_t* e_vec, uint32_t* z_vec, uint32_t* a_vec, uint8_t* status) {
   using CL = ConstLayout<G>;
+  constexpr int GN = N_GROUP<G>;
   const uint32_t kw = n_bits / 32;
   const uint64_t R = B * K;
   int32_t st;
   // ciphertext = Enc(message, r) :44-49 (per-proof key context; cm_common then switches c->consts to the row view)
   if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, n_stride ? B : 1, c->consts))) return st;
-  if ((st = sigma_enc<G>(c, n_bits, B, n, n_stride, message, (int)kw, r, (int)kw, ct))) return st;
+  if ((st = enc_launch<G>(c, n_bits, B, n, n_stride, message, (int)kw, r, (int)kw, ct))) return st;
   CmCommon o;
   if ((st = cm_common<G>(c, n_bits, B, K, n, n_stride, valid, ct, &o))) return st;
   for (int k : {S_CM_T0 + 3, S_CM_T0 + 4, S_CM_T0 + 5, S_CM_T0 + 6}) if ((st = ensure(c, c->scratch[k], R * 2 * kw * 4 + 64))) return st;
@@ -344,13 +321,7 @@ extern "C" int32_t zkp_correct_message_prove_batch(zkp_ctx* c, uint32_t n_bits, 
   uint32_t *dct = s.out(out_ciphertext, batch * 2 * kw), *dev = s.out(out_e_vec, R * 8), *dzv = s.out(out_z_vec, R * kw), *dav = s.out(out_a_vec, R * 2 * kw);
   uint8_t* dst = s.out(out_status, batch);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = cm_prove_impl<GA, GA>(c, n_bits, batch, K, dn, n_stride, dv, dm, dr, des, dzs, dw, dct, dev, dzv, dav, dst); break;
-      case GB: st = cm_prove_impl<GB, GA>(c, n_bits, batch, K, dn, n_stride, dv, dm, dr, des, dzs, dw, dct, dev, dzv, dav, dst); break;
-      default: st = cm_prove_impl<GC, GB>(c, n_bits, batch, K, dn, n_stride, dv, dm, dr, des, dzs, dw, dct, dev, dzv, dav, dst); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return cm_prove_impl<G()>(c, n_bits, batch, K, dn, n_stride, dv, dm, dr, des, dzs, dw, dct, dev, dzv, dav, dst); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -372,13 +343,7 @@ extern "C" int32_t zkp_correct_message_verify_batch(zkp_ctx* c, uint32_t n_bits,
                  *dav = s.in(a_vec, R * 2 * kw);
   uint8_t* dvd = s.out(out_verdict, batch);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = cm_verify_impl<GA>(c, n_bits, batch, K, dn, n_stride, dv, dct, dev, dzv, dav, dvd); break;
-      case GB: st = cm_verify_impl<GB>(c, n_bits, batch, K, dn, n_stride, dv, dct, dev, dzv, dav, dvd); break;
-      default: st = cm_verify_impl<GC>(c, n_bits, batch, K, dn, n_stride, dv, dct, dev, dzv, dav, dvd); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return cm_verify_impl<G()>(c, n_bits, batch, K, dn, n_stride, dv, dct, dev, dzv, dav, dvd); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)

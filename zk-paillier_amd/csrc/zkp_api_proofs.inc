@@ -1,14 +1,5 @@
 // zkp_api_proofs.inc — proof-level entry points of the C ABI (included by zkp_api.hip).
 
-enum { S_E = 0, S_ELEN, S_T1, S_T2, S_IPROOF, S_IROW, S_COUNTER, S_STATUS, S_MGF, S_PRIMES, S_DLOG_E };
-enum { S_ENCV = 19 };   // Enc-check verdicts of a two-stream verify call
-
-static int n_group(uint32_t n_bits) { return group_for_bits(n_bits); }
-
-struct RangeStaged {
-  zkp_range_ni_proofs p;
-};
-
 // which arrays of the struct a call dereferences
 enum : unsigned { RA_RANGE = 1, RA_CIPHERTEXT = 2, RA_PAIRS = 4, RA_RESP = 8 };
 static bool range_args_ok(const zkp_range_ni_proofs* p, unsigned need = RA_RANGE | RA_CIPHERTEXT | RA_PAIRS | RA_RESP) {
@@ -21,6 +12,26 @@ static bool range_args_ok(const zkp_range_ni_proofs* p, unsigned need = RA_RANGE
   if (p->error_factor && (need & RA_PAIRS) && (!p->c1 || !p->c2)) return false;
   if (p->error_factor && (need & RA_RESP) && (!p->resp_kind || !p->resp_j || !p->resp_w1 || !p->resp_r1 || !p->resp_w2 || !p->resp_r2)) return false;
   return true;
+}
+
+// proofs [lo, lo + count) of `p` at EF rows per proof, and their witness: a batch is structure-of-arrays, so a slice of it is one too
+static zkp_range_ni_proofs range_slice(const zkp_range_ni_proofs& p, size_t EF, uint64_t lo, uint64_t count) {
+  const size_t kw = p.n_bits / 32;
+  zkp_range_ni_proofs q = p;
+  q.batch = count;
+  if (q.n) q.n += lo * p.n_stride;
+  if (q.range) q.range += lo * kw;
+  if (q.ciphertext) q.ciphertext += lo * 2 * kw;
+  for (uint32_t** a : {&q.c1, &q.c2}) if (*a) *a += lo * EF * 2 * kw;
+  for (uint8_t** a : {&q.resp_kind, &q.resp_j}) if (*a) *a += lo * EF;
+  for (uint32_t** a : {&q.resp_w1, &q.resp_r1, &q.resp_w2, &q.resp_r2}) if (*a) *a += lo * EF * kw;
+  return q;
+}
+static zkp_range_ni_witness range_witness_slice(const zkp_range_ni_witness& w, size_t kw, size_t EF, uint64_t lo) {
+  zkp_range_ni_witness q = w;
+  for (const uint32_t** a : {&q.x, &q.r}) if (*a) *a += lo * kw;
+  for (const uint32_t** a : {&q.w1, &q.w2, &q.r1, &q.r2}) if (*a) *a += lo * EF * kw;
+  return q;
 }
 
 template <int G>
@@ -45,10 +56,11 @@ static int32_t range_hash(zkp_ctx* c, const zkp_range_ni_proofs& p, uint8_t* e, 
 }
 
 // phases: 1 = generate_encrypted_pairs, 2 = challenge + generate_proof; e_in != nullptr: challenge supplied by the caller
-template <int G, int GN>
+template <int G>
 static int32_t range_prove_impl(zkp_ctx* c, const zkp_range_ni_proofs& p, const zkp_range_ni_witness& w, uint8_t* e, uint8_t* elen, uint8_t* status,
                                 uint32_t EF = ZKP_SECURITY_PARAMETER, int phases = 3, const uint8_t* e_in = nullptr, const uint8_t* e_len_in = nullptr) {
   using CL = ConstLayout<G>;
+  constexpr int GN = N_GROUP<G>;
   const uint32_t kw = p.n_bits / 32;
   const uint64_t nkeys = p.n_stride ? p.batch : 1;
   int32_t st;
@@ -140,26 +152,13 @@ static int32_t range_prove_entry(zkp_ctx* c, const char* name, const zkp_range_n
     if (!st) st = pp.h2d(blocks[0], blocks[1], c->ev_pipe[0]);
     for (size_t k = 0; k < nb && !st; k++) {
       const size_t lo = blocks[k], hi = blocks[k + 1];
-      zkp_range_ni_proofs q = d;
-      q.batch = hi - lo;
-      if (p->n_stride) q.n = d.n + lo * kw;
-      if (phases & 2) q.range = d.range + lo * kw;
-      q.c1 = d.c1 + lo * EF * 2 * kw; q.c2 = d.c2 + lo * EF * 2 * kw;
-      if (phases & 2) {
-        q.resp_kind = d.resp_kind + lo * EF; q.resp_j = d.resp_j + lo * EF;
-        q.resp_w1 = d.resp_w1 + lo * EF * kw; q.resp_r1 = d.resp_r1 + lo * EF * kw; q.resp_w2 = d.resp_w2 + lo * EF * kw; q.resp_r2 = d.resp_r2 + lo * EF * kw;
-      }
-      zkp_range_ni_witness qw = dw;
-      if (phases & 2) { qw.x = dw.x + lo * kw; qw.r = dw.r + lo * kw; }
-      qw.w1 = dw.w1 + lo * EF * kw; qw.w2 = dw.w2 + lo * EF * kw; qw.r1 = dw.r1 + lo * EF * kw; qw.r2 = dw.r2 + lo * EF * kw;
+      // (arrays the phases do not read are the caller's own pointers here: sliced like the rest, and as little dereferenced)
+      const zkp_range_ni_proofs q = range_slice(d, EF, lo, hi - lo);
+      const zkp_range_ni_witness qw = range_witness_slice(dw, kw, EF, lo);
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pipe[2 * k], 0));
       const uint8_t* qe = dei ? dei + lo * 32 : nullptr;
       const uint8_t* ql = deli ? deli + lo : nullptr;
-      switch (group_for_bits(2 * p->n_bits)) {
-        case GA: st = range_prove_impl<GA, GA>(c, q, qw, de + lo * 32, dl + lo, ds + lo, ef, phases, qe, ql); break;
-        case GB: st = range_prove_impl<GB, GA>(c, q, qw, de + lo * 32, dl + lo, ds + lo, ef, phases, qe, ql); break;
-        default: st = range_prove_impl<GC, GB>(c, q, qw, de + lo * 32, dl + lo, ds + lo, ef, phases, qe, ql); break;
-      }
+      st = with_group<GA, GB, GC>(group_for_bits(2 * p->n_bits), [&](auto G) { return range_prove_impl<G()>(c, q, qw, de + lo * 32, dl + lo, ds + lo, ef, phases, qe, ql); });
       if (st) break;
       HIPCHK(c, hipEventRecord(c->ev_pipe[2 * k + 1], c->stream));
       if (k + 1 < nb) st = pp.h2d(blocks[k + 1], blocks[k + 2], c->ev_pipe[2 * k + 2]);     // (under the kernels of block k)
@@ -192,13 +191,7 @@ static int32_t range_prove_entry(zkp_ctx* c, const char* name, const zkp_range_n
   if (!st && !dl) { st = ensure(c, c->scratch[S_ELEN], B); dl = (uint8_t*)c->scratch[S_ELEN].p; }
   if (!st && !ds) { st = ensure(c, c->scratch[S_STATUS], B); ds = (uint8_t*)c->scratch[S_STATUS].p; }
   if (!st && ef == 0) HIPCHK(c, hipMemsetAsync(ds, 0, B, c->stream));   // no rows: nothing can go wrong
-  if (!st) {
-    switch (group_for_bits(2 * p->n_bits)) {
-      case GA: st = range_prove_impl<GA, GA>(c, d, dw, de, dl, ds, ef, phases, dei, deli); break;
-      case GB: st = range_prove_impl<GB, GA>(c, d, dw, de, dl, ds, ef, phases, dei, deli); break;
-      default: st = range_prove_impl<GC, GB>(c, d, dw, de, dl, ds, ef, phases, dei, deli); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * p->n_bits), [&](auto G) { return range_prove_impl<G()>(c, d, dw, de, dl, ds, ef, phases, dei, deli); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 }
@@ -307,22 +300,6 @@ template <class FH, class FT> static int32_t range_split_run(zkp_ctx* c, int hea
   if (st_tail) { c->err = err_tail; return st_tail; }
   return ZKP_OK;
 }
-static zkp_range_ni_proofs range_split_slice(const zkp_range_ni_proofs& p, uint64_t lo, uint64_t count) {
-  const size_t kw = p.n_bits / 32, EF = p.error_factor;
-  zkp_range_ni_proofs q = p;
-  q.batch = count;
-  if (q.range) q.range += lo * kw;
-  if (q.ciphertext) q.ciphertext += lo * 2 * kw;
-  if (q.c1) q.c1 += lo * EF * 2 * kw;
-  if (q.c2) q.c2 += lo * EF * 2 * kw;
-  if (q.resp_kind) q.resp_kind += lo * EF;
-  if (q.resp_j) q.resp_j += lo * EF;
-  if (q.resp_w1) q.resp_w1 += lo * EF * kw;
-  if (q.resp_r1) q.resp_r1 += lo * EF * kw;
-  if (q.resp_w2) q.resp_w2 += lo * EF * kw;
-  if (q.resp_r2) q.resp_r2 += lo * EF * kw;
-  return q;
-}
 #define ZKP_RANGE_SPLIT_RESET(c) if (c) (c)->last_split = 0;
 #else
 #define ZKP_RANGE_SPLIT_RESET(c)
@@ -337,10 +314,8 @@ extern "C" int32_t zkp_range_ni_prove_batch(zkp_ctx* c, const zkp_range_ni_proof
     const size_t kw = p->n_bits / 32, EF = ZKP_SECURITY_PARAMETER;
     const uint64_t head = sp.head, tail = p->batch - head;
     auto part = [&](const LatEngine* e, zkp_ctx* ec, uint64_t lo, uint64_t count) {
-      const zkp_range_ni_proofs q = range_split_slice(*p, lo, count);
-      zkp_range_ni_witness qw = *w;
-      qw.x += lo * kw; qw.r += lo * kw;
-      qw.w1 += lo * EF * kw; qw.w2 += lo * EF * kw; qw.r1 += lo * EF * kw; qw.r2 += lo * EF * kw;
+      const zkp_range_ni_proofs q = range_slice(*p, EF, lo, count);
+      const zkp_range_ni_witness qw = range_witness_slice(*w, kw, EF, lo);
       uint8_t* qe = out_e ? out_e + lo * 32 : nullptr; uint8_t* ql = out_e_len ? out_e_len + lo : nullptr; uint8_t* qs = out_status ? out_status + lo : nullptr;
       if (!e) return range_prove_entry(ec, "zkp_range_ni_prove_batch", &q, &qw, ZKP_SECURITY_PARAMETER, 3, nullptr, nullptr, qe, ql, qs, flags);      // (the head on this very ctx)
       return e->p_zkp_range_ni_prove_batch(ec, &q, &qw, qe, ql, qs, flags);
@@ -352,7 +327,6 @@ extern "C" int32_t zkp_range_ni_prove_batch(zkp_ctx* c, const zkp_range_ni_proof
   return range_prove_entry(c, "zkp_range_ni_prove_batch", p, w, ZKP_SECURITY_PARAMETER, 3, nullptr, nullptr, out_e, out_e_len, out_status, flags);
 } ZKP_CATCH(c)
 // ---- seeded proving: the witness expanded on the device (kernels_sample.hpp) -----------------------------------------------------------
-enum { S_SAMPLE_THIRD = 44, S_SAMPLE_META = 45, S_SAMPLE_STATUS = 46, S_RESIDUE = 47 };
 enum { RANGE_SAMPLE_MAX_ATTEMPTS = 128 };
 
 // every pointer is device memory; `d` supplies n_bits, batch, n, n_stride and range; status is written for every proof
@@ -381,6 +355,16 @@ static int32_t range_sample_launch(zkp_ctx* c, const zkp_range_ni_proofs& d, uin
     default: hipLaunchKernelGGL(k_range_sample<8>, dim3(sample_blocks), dim3(256), 0, c->stream, a);
              hipLaunchKernelGGL(k_range_sample_fixup<8>, dim3(fix_blocks), dim3(256), 0, c->stream, a); break;
   }
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+
+// out_status (device, nullable) = / |= the status of the sampler that ran in front of the prove
+static int32_t seeded_status(zkp_ctx* c, uint8_t* ds, const uint8_t* sampler_status, uint64_t B, bool merge) {
+  if (!ds) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!merge) HIPCHK(c, hipMemsetAsync(ds, 0, B, c->stream));
+  hipLaunchKernelGGL(k_or_bytes, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, ds, sampler_status, B);
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
 }
@@ -449,11 +433,7 @@ extern "C" int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* c, const zkp_range_n
   uint8_t* sampler_status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p;
   if (!st) st = range_sample_launch(c, d, (uint32_t)EF, key, first_index, wit[0], wit[1], wit[2], wit[3], sampler_status);
   if (!st) st = zkp_range_ni_prove_batch(c, &d, &dw, de, dl, ds, ZKP_F_DEVICE_PTRS);      // (a null x or r is refused there: ZKP_EINVAL, after the sampler ran)
-  if (!st && ds) {
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_or_bytes, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, ds, (const uint8_t*)sampler_status, (uint64_t)B);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (!st) st = seeded_status(c, ds, sampler_status, B, true);
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -645,7 +625,7 @@ extern "C" int32_t zkp_range_ni_verify_batch(zkp_ctx* c, const zkp_range_ni_proo
   if (const RangeSplit sp = (p && out_verdict && range_args_ok(p)) ? range_split_plan(c, p, 2 * (uint64_t)p->error_factor, true) : RangeSplit(); sp.head && range_split_ready(c)) {
     const uint64_t head = sp.head, tail = p->batch - head;
     auto part = [&](const LatEngine* e, zkp_ctx* ec, uint64_t lo, uint64_t count) {
-      const zkp_range_ni_proofs q = range_split_slice(*p, lo, count);
+      const zkp_range_ni_proofs q = range_slice(*p, p->error_factor, lo, count);
       return e->p_zkp_range_ni_verify_batch(ec, &q, out_verdict + lo, flags);
     };
     return range_split_run(c, sp.head_engine, tail, [&](const LatEngine* e, zkp_ctx* ec) { return part(e, ec, 0, head); }, [&](const LatEngine* e, zkp_ctx* ec) { return part(e, ec, head, tail); });
@@ -690,19 +670,9 @@ static int32_t range_verify_entry(zkp_ctx* c, const zkp_range_ni_proofs* p, cons
     if (!st) st = pp.h2d(blocks[0], blocks[1], c->ev_pipe[0]);
     for (size_t k = 0; k < nb && !st; k++) {
       const size_t lo = blocks[k], hi = blocks[k + 1];
-      zkp_range_ni_proofs q = d;
-      q.batch = hi - lo;
-      if (p->n_stride) q.n = d.n + lo * kw;
-      q.range = d.range + lo * kw; q.ciphertext = d.ciphertext + lo * 2 * kw;
-      q.c1 = d.c1 + lo * EF * 2 * kw; q.c2 = d.c2 + lo * EF * 2 * kw;
-      q.resp_kind = d.resp_kind + lo * EF; q.resp_j = d.resp_j + lo * EF;
-      q.resp_w1 = d.resp_w1 + lo * EF * kw; q.resp_r1 = d.resp_r1 + lo * EF * kw; q.resp_w2 = d.resp_w2 + lo * EF * kw; q.resp_r2 = d.resp_r2 + lo * EF * kw;
+      const zkp_range_ni_proofs q = range_slice(d, EF, lo, hi - lo);
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pipe[2 * k], 0));
-      switch (group_for_bits(2 * p->n_bits)) {
-        case GA: st = range_verify_impl<GA>(c, q, dv + lo, dei ? dei + lo * 32 : nullptr, deli ? deli + lo : nullptr); break;
-        case GB: st = range_verify_impl<GB>(c, q, dv + lo, dei ? dei + lo * 32 : nullptr, deli ? deli + lo : nullptr); break;
-        default: st = range_verify_impl<GC>(c, q, dv + lo, dei ? dei + lo * 32 : nullptr, deli ? deli + lo : nullptr); break;
-      }
+      st = with_group<GA, GB, GC>(group_for_bits(2 * p->n_bits), [&](auto G) { return range_verify_impl<G()>(c, q, dv + lo, dei ? dei + lo * 32 : nullptr, deli ? deli + lo : nullptr); });
       if (st) break;
       HIPCHK(c, hipEventRecord(c->ev_pipe[2 * k + 1], c->stream));
       if (k + 1 < nb) st = pp.h2d(blocks[k + 1], blocks[k + 2], c->ev_pipe[2 * k + 2]);     // (under the kernels of block k)
@@ -724,13 +694,7 @@ static int32_t range_verify_entry(zkp_ctx* c, const zkp_range_ni_proofs* p, cons
   const uint8_t* dei = s.in(e_in, B * 32);
   const uint8_t* deli = s.in(e_len_in, B);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * p->n_bits)) {
-      case GA: st = range_verify_impl<GA>(c, d, dv, dei, deli); break;
-      case GB: st = range_verify_impl<GB>(c, d, dv, dei, deli); break;
-      default: st = range_verify_impl<GC>(c, d, dv, dei, deli); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * p->n_bits), [&](auto G) { return range_verify_impl<G()>(c, d, dv, dei, deli); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 }
@@ -802,20 +766,13 @@ extern "C" int32_t zkp_correct_key_ni_verify_batch(zkp_ctx* c, uint32_t n_bits, 
   // the salt is a short host byte string in both memory modes
   const uint8_t* dsalt = salt_len ? s.host_in(salt, salt_len) : nullptr;
   int32_t st = s.st;
-  if (!st) {
-    switch (n_group(n_bits)) {
-      case GA: st = ck_verify_impl<GA>(c, n_bits, batch, dn, dsg, dsalt, salt_len, dv); break;
-      default: st = ck_verify_impl<GB>(c, n_bits, batch, dn, dsg, dsalt, salt_len, dv); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return ck_verify_impl<G()>(c, n_bits, batch, dn, dsg, dsalt, salt_len, dv); });
   if (!st && (flags & ZKP_F_DEVICE_PTRS)) { if (hipStreamSynchronize(c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "sync"; } }   // salt staging is freed below
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
 
 // ---- CompositeDLogProof ------------------------------------------------------------------------
-enum { S_DL_T1 = 11, S_DL_T2 = 12, S_DL_T3 = 13, S_DL_GCD = 14 };
-
 static bool dlog_args_ok(uint32_t n_bits, uint32_t y_bits, uint64_t batch) {
   return (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && y_bits >= 544 && y_bits % 32 == 0 && y_bits <= n_bits && batch <= (1ull << 24);
 }
@@ -848,12 +805,7 @@ extern "C" int32_t zkp_dlog_prove_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y_
   uint32_t* dx = s.out(out_x, batch * kw);
   uint32_t* dy = s.out(out_y, batch * (y_bits / 32));
   int32_t st = s.st;
-  if (!st) {
-    switch (n_group(n_bits)) {
-      case GA: st = dlog_prove_impl<GA>(c, n_bits, y_bits, batch, dN, dg, dni, dsec, dr, dx, dy); break;
-      default: st = dlog_prove_impl<GB>(c, n_bits, y_bits, batch, dN, dg, dni, dsec, dr, dx, dy); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return dlog_prove_impl<G()>(c, n_bits, y_bits, batch, dN, dg, dni, dsec, dr, dx, dy); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -862,13 +814,12 @@ template <int G>
 static int32_t dlog_verify_impl(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* N, const uint32_t* g, const uint32_t* ni,
                                 const uint32_t* x, const uint32_t* y, uint8_t* verdict) {
   using CL = ConstLayout<G>;
-  using LL = LdsLayout<G>;
   const uint32_t kw = n_bits / 32;
   int32_t st;
   if ((st = run_setup<G>(c, N, kw, (int)kw, 0, batch, c->consts))) return st;
   if ((st = ensure(c, c->scratch[S_DLOG_E], batch * 32))) return st;
-  for (int k : {S_DL_T1, S_DL_T2, S_DL_T3}) if ((st = ensure(c, c->scratch[k], batch * kw * 4))) return st;
-  HIPCHK(c, hipMemsetAsync(c->scratch[S_DL_T3].p, 0, batch * kw * 4, c->stream));
+  for (int k : {S_TMP1, S_TMP2, S_TMP3}) if ((st = ensure(c, c->scratch[k], batch * kw * 4))) return st;
+  HIPCHK(c, hipMemsetAsync(c->scratch[S_TMP3].p, 0, batch * kw * 4, c->stream));
   // A call that leaves room on the GPU runs the verifier's pre-checks (N > 2^128 and the two GCDs: ~1 ms on one lane per
   // proof, needed only by the final compare) on the second stream, next to the exponentiations; the challenge stays here.
   const bool two = batch <= 16ull * (uint64_t)c->cus;      // (64 wavefronts of pre-checks at most)
@@ -887,13 +838,11 @@ static int32_t dlog_verify_impl(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, ui
   }
   hipLaunchKernelGGL(k_dlog_hash, hash_grid, dim3(DLOG_THREADS), hash_lds, c->stream, h);
   HIPCHK(c, hipGetLastError());
-  uint32_t *t1 = (uint32_t*)c->scratch[S_DL_T1].p, *t2 = (uint32_t*)c->scratch[S_DL_T2].p, *t3 = (uint32_t*)c->scratch[S_DL_T3].p;
+  uint32_t *t1 = (uint32_t*)c->scratch[S_TMP1].p, *t2 = (uint32_t*)c->scratch[S_TMP2].p, *t3 = (uint32_t*)c->scratch[S_TMP3].p;
   // ni^e (:81) and g^y (:82) side by side in one launch
   if ((st = modexp_multi<G>(c, batch, true, {{256, ni, (const uint32_t*)c->scratch[S_DLOG_E].p, 8, t1, (int)kw, 0},
                                              {y_bits, g, y, y_bits / 32, t2, (int)kw, 0}}))) return st;
-  ModmulArgs m{t1, t2, (const uint32_t*)c->consts.p, (uint64_t)CL::WORDS, t3, batch, (int)kw};                               // mod_mul :83
-  hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
-  HIPCHK(c, hipGetLastError());
+  if ((st = modmul_ctx<G>(c, c->consts, true, batch, t1, 0, t2, 0, t3, (int)kw))) return st;                                // mod_mul :83
   if (two) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); c->side_busy = false; }
   DlogCmpArgs q{x, t3, (const uint32_t*)c->consts.p, (uint64_t)CL::WORDS, CL::OFF_ST, kw, batch, verdict};
   hipLaunchKernelGGL(k_dlog_compare, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, q);
@@ -913,40 +862,27 @@ extern "C" int32_t zkp_dlog_verify_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y
   const uint32_t *dN = s.in(N, batch * kw), *dg = s.in(g, batch * kw), *dni = s.in(ni, batch * kw), *dx = s.in(x, batch * kw), *dy = s.in(y, batch * (y_bits / 32));
   uint8_t* dv = s.out(out_verdict, batch);
   int32_t st = s.st;
-  if (!st) {
-    switch (n_group(n_bits)) {
-      case GA: st = dlog_verify_impl<GA>(c, n_bits, y_bits, batch, dN, dg, dni, dx, dy, dv); break;
-      default: st = dlog_verify_impl<GB>(c, n_bits, y_bits, batch, dN, dg, dni, dx, dy, dv); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return dlog_verify_impl<G()>(c, n_bits, y_bits, batch, dN, dg, dni, dx, dy, dv); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
 
 // ---- ZeroProof / CiphertextProof (SURVEY §8(f) rank 1): compositions of the same kernels ---------------
-enum { S_SG_E = 0, S_SG_T1 = 11, S_SG_T2 = 12, S_SG_T3 = 13 };
-
 static bool sigma_args_ok(uint32_t n_bits, uint64_t batch, uint64_t n_stride) {
   return (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && batch <= (1ull << 24) && (n_stride == 0 || n_stride == n_bits / 32);
 }
 
+static int32_t sigma_hash(zkp_ctx* c, const SigmaHashArgs& h) {
+  hipLaunchKernelGGL(k_sigma_hash, dim3((unsigned)((h.batch + 255) / 256)), dim3(256), 0, c->stream, h);
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+// verdict = lhs == rhs, word for word (MALFORMED under a key the set-up rejected; the constants are c->consts)
 template <int G>
-static int32_t sigma_enc(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* m, int m_words,
-                         const uint32_t* r, int r_words, uint32_t* out) {
+static int32_t words_compare(zkp_ctx* c, bool per_item, uint64_t batch, const uint32_t* lhs, const uint32_t* rhs, uint32_t words, uint8_t* verdict) {
   using CL = ConstLayout<G>;
-  unsigned blocks = 0;
-  int32_t st;
-  if ((st = table_for<G>(c, k_enc<G, true>, batch, &blocks))) return st;
-  EncArgs a{};
-  a.n = n; a.n_stride = n_stride; a.consts = (const uint32_t*)c->consts.p; a.const_stride = n_stride ? (uint64_t)CL::WORDS : 0;
-  a.table = (uint32_t*)c->table.p; a.count = batch; a.n_bits = (int)n_bits; a.mode = 0;
-  a.m = m; a.r = r; a.out = out; a.items_per_key = n_stride ? 1 : batch; a.m_words = m_words; a.r_words = r_words;
-  if (n_stride == 0 && !pair_ladder<G>(c, a.count) && (st = build_schedule(c, n, n_bits, &a.sched))) return st;
-  if ((st = fresh_work_counter(c, &a.work_counter))) return st;
-  {
-    TimedRegion tr(c, batch);
-    launch_k_enc<G>(c, blocks, a);
-  }
+  WordsCmpArgs q{lhs, rhs, (const uint32_t*)c->consts.p, per_item ? (uint64_t)CL::WORDS : 0, CL::OFF_ST, words, batch, verdict};
+  hipLaunchKernelGGL(k_words_compare, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, q);
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
 }
@@ -956,52 +892,36 @@ template <int G>
 static int32_t sigma_prove_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
                                 const uint32_t* x, const uint32_t* r, const uint32_t* x_prime, const uint32_t* r_prime, uint32_t* out_z1,
                                 uint32_t* out_z, uint32_t* out_commit) {
-  using CL = ConstLayout<G>;
-  using LL = LdsLayout<G>;
   const uint32_t kw = n_bits / 32;
   const uint64_t nkeys = n_stride ? batch : 1;
   int32_t st;
   if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, nkeys, c->consts))) return st;
-  if ((st = sigma_enc<G>(c, n_bits, batch, n, n_stride, x_prime, x_prime ? 0 : -1, r_prime, 0, out_commit))) return st;
-  if ((st = ensure(c, c->scratch[S_SG_E], batch * 32))) return st;
-  if ((st = ensure(c, c->scratch[S_SG_T1], batch * 2 * kw * 4))) return st;
-  SigmaHashArgs h{n, n_stride, cc, out_commit, kw, batch, (uint32_t*)c->scratch[S_SG_E].p, x, x_prime, out_z1, kw + ZKP_Z1_EXTRA_LIMBS};
-  hipLaunchKernelGGL(k_sigma_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
-  HIPCHK(c, hipGetLastError());
-  uint32_t* t1 = (uint32_t*)c->scratch[S_SG_T1].p;
-  if ((st = modexp_core<G>(c, 256, batch, r, (const uint32_t*)c->scratch[S_SG_E].p, 8, n_stride != 0, t1, (int)kw, (int)(2 * kw)))) return st;   // r^e mod nn
-  ModmulArgs m{r_prime, t1, (const uint32_t*)c->consts.p, n_stride ? (uint64_t)CL::WORDS : 0, out_z, batch, (int)(2 * kw), (int)kw, (int)(2 * kw)};
-  hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  if ((st = enc_launch<G>(c, n_bits, batch, n, n_stride, x_prime, x_prime ? 0 : -1, r_prime, 0, out_commit))) return st;
+  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
+  if ((st = ensure(c, c->scratch[S_TMP1], batch * 2 * kw * 4))) return st;
+  if ((st = sigma_hash(c, {n, n_stride, cc, out_commit, kw, batch, (uint32_t*)c->scratch[S_E].p, x, x_prime, out_z1, kw + ZKP_Z1_EXTRA_LIMBS}))) return st;
+  uint32_t* t1 = (uint32_t*)c->scratch[S_TMP1].p;
+  if ((st = modexp_core<G>(c, 256, batch, r, (const uint32_t*)c->scratch[S_E].p, 8, n_stride != 0, t1, (int)kw, (int)(2 * kw)))) return st;   // r^e mod nn
+  return modmul_ctx<G>(c, c->consts, n_stride != 0, batch, r_prime, (int)kw, t1, (int)(2 * kw), out_z, (int)(2 * kw));
 }
 
 // Enc(z1, z) == c^e * commit mod n^2
 template <int G>
 static int32_t sigma_verify_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
                                  const uint32_t* z1, const uint32_t* z, const uint32_t* commit, uint8_t* verdict) {
-  using CL = ConstLayout<G>;
-  using LL = LdsLayout<G>;
   const uint32_t kw = n_bits / 32;
   const uint64_t nkeys = n_stride ? batch : 1;
   int32_t st;
   if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, nkeys, c->consts))) return st;
-  if ((st = ensure(c, c->scratch[S_SG_E], batch * 32))) return st;
-  for (int k : {S_SG_T1, S_SG_T2, S_SG_T3}) if ((st = ensure(c, c->scratch[k], batch * 2 * kw * 4))) return st;
-  uint32_t *t1 = (uint32_t*)c->scratch[S_SG_T1].p, *t2 = (uint32_t*)c->scratch[S_SG_T2].p, *t3 = (uint32_t*)c->scratch[S_SG_T3].p;
+  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
+  for (int k : {S_TMP1, S_TMP2, S_TMP3}) if ((st = ensure(c, c->scratch[k], batch * 2 * kw * 4))) return st;
+  uint32_t *t1 = (uint32_t*)c->scratch[S_TMP1].p, *t2 = (uint32_t*)c->scratch[S_TMP2].p, *t3 = (uint32_t*)c->scratch[S_TMP3].p;
   HIPCHK(c, hipMemsetAsync(t3, 0, batch * 2 * kw * 4, c->stream));
-  SigmaHashArgs h{n, n_stride, cc, commit, kw, batch, (uint32_t*)c->scratch[S_SG_E].p, nullptr, nullptr, nullptr, 0};
-  hipLaunchKernelGGL(k_sigma_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
-  HIPCHK(c, hipGetLastError());
-  if ((st = sigma_enc<G>(c, n_bits, batch, n, n_stride, z1, z1 ? (int)(kw + ZKP_Z1_EXTRA_LIMBS) : -1, z, (int)(2 * kw), t1))) return st;          // c_z
-  if ((st = modexp_core<G>(c, 256, batch, cc, (const uint32_t*)c->scratch[S_SG_E].p, 8, n_stride != 0, t2, (int)(2 * kw)))) return st;          // c^e  (Paillier::mul)
-  ModmulArgs m{t2, commit, (const uint32_t*)c->consts.p, n_stride ? (uint64_t)CL::WORDS : 0, t3, batch, (int)(2 * kw)};                         // Paillier::add
-  hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
-  HIPCHK(c, hipGetLastError());
-  WordsCmpArgs q{t1, t3, (const uint32_t*)c->consts.p, n_stride ? (uint64_t)CL::WORDS : 0, CL::OFF_ST, 2 * kw, batch, verdict};
-  hipLaunchKernelGGL(k_words_compare, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, q);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  if ((st = sigma_hash(c, {n, n_stride, cc, commit, kw, batch, (uint32_t*)c->scratch[S_E].p, nullptr, nullptr, nullptr, 0}))) return st;
+  if ((st = enc_launch<G>(c, n_bits, batch, n, n_stride, z1, z1 ? (int)(kw + ZKP_Z1_EXTRA_LIMBS) : -1, z, (int)(2 * kw), t1))) return st;          // c_z
+  if ((st = modexp_core<G>(c, 256, batch, cc, (const uint32_t*)c->scratch[S_E].p, 8, n_stride != 0, t2, (int)(2 * kw)))) return st;          // c^e  (Paillier::mul)
+  if ((st = modmul_ctx<G>(c, c->consts, n_stride != 0, batch, t2, 0, commit, 0, t3, (int)(2 * kw)))) return st;                                // Paillier::add
+  return words_compare<G>(c, n_stride != 0, batch, t1, t3, 2 * kw, verdict);
 }
 
 static int32_t sigma_prove_entry(zkp_ctx* c, const char* name, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -1025,13 +945,7 @@ static int32_t sigma_prove_entry(zkp_ctx* c, const char* name, uint32_t n_bits, 
   uint32_t* dz = s.out(out_z, batch * 2 * kw);
   uint32_t* dcm = s.out(out_commit, batch * 2 * kw);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = sigma_prove_impl<GA>(c, n_bits, batch, dn, n_stride, dc, dx, dr, dxp, drp, dz1, dz, dcm); break;
-      case GB: st = sigma_prove_impl<GB>(c, n_bits, batch, dn, n_stride, dc, dx, dr, dxp, drp, dz1, dz, dcm); break;
-      default: st = sigma_prove_impl<GC>(c, n_bits, batch, dn, n_stride, dc, dx, dr, dxp, drp, dz1, dz, dcm); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return sigma_prove_impl<G()>(c, n_bits, batch, dn, n_stride, dc, dx, dr, dxp, drp, dz1, dz, dcm); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 }
@@ -1051,13 +965,7 @@ static int32_t sigma_verify_entry(zkp_ctx* c, const char* name, uint32_t n_bits,
   const uint32_t* dcm = s.in(commit, batch * 2 * kw);
   uint8_t* dv = s.out(verdict, batch);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = sigma_verify_impl<GA>(c, n_bits, batch, dn, n_stride, dc, dz1, dz, dcm, dv); break;
-      case GB: st = sigma_verify_impl<GB>(c, n_bits, batch, dn, n_stride, dc, dz1, dz, dcm, dv); break;
-      default: st = sigma_verify_impl<GC>(c, n_bits, batch, dn, n_stride, dc, dz1, dz, dcm, dv); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return sigma_verify_impl<G()>(c, n_bits, batch, dn, n_stride, dc, dz1, dz, dcm, dv); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 }
@@ -1085,32 +993,20 @@ extern "C" int32_t zkp_ciphertext_proof_verify_batch(zkp_ctx* c, uint32_t n_bits
 } ZKP_CATCH(c)
 
 // ---- VerlinProof (verlin_proof.rs:35-165): the same kernels once more ------------------------------------
-enum { S_VL_T1 = 11, S_VL_T2 = 12, S_VL_T3 = 13, S_VL_T4 = 16, S_VL_T5 = 17 };
-
-template <int G>
-static int32_t modmul_dev(zkp_ctx* c, uint64_t batch, const uint32_t* a, const uint32_t* b, bool per_item_mod, uint32_t* out, int words) {
-  using CL = ConstLayout<G>;
-  using LL = LdsLayout<G>;
-  ModmulArgs m{a, b, (const uint32_t*)c->consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, out, batch, words};
-  hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
-}
-
 // out = c^y * c'^y' * Enc(y'', r_y) mod n^2   (gen_phi, verlin_proof.rs:138-165).  Uses scratch T1..T3.
 template <int G>
 static int32_t verlin_gen_phi(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc, const uint32_t* ccp,
                               const uint32_t* y, const uint32_t* yp, const uint32_t* ypp, int y_words, const uint32_t* ry, int ry_words, uint32_t* out) {
   const uint32_t kw = n_bits / 32;
-  uint32_t *t1 = (uint32_t*)c->scratch[S_VL_T1].p, *t2 = (uint32_t*)c->scratch[S_VL_T2].p, *t3 = (uint32_t*)c->scratch[S_VL_T3].p;
+  uint32_t *t1 = (uint32_t*)c->scratch[S_TMP1].p, *t2 = (uint32_t*)c->scratch[S_TMP2].p, *t3 = (uint32_t*)c->scratch[S_TMP3].p;
   int32_t st;
   const bool per = n_stride != 0;
   // Paillier::mul(c, y) and Paillier::mul(c', y'): one launch
   if ((st = modexp_multi<G>(c, batch, per, {{(uint32_t)y_words * 32, cc, y, (uint64_t)y_words, t1, (int)(2 * kw), 0},
                                             {(uint32_t)y_words * 32, ccp, yp, (uint64_t)y_words, t2, (int)(2 * kw), 0}}))) return st;
-  if ((st = sigma_enc<G>(c, n_bits, batch, n, n_stride, ypp, y_words, ry, ry_words, t3))) return st;                              // Enc(y'', r_y)
-  if ((st = modmul_dev<G>(c, batch, t1, t2, per, t1, (int)(2 * kw)))) return st;                                                  // Paillier::add
-  return modmul_dev<G>(c, batch, t1, t3, per, out, (int)(2 * kw));
+  if ((st = enc_launch<G>(c, n_bits, batch, n, n_stride, ypp, y_words, ry, ry_words, t3))) return st;                              // Enc(y'', r_y)
+  if ((st = modmul_ctx<G>(c, c->consts, per, batch, t1, 0, t2, 0, t1, (int)(2 * kw)))) return st;                                                  // Paillier::add
+  return modmul_ctx<G>(c, c->consts, per, batch, t1, 0, t3, 0, out, (int)(2 * kw));
 }
 
 template <int G>
@@ -1122,32 +1018,25 @@ static int32_t verlin_impl(zkp_ctx* c, bool prove, uint32_t n_bits, uint64_t bat
   const bool per = n_stride != 0;
   int32_t st;
   if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, nkeys, c->consts))) return st;
-  if ((st = ensure(c, c->scratch[S_SG_E], batch * 32))) return st;
-  for (int k : {S_VL_T1, S_VL_T2, S_VL_T3, S_VL_T4, S_VL_T5}) if ((st = ensure(c, c->scratch[k], batch * 2 * kw * 4))) return st;
-  uint32_t* e = (uint32_t*)c->scratch[S_SG_E].p;
-  uint32_t *t4 = (uint32_t*)c->scratch[S_VL_T4].p, *t5 = (uint32_t*)c->scratch[S_VL_T5].p;
+  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
+  for (int k : {S_TMP1, S_TMP2, S_TMP3, S_TMP4, S_TMP5}) if ((st = ensure(c, c->scratch[k], batch * 2 * kw * 4))) return st;
+  uint32_t* e = (uint32_t*)c->scratch[S_E].p;
+  uint32_t *t4 = (uint32_t*)c->scratch[S_TMP4].p, *t5 = (uint32_t*)c->scratch[S_TMP5].p;
   if (prove) {
     if ((st = verlin_gen_phi<G>(c, n_bits, batch, n, n_stride, cc, ccp, a[0], a[1], a[2], (int)kw, r_a, (int)kw, phi_a))) return st;
     VerlinHashArgs h{n, n_stride, {cc, ccp, phi_x, phi_a}, kw, batch, e, {x[0], x[1], x[2]}, {a[0], a[1], a[2]}, {z[0], z[1], z[2]}, zw};
     hipLaunchKernelGGL(k_verlin_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
     HIPCHK(c, hipGetLastError());
     if ((st = modexp_core<G>(c, 256, batch, r_x, e, 8, per, t4, (int)kw, (int)(2 * kw)))) return st;     // r_x^e mod nn (:88)
-    ModmulArgs m{t4, r_a, (const uint32_t*)c->consts.p, per ? (uint64_t)ConstLayout<G>::WORDS : 0, r_z, batch, (int)(2 * kw), (int)(2 * kw), (int)kw};
-    using LL = LdsLayout<G>;
-    hipLaunchKernelGGL(k_modmul<G>, dim3((unsigned)((batch + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK)), dim3(256), LL::BYTES_PER_BLOCK, c->stream, m);
-    HIPCHK(c, hipGetLastError());
-    return ZKP_OK;
+    return modmul_ctx<G>(c, c->consts, per, batch, t4, (int)(2 * kw), r_a, (int)kw, r_z, (int)(2 * kw));
   }
   VerlinHashArgs h{n, n_stride, {cc, ccp, phi_x, phi_a}, kw, batch, e, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, 0};
   hipLaunchKernelGGL(k_verlin_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
   HIPCHK(c, hipGetLastError());
   if ((st = verlin_gen_phi<G>(c, n_bits, batch, n, n_stride, cc, ccp, z[0], z[1], z[2], (int)zw, r_z, (int)(2 * kw), t4))) return st;    // phi_z
   if ((st = modexp_core<G>(c, 256, batch, phi_x, e, 8, per, t5, (int)(2 * kw)))) return st;                                              // phi_x^e
-  if ((st = modmul_dev<G>(c, batch, t5, phi_a, per, t5, (int)(2 * kw)))) return st;                                                       // * phi_a
-  WordsCmpArgs q{t4, t5, (const uint32_t*)c->consts.p, per ? (uint64_t)ConstLayout<G>::WORDS : 0, ConstLayout<G>::OFF_ST, 2 * kw, batch, verdict};
-  hipLaunchKernelGGL(k_words_compare, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, q);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  if ((st = modmul_ctx<G>(c, c->consts, per, batch, t5, 0, phi_a, 0, t5, (int)(2 * kw)))) return st;                                                       // * phi_a
+  return words_compare<G>(c, per, batch, t4, t5, 2 * kw, verdict);
 }
 
 extern "C" int32_t zkp_verlin_proof_prove_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -1172,13 +1061,7 @@ extern "C" int32_t zkp_verlin_proof_prove_batch(zkp_ctx* c, uint32_t n_bits, uin
   uint32_t* dz[3] = {s.out(out_z, batch * zw), s.out(out_z_prime, batch * zw), s.out(out_z_double_prime, batch * zw)};
   uint32_t* drz = s.out(out_r_z, batch * 2 * kw);
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = verlin_impl<GA>(c, true, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, drx, da, dra, dpa, dz, drz, nullptr); break;
-      case GB: st = verlin_impl<GB>(c, true, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, drx, da, dra, dpa, dz, drz, nullptr); break;
-      default: st = verlin_impl<GC>(c, true, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, drx, da, dra, dpa, dz, drz, nullptr); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return verlin_impl<G()>(c, true, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, drx, da, dra, dpa, dz, drz, nullptr); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -1203,13 +1086,7 @@ extern "C" int32_t zkp_verlin_proof_verify_batch(zkp_ctx* c, uint32_t n_bits, ui
   uint8_t* dv = s.out(out_verdict, batch);
   const uint32_t* none[3] = {nullptr, nullptr, nullptr};
   int32_t st = s.st;
-  if (!st) {
-    switch (group_for_bits(2 * n_bits)) {
-      case GA: st = verlin_impl<GA>(c, false, n_bits, batch, dn, n_stride, dc, dcp, dphx, none, nullptr, none, nullptr, (uint32_t*)dpa, dz, (uint32_t*)drz, dv); break;
-      case GB: st = verlin_impl<GB>(c, false, n_bits, batch, dn, n_stride, dc, dcp, dphx, none, nullptr, none, nullptr, (uint32_t*)dpa, dz, (uint32_t*)drz, dv); break;
-      default: st = verlin_impl<GC>(c, false, n_bits, batch, dn, n_stride, dc, dcp, dphx, none, nullptr, none, nullptr, (uint32_t*)dpa, dz, (uint32_t*)drz, dv); break;
-    }
-  }
+  if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return verlin_impl<G()>(c, false, n_bits, batch, dn, n_stride, dc, dcp, dphx, none, nullptr, none, nullptr, (uint32_t*)dpa, dz, (uint32_t*)drz, dv); });
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)

@@ -1,36 +1,60 @@
-// zkp_api_seeded.inc — seeded proving for ZeroProof, CiphertextProof, CorrectMessageProof and CompositeDLogProof: the nonces the reference's
-// prove draws itself are expanded on the device from a 32-byte seed (kernels_sample.hpp: k_nonce_sample; the stream is defined in
-// include/zkp_hip.h and DESIGN.md section 4), the nonce-input entry point runs on them as the device-pointer call it already knows, and
-// Stage::secret wipes them — with the staged copies of the caller's secrets — on every path out.
+// zkp_api_seeded.inc — seeded proving for ZeroProof, CiphertextProof, CorrectMessageProof, CompositeDLogProof, VerlinProof and MulProof: the
+// nonces the reference's prove draws itself are expanded on the device from a 32-byte seed (kernels_sample.hpp: k_nonce_sample; the two proofs
+// whose prove redraws a nonce until it is coprime to n — verlin_proof.rs:64-67, multiplication_proof.rs:148-154 — kernels_coprime.hpp:
+// k_nonce_coprime; the stream is defined in include/zkp_hip.h and DESIGN.md section 4), the nonce-input entry point runs on them as the
+// device-pointer call it already knows, and Stage::secret wipes them — with the staged copies of the caller's secrets — on every path out.
 
-static bool nonce_kind_ok(uint32_t kind) { return kind >= ZKP_SEEDED_KIND_ZERO && kind <= ZKP_SEEDED_KIND_DLOG; }
+// The nonce fields of every kind, in the order of out_field[]: how a field is drawn, its rows per proof (1, or one per simulated message:
+// K - 1), the slot of its first row and the words of a row (0: kw).  At most three BELOW fields and one RAW or COPRIME field per kind.
+enum NonceDraw : uint8_t { ND_NONE = 0, ND_BELOW /* sample_below(n) */, ND_RAW /* a power of two: the block's first words */, ND_COPRIME /* below n and coprime to it */ };
+struct NonceField { NonceDraw draw; bool per_sim; uint8_t slot0, words; };
+static constexpr NonceField NONCE_FIELDS[ZKP_SEEDED_KIND_MUL + 1][4] = {
+  {},
+  /* ZERO */            {{ND_BELOW, false, 0, 0}},
+  /* CIPHERTEXT */      {{ND_BELOW, false, 0, 0}, {ND_BELOW, false, 0, 0}},
+  /* CORRECT_MESSAGE */ {{ND_BELOW, false, 0, 0}, {ND_BELOW, false, 0, 0}, {ND_RAW, true, 1, 8}, {ND_BELOW, true, 1, 0}},
+  /* DLOG */            {{ND_RAW, false, 0, 16}},
+  /* VERLIN */          {{ND_BELOW, false, 0, 0}, {ND_BELOW, false, 0, 0}, {ND_BELOW, false, 0, 0}, {ND_COPRIME, false, 0, 0}},
+  /* MUL */             {{ND_BELOW, false, 0, 0}, {ND_COPRIME, false, 0, 0}},
+};
+static bool nonce_kind_ok(uint32_t kind) { return kind >= ZKP_SEEDED_KIND_ZERO && kind <= ZKP_SEEDED_KIND_MUL; }
+// does the kind have a coprime field (the kinds of zkp_nonce_sample_coprime_batch)?
+static bool nonce_kind_coprime(uint32_t kind) {
+  for (const NonceField& d : NONCE_FIELDS[kind]) if (d.draw == ND_COPRIME) return true;
+  return false;
+}
+static uint32_t nonce_field_rows(const NonceField& d, uint32_t K) { return d.draw == ND_NONE ? 0 : d.per_sim ? K - 1 : 1; }
+// the words of one proof's rows of field f, 0 where the kind has no such field
+static size_t nonce_field_words(uint32_t kind, uint32_t f, uint32_t kw, uint32_t K) {
+  const NonceField& d = NONCE_FIELDS[kind][f];
+  return (size_t)nonce_field_rows(d, K) * (d.words ? d.words : kw);
+}
 
 // every pointer is device memory; out[f] is the array of field f (null where the kind has none, or no slots); status is written for every proof
 static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, uint64_t B, uint32_t K, const uint32_t* n, uint64_t n_stride,
                                    const uint32_t* key, uint64_t first_index, uint32_t* const out[4], uint8_t* status) {
   int32_t st;
   if ((st = ensure(c, c->scratch[S_SAMPLE_META], B * 8))) return st;
+  const uint32_t kw = n_bits / 32;
   NonceSampleArgs a{};
   a.key = key; a.n = kind == ZKP_SEEDED_KIND_DLOG ? nullptr : n; a.n_stride = n_stride;
   a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p; a.status = status;
-  a.first_index = first_index; a.batch = B; a.kw = n_bits / 32; a.kind = kind; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
-  auto below = [&](uint32_t field, uint32_t per, uint32_t slot0) {
-    a.below[a.nbelow] = out[field]; a.below_field[a.nbelow] = field; a.below_per[a.nbelow] = per; a.below_slot0[a.nbelow] = slot0; a.nbelow++;
-  };
-  switch (kind) {
-    case ZKP_SEEDED_KIND_ZERO: below(0, 1, 0); break;
-    case ZKP_SEEDED_KIND_CIPHERTEXT: below(0, 1, 0); below(1, 1, 0); break;
-    case ZKP_SEEDED_KIND_CORRECT_MESSAGE:
-      below(0, 1, 0); below(1, 1, 0); below(3, K - 1, 1);
-      a.raw = out[2]; a.raw_field = 2; a.raw_per = K - 1; a.raw_slot0 = 1; a.raw_words = 8;
-      break;
-    default: a.raw = out[0]; a.raw_field = 0; a.raw_per = 1; a.raw_slot0 = 0; a.raw_words = 16; break;
+  a.first_index = first_index; a.batch = B; a.kw = kw; a.kind = kind; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
+  NonceDraw fourth = ND_NONE;          // the kind's RAW or COPRIME field; k_nonce_prep and k_nonce_sample do not read it, k_nonce_fixup zeroes
+  for (uint32_t f = 0; f < 4; f++) {   // it by (raw_per, raw_words): a COPRIME field is handed to it as one row of kw words per proof
+    const NonceField& d = NONCE_FIELDS[kind][f];
+    if (d.draw == ND_BELOW) {
+      a.below[a.nbelow] = out[f]; a.below_field[a.nbelow] = f; a.below_per[a.nbelow] = nonce_field_rows(d, K); a.below_slot0[a.nbelow] = d.slot0; a.nbelow++;
+    } else if (d.draw != ND_NONE) {
+      a.raw = out[f]; a.raw_field = f; a.raw_per = nonce_field_rows(d, K); a.raw_slot0 = d.slot0; a.raw_words = d.words ? d.words : kw;
+      fourth = d.draw;
+    }
   }
   hipLaunchKernelGGL(k_nonce_prep, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  const uint64_t G = a.kw / 16;
+  const uint64_t G = kw / 16;
   uint64_t tasks = 0, fix = 0;
-  for (uint32_t k = 0; k < a.nbelow; k++) { tasks += B * a.below_per[k]; fix = std::max<uint64_t>(fix, B * a.below_per[k] * a.kw / 4); }
+  for (uint32_t k = 0; k < a.nbelow; k++) { tasks += B * a.below_per[k]; fix = std::max<uint64_t>(fix, B * a.below_per[k] * kw / 4); }
   if (tasks) {
     const dim3 grid((unsigned)((tasks * G + 255) / 256));
     switch (G) {
@@ -40,11 +64,17 @@ static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, u
     }
     HIPCHK(c, hipGetLastError());
   }
-  if (const uint64_t raw = B * a.raw_per; raw && a.raw_words) {
-    hipLaunchKernelGGL(k_nonce_raw, dim3((unsigned)((raw + 255) / 256)), dim3(256), 0, c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    fix = std::max<uint64_t>(fix, raw * a.raw_words / 4);
+  const uint64_t rows = B * a.raw_per;
+  if (fourth == ND_RAW && rows) hipLaunchKernelGGL(k_nonce_raw, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, a);
+  if (fourth == ND_COPRIME) {
+    // As launch_modinv: latency-bound work with data-dependent trip counts, so small blocks — divergence stays among 16 lanes, several
+    // wavefronts share a compute unit, and two operands per lane are 16 KB of LDS per block at kw = 128.
+    const int lanes = 16;
+    NonceCoprimeArgs q{key, n, n_stride, a.meta, a.raw, status, first_index, B, kw, kind, a.raw_field, RANGE_SAMPLE_MAX_ATTEMPTS};
+    hipLaunchKernelGGL(k_nonce_coprime, dim3((unsigned)((B + lanes - 1) / lanes)), dim3(lanes), lanes * coprime_lds_words_per_lane(kw) * 4, c->stream, q);
   }
+  HIPCHK(c, hipGetLastError());
+  fix = std::max<uint64_t>(fix, rows * a.raw_words / 4);
   if (a.n && fix) {                      // (a kind without a bound has no MALFORMED case)
     hipLaunchKernelGGL(k_nonce_fixup, dim3((unsigned)((fix + 255) / 256)), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
@@ -52,32 +82,24 @@ static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, u
   return ZKP_OK;
 }
 
-// the words of one proof's rows of field f, 0 where the kind has no such field
-static size_t nonce_field_words(uint32_t kind, uint32_t f, uint32_t kw, uint32_t K) {
-  switch (kind) {
-    case ZKP_SEEDED_KIND_ZERO: return f == 0 ? kw : 0;
-    case ZKP_SEEDED_KIND_CIPHERTEXT: return f <= 1 ? kw : 0;
-    case ZKP_SEEDED_KIND_CORRECT_MESSAGE: return f <= 1 ? kw : f == 2 ? (size_t)(K - 1) * 8 : (size_t)(K - 1) * kw;
-    default: return f == 0 ? 16 : 0;
-  }
-}
-
 static bool nonce_args_ok(uint32_t kind, uint32_t n_bits, uint64_t batch, uint32_t K, uint64_t n_stride) {
   if (!nonce_kind_ok(kind) || !sigma_args_ok(n_bits, batch, n_stride)) return false;
   return kind != ZKP_SEEDED_KIND_CORRECT_MESSAGE || (K >= 1 && K <= 65536 && batch * K <= (1ull << 24));
 }
 
-extern "C" int32_t zkp_nonce_sample_batch(zkp_ctx* c, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, uint32_t num_messages, const uint32_t* n,
-                                          uint64_t n_stride, const uint8_t* seed, uint64_t first_index, uint32_t** out_field,
-                                          uint8_t* out_status, uint32_t flags) try {
+// zkp_nonce_sample_batch (the kinds without a coprime field) and zkp_nonce_sample_coprime_batch (those with one)
+static int32_t nonce_sample_entry(zkp_ctx* c, const char* name, bool coprime, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, uint32_t num_messages,
+                                  const uint32_t* n, uint64_t n_stride, const uint8_t* seed, uint64_t first_index, uint32_t** out_field, uint8_t* out_status,
+                                  uint32_t flags) {
   if (!c) return ZKP_EINVAL;
-  bool ok = nonce_args_ok(proof_kind, n_bits, batch, num_messages, n_stride) && seed && out_field && (n || proof_kind == ZKP_SEEDED_KIND_DLOG);
+  bool ok = nonce_args_ok(proof_kind, n_bits, batch, num_messages, n_stride) && nonce_kind_coprime(proof_kind) == coprime && seed && out_field &&
+            (n || proof_kind == ZKP_SEEDED_KIND_DLOG);
   const uint32_t kw = n_bits / 32, K = proof_kind == ZKP_SEEDED_KIND_CORRECT_MESSAGE ? num_messages : 1;
   uintptr_t align = 0;
   for (uint32_t f = 0; ok && f < 4; f++)
     if (nonce_field_words(proof_kind, f, kw, K)) { ok = out_field[f] != nullptr; align |= (uintptr_t)out_field[f]; }
-  if (!ok) { c->err = "zkp_nonce_sample_batch: invalid argument"; return ZKP_EINVAL; }
-  if ((flags & ZKP_F_DEVICE_PTRS) && (align & 15u)) { c->err = "zkp_nonce_sample_batch: device output arrays must be 16-byte aligned"; return ZKP_EINVAL; }
+  if (!ok) { c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL; }
+  if ((flags & ZKP_F_DEVICE_PTRS) && (align & 15u)) { c->err = std::string(name) + ": device output arrays must be 16-byte aligned"; return ZKP_EINVAL; }
   if (batch == 0) return ZKP_OK;
   HIPCHK(c, hipSetDevice(c->device));
   Stage s(c, flags);
@@ -96,10 +118,23 @@ extern "C" int32_t zkp_nonce_sample_batch(zkp_ctx* c, uint32_t proof_kind, uint3
   if (!st) st = nonce_sample_launch(c, proof_kind, n_bits, batch, K, dn, n_stride, key, first_index, out, ds);
   const int32_t fin = s.finish();
   return st ? st : fin;
+}
+
+extern "C" int32_t zkp_nonce_sample_batch(zkp_ctx* c, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, uint32_t num_messages, const uint32_t* n,
+                                          uint64_t n_stride, const uint8_t* seed, uint64_t first_index, uint32_t** out_field,
+                                          uint8_t* out_status, uint32_t flags) try {
+  return nonce_sample_entry(c, "zkp_nonce_sample_batch", false, proof_kind, n_bits, batch, num_messages, n, n_stride, seed, first_index, out_field, out_status, flags);
 } ZKP_CATCH(c)
 
-// What the four seeded proves share: the seed and the nonce blocks of a call, all of them secret.  The sampler's status goes to the ctx's
-// own array: Zero, Ciphertext and DLog copy it out (their nonce-input calls have no status), CorrectMessage ORs it into the prove's.
+extern "C" int32_t zkp_nonce_sample_coprime_batch(zkp_ctx* c, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                                  const uint8_t* seed, uint64_t first_index, uint32_t** out_field, uint8_t* out_status,
+                                                  uint32_t flags) try {
+  return nonce_sample_entry(c, "zkp_nonce_sample_coprime_batch", true, proof_kind, n_bits, batch, 1, n, n_stride, seed, first_index, out_field, out_status, flags);
+} ZKP_CATCH(c)
+
+// What the six seeded proves share: the seed and the nonce blocks of a call, all of them secret.  The sampler's status goes to the ctx's
+// own array: Zero, Ciphertext, DLog and Verlin copy it out (their nonce-input calls have no status), CorrectMessage and Mul OR it into the prove's
+// (seeded_status, zkp_api_proofs.inc).
 struct SeededNonces {
   const uint32_t* key = nullptr;
   uint32_t* f[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -117,16 +152,6 @@ struct SeededNonces {
     st = nonce_sample_launch(c, kind, n_bits, B, K, dn, n_stride, key, first_index, f, status);
   }
 };
-
-// out_status (device, nullable) = / |= the sampler's status
-static int32_t seeded_status(zkp_ctx* c, uint8_t* ds, const SeededNonces& q, uint64_t B, bool merge) {
-  if (!ds) return ZKP_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!merge) HIPCHK(c, hipMemsetAsync(ds, 0, B, c->stream));
-  hipLaunchKernelGGL(k_or_bytes, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, ds, (const uint8_t*)q.status, B);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
-}
 
 static int32_t sigma_prove_seeded(zkp_ctx* c, const char* name, bool with_x, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
                                   const uint32_t* cc, const uint32_t* x, const uint32_t* r, const uint8_t* seed, uint64_t first_index, uint32_t* out_z1,
@@ -150,7 +175,7 @@ static int32_t sigma_prove_seeded(zkp_ctx* c, const char* name, bool with_x, uin
   int32_t st = q.st;      // (a null c, x, r or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
   if (!st) st = with_x ? zkp_ciphertext_proof_prove_batch(c, n_bits, batch, dn, n_stride, dc, dx, dr, q.f[0], q.f[1], dz1, dz, dcm, ZKP_F_DEVICE_PTRS)
                        : zkp_zero_proof_prove_batch(c, n_bits, batch, dn, n_stride, dc, dr, q.f[0], dz, dcm, ZKP_F_DEVICE_PTRS);
-  if (!st) st = seeded_status(c, ds, q, batch, false);
+  if (!st) st = seeded_status(c, ds, q.status, batch, false);
   const int32_t fin = s.finish();
   return st ? st : fin;
 }
@@ -190,7 +215,7 @@ extern "C" int32_t zkp_correct_message_prove_seeded_batch(zkp_ctx* c, uint32_t n
   SeededNonces q(c, s, ZKP_SEEDED_KIND_CORRECT_MESSAGE, n_bits, batch, K, dn, n_stride, seed, first_index);
   int32_t st = q.st;      // (a null list, message or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
   if (!st) st = zkp_correct_message_prove_batch(c, n_bits, batch, K, dn, n_stride, dv, dm, q.f[0], q.f[2], q.f[3], q.f[1], dct, dev, dzv, dav, ds, ZKP_F_DEVICE_PTRS);
-  if (!st) st = seeded_status(c, ds, q, batch, true);
+  if (!st) st = seeded_status(c, ds, q.status, batch, true);
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
@@ -212,7 +237,62 @@ extern "C" int32_t zkp_dlog_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint
   SeededNonces q(c, s, ZKP_SEEDED_KIND_DLOG, n_bits, batch, 1, nullptr, 0, seed, first_index);
   int32_t st = q.st;      // (a null statement, secret or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
   if (!st) st = zkp_dlog_prove_batch(c, n_bits, y_bits, batch, dN, dg, dni, dsec, q.f[0], dx, dy, ZKP_F_DEVICE_PTRS);
-  if (!st) st = seeded_status(c, ds, q, batch, false);
+  if (!st) st = seeded_status(c, ds, q.status, batch, false);
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_verlin_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
+                                                       const uint32_t* c_prime, const uint32_t* phi_x, const uint32_t* x, const uint32_t* x_prime,
+                                                       const uint32_t* x_double_prime, const uint32_t* r_x, const uint8_t* seed, uint64_t first_index,
+                                                       uint32_t* out_phi_a, uint32_t* out_z, uint32_t* out_z_prime, uint32_t* out_z_double_prime,
+                                                       uint32_t* out_r_z, uint8_t* out_status, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (!sigma_args_ok(n_bits, batch, n_stride) || !n || !seed) { c->err = "zkp_verlin_proof_prove_seeded_batch: invalid argument"; return ZKP_EINVAL; }
+  if (batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = n_bits / 32, zw = kw + ZKP_Z1_EXTRA_LIMBS;
+  Stage s(c, flags);
+  const uint32_t* dn = s.in(n, n_stride ? batch * kw : kw);
+  const uint32_t *dc = s.in(cc, batch * 2 * kw), *dcp = s.in(c_prime, batch * 2 * kw), *dphx = s.in(phi_x, batch * 2 * kw);
+  const uint32_t *dx = s.in(x, batch * kw), *dxp = s.in(x_prime, batch * kw), *dxpp = s.in(x_double_prime, batch * kw), *drx = s.in(r_x, batch * kw);
+  if (!s.dev) for (const uint32_t* p : {dx, dxp, dxpp, drx}) s.secret(p, batch * kw * 4);
+  uint32_t* dpa = s.out(out_phi_a, batch * 2 * kw);
+  uint32_t *dz = s.out(out_z, batch * zw), *dzp = s.out(out_z_prime, batch * zw), *dzpp = s.out(out_z_double_prime, batch * zw);
+  uint32_t* drz = s.out(out_r_z, batch * 2 * kw);
+  uint8_t* ds = s.out(out_status, batch);
+  SeededNonces q(c, s, ZKP_SEEDED_KIND_VERLIN, n_bits, batch, 1, dn, n_stride, seed, first_index);
+  int32_t st = q.st;      // (a null statement, witness or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
+  if (!st) st = zkp_verlin_proof_prove_batch(c, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, dxp, dxpp, drx, q.f[0], q.f[1], q.f[2], q.f[3], dpa, dz, dzp,
+                                             dzpp, drz, ZKP_F_DEVICE_PTRS);
+  if (!st) st = seeded_status(c, ds, q.status, batch, false);
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* e_a,
+                                                    const uint32_t* e_b, const uint32_t* e_c, const uint32_t* a, const uint32_t* b, const uint32_t* r_a,
+                                                    const uint32_t* r_b, const uint32_t* r_c, const uint8_t* seed, uint64_t first_index, uint32_t* out_f,
+                                                    uint32_t* out_z1, uint32_t* out_z2, uint32_t* out_e_d, uint32_t* out_e_db, uint8_t* out_status,
+                                                    uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (!sigma_args_ok(n_bits, batch, n_stride) || !n || !seed) { c->err = "zkp_mul_proof_prove_seeded_batch: invalid argument"; return ZKP_EINVAL; }
+  if (batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = n_bits / 32;
+  Stage s(c, flags);
+  const uint32_t* dn = s.in(n, n_stride ? batch * kw : kw);
+  const uint32_t *dea = s.in(e_a, batch * 2 * kw), *deb = s.in(e_b, batch * 2 * kw), *dec = s.in(e_c, batch * 2 * kw);
+  const uint32_t *da = s.in(a, batch * kw), *db = s.in(b, batch * kw), *dra = s.in(r_a, batch * kw), *drb = s.in(r_b, batch * kw), *drc = s.in(r_c, batch * kw);
+  if (!s.dev) for (const uint32_t* p : {da, db, dra, drb, drc}) s.secret(p, batch * kw * 4);
+  uint32_t* df = s.out(out_f, batch * kw);
+  uint32_t *dz1 = s.out(out_z1, batch * 2 * kw), *dz2 = s.out(out_z2, batch * 2 * kw), *ded = s.out(out_e_d, batch * 2 * kw), *dedb = s.out(out_e_db, batch * 2 * kw);
+  uint8_t* ds = s.out(out_status, batch);
+  SeededNonces q(c, s, ZKP_SEEDED_KIND_MUL, n_bits, batch, 1, dn, n_stride, seed, first_index);
+  int32_t st = q.st;      // (a null statement, witness or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
+  if (!st) st = zkp_mul_proof_prove_batch(c, n_bits, batch, dn, n_stride, dea, deb, dec, da, db, dra, drb, drc, q.f[0], q.f[1], df, dz1, dz2, ded, dedb, ds,
+                                          ZKP_F_DEVICE_PTRS);
+  if (!st) st = seeded_status(c, ds, q.status, batch, true);
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
