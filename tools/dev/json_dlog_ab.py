@@ -9,7 +9,7 @@ factorisation), g random below N, ni = g^-s mod N, the proofs made by zkp_dlog_p
 the two writers, decimal form.  Every verdict must be ACCEPT on all three routes.  B's split (upload, statements, proofs, domain check and
 verify) comes from HIP events on the ctx stream (zkp_diag_last_json_scan_ms).  Appends one JSON line to profiles/json_reader/dlog_ab.jsonl
 (or --out).
-Usage: python tools/dev/json_dlog_ab.py [--pairs 65536] [--rounds 2]"""
+Usage: python tools/dev/json_dlog_ab.py [--pairs 65536] [--rounds 2] [--label TEXT]"""
 import argparse
 import importlib
 import json
@@ -43,6 +43,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=65536)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "json_reader", "dlog_ab.jsonl"))
+    ap.add_argument("--label", default=None, help="written into the record (which build this run measured)")
     a = ap.parse_args()
     import torch
     n_bits, y_bits, B = 2048, 768, a.pairs
@@ -118,6 +119,8 @@ def main():
                warm_up="one A, one B and one C before the timed rounds", a_ms=A, a_read_ms=Ar, b_ms=Bs, b_split=Bsplit, c_ms=Cs, a_median=float(np.median(A)),
                b_median=float(np.median(Bs)), c_median=float(np.median(Cs)), fast_docs=scan[0], fallback_docs=scan[1], same_statuses_and_verdicts=same,
                accepted=int((va == 1).sum()), sclk_mhz=sclk_mhz())
+    if a.label is not None:
+        rec["label"] = a.label
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "a") as f:

@@ -5,7 +5,7 @@
 The documents are the writer's (zkp_json_write_range_proof_ni_batch on a seeded, device-resident prove result).  B's split (upload, scan,
 convert, verify) comes from HIP events on the ctx stream (zkp_diag_last_json_scan_ms).  Appends one JSON line to
 profiles/json_reader/ab.jsonl (or --out).
-Usage: python tools/dev/json_reader_ab.py [--proofs 4096] [--rounds 2]"""
+Usage: python tools/dev/json_reader_ab.py [--proofs 4096] [--rounds 2] [--label TEXT]"""
 import argparse
 import ctypes as C
 import hashlib
@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--proofs", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "json_reader", "ab.jsonl"))
+    ap.add_argument("--label", default=None, help="written into the record (which build this run measured)")
     a = ap.parse_args()
     import torch
     n_bits, kw, B, EF = 2048, 64, a.proofs, 128
@@ -101,6 +102,8 @@ def main():
     rec = dict(proofs=B, n_bits=n_bits, error_factor=EF, text_bytes=int(off[-1]), order="A B C " * a.rounds, warm_up="one A, one B and one C before the timed rounds",
                a_ms=A, a_read_ms=Ar, b_ms=Bs, b_split=Bsplit, c_ms=Cs, a_median=float(np.median(A)), b_median=float(np.median(Bs)), c_median=float(np.median(Cs)),
                fast_docs=scan[0], fallback_docs=scan[1], same_statuses_and_verdicts=same, accepted=int((va == 1).sum()), sclk_mhz=sclk_mhz())
+    if a.label is not None:
+        rec["label"] = a.label
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "a") as f:

@@ -8,7 +8,7 @@ Keys and roots are the benchmark's distinct-key material (bench.py configs[3]: r
 proof is rejected, and k_ck_check does the same work whatever the verdict); the documents are the writer's
 (zkp_json_write_correct_key_proof_batch on the device-resident roots).  B's split (upload, scan, convert, verify) comes from HIP events on
 the ctx stream (zkp_diag_last_json_scan_ms).  Appends one JSON line to profiles/json_reader/ck_ab.jsonl (or --out).
-Usage: python tools/dev/json_reader_ck_ab.py [--keys 65536] [--rounds 2]"""
+Usage: python tools/dev/json_reader_ck_ab.py [--keys 65536] [--rounds 2] [--label TEXT]"""
 import argparse
 import importlib
 import json
@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--keys", type=int, default=65536)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "json_reader", "ck_ab.jsonl"))
+    ap.add_argument("--label", default=None, help="written into the record (which build this run measured)")
     a = ap.parse_args()
     import torch
     n_bits, kw, B, M2 = 2048, 64, a.keys, 11
@@ -93,6 +94,8 @@ def main():
     rec = dict(keys=B, n_bits=n_bits, text_bytes=int(off[-1]), order="A B C " * a.rounds, warm_up="one A, one B and one C before the timed rounds",
                a_ms=A, a_read_ms=Ar, b_ms=Bs, b_split=Bsplit, c_ms=Cs, a_median=float(np.median(A)), b_median=float(np.median(Bs)), c_median=float(np.median(Cs)),
                fast_docs=scan[0], fallback_docs=scan[1], same_statuses_and_verdicts=same, accepted=int((va == 1).sum()), sclk_mhz=sclk_mhz())
+    if a.label is not None:
+        rec["label"] = a.label
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "a") as f:

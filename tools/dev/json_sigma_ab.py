@@ -9,7 +9,7 @@ The pairs are honest proofs under the reference's 2048-bit fixture key, one key 
 written from there by zkp_json_write_sigma_batch, decimal form.  Every verdict must be ACCEPT on all three routes.  A's split (upload, statements,
 proofs, domain check and verify) comes from HIP events on the ctx stream (zkp_diag_last_json_scan_ms).  Appends one JSON line per proof type to
 profiles/json_reader/sigma_ab.jsonl (or --out).
-Usage: python tools/dev/json_sigma_ab.py [--pairs 4096] [--rounds 3]"""
+Usage: python tools/dev/json_sigma_ab.py [--pairs 4096] [--rounds 3] [--label TEXT]"""
 import argparse
 import ctypes as C
 import importlib
@@ -103,6 +103,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "json_reader", "sigma_ab.jsonl"))
+    ap.add_argument("--label", default=None, help="written into the record (which build this run measured)")
     a = ap.parse_args()
     import torch
     n_bits, B = 2048, a.pairs
@@ -165,6 +166,8 @@ def main():
                    warm_up="one A, one B and one C before the timed rounds", a_ms=A, a_split=Asplit, b_ms=Bs, c_ms=Cs, c_read_ms=Cr, a_median=am, b_median=bm,
                    c_median=cm, device_text_cost_ms=am - bm, host_text_cost_ms=cm - bm, fast_docs=scan[0], fallback_docs=scan[1], same_statuses_and_verdicts=same,
                    accepted=int((va == 1).sum()), sclk_mhz=sclk_mhz())
+        if a.label is not None:
+            rec["label"] = a.label
         print(json.dumps(rec), flush=True)
         with open(a.out, "a") as f:
             f.write(json.dumps(rec) + "\n")

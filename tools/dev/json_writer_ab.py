@@ -4,7 +4,7 @@
      (bytes.join over slices of the padded rows, one thread);
   B  zkp_json_write_range_proof_ni_batch reading the same device-resident batch: sizing call + writing call.
 Both end with the same bytes in host memory (checked).  Writes one JSON line to profiles/json_writer/ab.jsonl (or --out).
-Usage: python tools/dev/json_writer_ab.py [--proofs 4096] [--rounds 2]"""
+Usage: python tools/dev/json_writer_ab.py [--proofs 4096] [--rounds 2] [--label TEXT]"""
 import argparse
 import hashlib
 import importlib
@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--proofs", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "json_writer", "ab.jsonl"))
+    ap.add_argument("--label", default=None, help="written into the record (which build this run measured)")
     a = ap.parse_args()
     import torch
     n_bits, kw, B, EF = 2048, 64, a.proofs, 128
@@ -98,6 +99,8 @@ def main():
                a_ms=A, a_download_and_convert_ms=Ac, a_assembly="python bytes.join, one thread", b_ms=Bs, a_median=float(np.median(A)), b_median=float(np.median(Bs)),
                a_spread=float(max(A) - min(A)), b_spread=float(max(Bs) - min(Bs)), same_bytes=bool(same), prove_seeded_device_ms=prove_ms,
                b_share_of_1575_ms_prove=float(np.median(Bs)) / 1575.0)
+    if a.label is not None:
+        rec["label"] = a.label
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "a") as f:

@@ -120,4 +120,22 @@ __global__ void __launch_bounds__(SERDE_LANES) k_bin2dec(const uint32_t* __restr
   out_len[idx] = pitch - pos;
 }
 
+// ---- the documents' statuses (zkp_api_serde.inc launches both)
+// pass 0: a number the fixed width cannot carry (negative, too wide) sends its document to the caller's host path; pass 1 (a later
+// launch on the same stream, so it always wins): a string that is no integer at all is a serde error
+__global__ void k_mark_docs(const uint8_t* __restrict__ item_status, const uint32_t* __restrict__ item_doc, uint64_t count, uint8_t* __restrict__ doc_status, int pass) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const uint8_t st = item_status[i];
+  if (pass == 0 && (st == ZKP_DEC_NEGATIVE || st == ZKP_DEC_OVERFLOW) && doc_status[item_doc[i]] == ZKP_DOC_OK) doc_status[item_doc[i]] = ZKP_DOC_HOST_PATH;
+  if (pass == 1 && st == ZKP_DEC_INVALID) doc_status[item_doc[i]] = ZKP_DOC_INVALID;
+}
+
+// "Its rows here are zero": whatever was converted of a document that ends up ZKP_DOC_INVALID or ZKP_DOC_HOST_PATH is cleared again, so
+// that a caller who ignores the status never verifies a half-read proof
+template <class T> __global__ void k_clear_failed_docs(const uint8_t* __restrict__ doc_status, T* __restrict__ dst, uint64_t units_per_doc, uint64_t docs) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < docs * units_per_doc && doc_status[i / units_per_doc] != ZKP_DOC_OK) dst[i] = 0;
+}
+
 }  // namespace zkp

@@ -13,9 +13,9 @@
 //   CompositeDLogProof {"x":X,"y":X}                       heads only: the head phase, then `}` and the document's end
 //   DLogStatement      {"N":X,"g":X,"ni":X}
 //   ZeroStatement .. MulProof                              heads only, up to five of three widths, a statement's first one behind `{"ek":{"n":`
-// Which heads a kind has — literal, destination, limbs, digit bound, text form — is the table w_doc_spec() (kernels_serde_write.hpp); the host
+// Which heads a kind has — literal, destination, limbs, digit bound, text form — is the table w_doc_spec() (serde_docs.hpp); the host
 // copies the kind's rows into ScanJob::head, and the head phase below is a loop over them that knows no document kind.
-// A document that differs in ONE byte from this is marked `fall back` and nothing else: the host tokeniser (zkp_api_serde.inc) reads it and
+// A document that differs in ONE byte from this is marked `fall back` and nothing else: the host tokeniser (json_host.hpp) reads it and
 // decides its status.  So the scanner never has an opinion about a document it does not fully understand, and for one it understands the
 // only thing left open is whether every number fits its field — k_dec2bin's overflow status, the host reader's ZKP_DOC_HOST_PATH.
 //

@@ -343,6 +343,9 @@ static int32_t ensure(zkp_ctx* c, DevBuf& b, size_t bytes) {
 // on), nullptr otherwise; cleared on the stream when the buffer has changed hands since the tag was written
 static int32_t setup_tag(zkp_ctx* c, DevBuf& b, uint64_t count, uint32_t** out);
 
+// the Paillier key sizes (and DLog modulus sizes) every entry point takes
+static bool key_bits_ok(uint32_t n_bits) { return n_bits == 1024 || n_bits == 2048 || n_bits == 4096; }
+
 // ---- staging of host buffers --------------------------------------------------------------
 struct Stage {
   zkp_ctx* c;
@@ -1467,7 +1470,7 @@ extern "C" int32_t zkp_paillier_enc_batch(zkp_ctx* c, uint32_t n_bits, uint64_t 
   ZKP_ROUTE_ENC(c, count, 2 * n_bits, n_stride == 0, zkp_paillier_enc_batch, n_bits, count, n, n_stride, m, r, out_c, flags)
   if (!c) return ZKP_EINVAL;
   if (count == 0) return ZKP_OK;
-  if (!n || !m || !r || !out_c || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || count > (1ull << 40) || (n_stride && n_stride < n_bits / 32)) { c->err = "zkp_paillier_enc_batch: invalid argument"; return ZKP_EINVAL; }
+  if (!n || !m || !r || !out_c || !key_bits_ok(n_bits) || count > (1ull << 40) || (n_stride && n_stride < n_bits / 32)) { c->err = "zkp_paillier_enc_batch: invalid argument"; return ZKP_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t kw = n_bits / 32;
   Stage s(c, flags);
@@ -1496,7 +1499,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
   if (!c) return ZKP_EINVAL;
   if (count == 0) return ZKP_OK;
   const bool product = mulc_a || mulc_b;
-  if (!n || !m || !r || !out_ok || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || count > (1ull << 40) || (n_stride && n_stride != n_bits / 32) ||
+  if (!n || !m || !r || !out_ok || !key_bits_ok(n_bits) || count > (1ull << 40) || (n_stride && n_stride != n_bits / 32) ||
       (product ? (!mulc_a || !mulc_b || expected) : !expected)) { c->err = "zkp_paillier_enc_check_batch: invalid argument"; return ZKP_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t kw = n_bits / 32;

@@ -4,7 +4,7 @@
 enum : unsigned { RA_RANGE = 1, RA_CIPHERTEXT = 2, RA_PAIRS = 4, RA_RESP = 8 };
 static bool range_args_ok(const zkp_range_ni_proofs* p, unsigned need = RA_RANGE | RA_CIPHERTEXT | RA_PAIRS | RA_RESP) {
   if (!p) return false;
-  if (p->n_bits != 1024 && p->n_bits != 2048 && p->n_bits != 4096) return false;
+  if (!key_bits_ok(p->n_bits)) return false;
   if (p->batch > (1ull << 24) || p->error_factor > 256) return false;   // challenge has at most 256 bits
   if (p->n_stride != 0 && p->n_stride != p->n_bits / 32) return false;
   if (p->batch == 0) return true;
@@ -756,7 +756,7 @@ extern "C" int32_t zkp_correct_key_ni_verify_batch(zkp_ctx* c, uint32_t n_bits, 
   ZKP_ROUTE(c, batch * ZKP_CORRECT_KEY_M2, n_bits, zkp_correct_key_ni_verify_batch, n_bits, batch, n, sigma, salt, salt_len, out_verdict, flags)
   if (!c) return ZKP_EINVAL;
   if (batch == 0) return ZKP_OK;
-  if (!n || !sigma || !out_verdict || (salt_len && !salt) || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || batch > (1ull << 26)) { c->err = "zkp_correct_key_ni_verify_batch: invalid argument"; return ZKP_EINVAL; }
+  if (!n || !sigma || !out_verdict || (salt_len && !salt) || !key_bits_ok(n_bits) || batch > (1ull << 26)) { c->err = "zkp_correct_key_ni_verify_batch: invalid argument"; return ZKP_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t kw = n_bits / 32;
   Stage s(c, flags);
@@ -774,7 +774,7 @@ extern "C" int32_t zkp_correct_key_ni_verify_batch(zkp_ctx* c, uint32_t n_bits, 
 
 // ---- CompositeDLogProof ------------------------------------------------------------------------
 static bool dlog_args_ok(uint32_t n_bits, uint32_t y_bits, uint64_t batch) {
-  return (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && y_bits >= 544 && y_bits % 32 == 0 && y_bits <= n_bits && batch <= (1ull << 24);
+  return key_bits_ok(n_bits) && y_bits >= 544 && y_bits % 32 == 0 && y_bits <= n_bits && batch <= (1ull << 24);
 }
 
 template <int G>
@@ -869,7 +869,7 @@ extern "C" int32_t zkp_dlog_verify_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y
 
 // ---- ZeroProof / CiphertextProof (SURVEY §8(f) rank 1): compositions of the same kernels ---------------
 static bool sigma_args_ok(uint32_t n_bits, uint64_t batch, uint64_t n_stride) {
-  return (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && batch <= (1ull << 24) && (n_stride == 0 || n_stride == n_bits / 32);
+  return key_bits_ok(n_bits) && batch <= (1ull << 24) && (n_stride == 0 || n_stride == n_bits / 32);
 }
 
 static int32_t sigma_hash(zkp_ctx* c, const SigmaHashArgs& h) {

@@ -3,7 +3,25 @@
 // (text offset, length, destination) per big integer.  GPU: k_dec2bin converts every decimal string straight into the
 // SoA limb arrays of the batch.
 
-#include <thread>
+#include "json_host.hpp"
+
+namespace {
+// bigint_forms = ZKP_BIGINT_FORMS(key, bare): the text form of ek.n, the text form of every other un-annotated integer, and whether both are forms
+struct BigintForms { uint32_t key, bare; bool ok; };
+BigintForms decode_forms(uint32_t forms) {
+  const uint32_t key = (forms >> 4) & 15u, bare = forms & 15u;
+  return {key, bare, !(forms >> 8) && key <= ZKP_BIGINT_BYTES && bare <= ZKP_BIGINT_BYTES};
+}
+
+// The end of a call: the first error goes into the stage (nothing is copied back after one), the outputs are delivered and the blocks returned;
+// sync: the stream is idle when the call returns, in device-pointer mode too (host vectors of the call were read by copies on it)
+int32_t call_end(zkp_ctx* c, Stage& s, int32_t st, bool sync = false) {
+  if (st && !s.st) s.st = st;
+  const int32_t fin = s.finish();
+  if (sync && hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
+  return st ? st : fin;
+}
+}  // namespace
 
 extern "C" uint32_t zkp_decimal_pitch(uint32_t words) { return (uint32_t)((uint64_t)words * 32 * 30103 / 100000 + 2); }
 
@@ -40,8 +58,7 @@ extern "C" int32_t zkp_decimal_to_limbs_batch(zkp_ctx* c, const char* text, uint
   uint8_t* ds = s.out(out_status, count);
   int32_t st = s.st;
   if (!st) st = launch_dec2bin(c, dt, di, count, dd, ds, max_words);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return call_end(c, s, st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_limbs_to_decimal_batch(zkp_ctx* c, const uint32_t* src, uint64_t src_stride, uint32_t words, uint64_t count, char* out_text,
@@ -62,231 +79,93 @@ extern "C" int32_t zkp_limbs_to_decimal_batch(zkp_ctx* c, const uint32_t* src, u
                        src_stride, (int)words, count, dt, pitch, dl);
     if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_bin2dec launch"; }
   }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return call_end(c, s, st);
 } ZKP_CATCH(c)
 
-// ---- a JSON reader for the three document shapes, as tolerant as serde_json + the derived Deserialize impls are:
-// object fields in any order, unknown fields skipped (whatever their value), white space anywhere, strings with escapes
-// (\uXXXX included: serde_json hands the decoded text to the bigint visitors, serialize.rs:24-27,62-66); duplicate or
-// missing fields, more than one variant key in a Response, and wrong value types are errors, as they are for serde.
 namespace {
-constexpr uint64_t EXTRA_FLAG = 1ull << 63;     // text_off of a string that had escapes: offset into the thread's decoded-copy buffer
-
-struct JCur {
-  const char* t; uint64_t p, end; bool ok = true;
-  std::string* extra = nullptr;                 // decoded copies of value strings that contain escapes (per thread)
-  void ws() { while (p < end && (t[p] == ' ' || t[p] == '\n' || t[p] == '\t' || t[p] == '\r')) p++; }
-  bool eat(char ch) { ws(); if (p < end && t[p] == ch) { p++; return true; } return false; }
-  bool expect(char ch) { if (!eat(ch)) ok = false; return ok; }
-  // raw string token: content span and whether it holds a backslash
-  bool raw_str(uint64_t* off, uint32_t* len, bool* esc) {
-    ws();
-    if (p >= end || t[p] != '"') return ok = false;
-    const uint64_t b = ++p;
-    *esc = false;
-    while (p < end && t[p] != '"') {
-      if ((unsigned char)t[p] < 0x20) return ok = false;           // control characters must be escaped
-      if (t[p] == '\\') { *esc = true; p++; if (p >= end) return ok = false; }
-      p++;
-    }
-    if (p >= end) return ok = false;
-    *off = b; *len = (uint32_t)(p - b); p++;
-    return true;
-  }
-  static int hexv(char ch) { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1; }
-  bool decode(uint64_t off, uint32_t len, std::string* out) {
-    for (uint64_t i = off; i < off + len; i++) {
-      if (t[i] != '\\') { out->push_back(t[i]); continue; }
-      const char e = t[++i];
-      switch (e) {
-        case '"': out->push_back('"'); break;   case '\\': out->push_back('\\'); break;   case '/': out->push_back('/'); break;
-        case 'b': out->push_back('\b'); break;  case 'f': out->push_back('\f'); break;    case 'n': out->push_back('\n'); break;
-        case 'r': out->push_back('\r'); break;  case 't': out->push_back('\t'); break;
-        case 'u': {
-          if (i + 4 >= off + len) return ok = false;
-          int v = 0;
-          for (int k = 1; k <= 4; k++) { const int h = hexv(t[i + k]); if (h < 0) return ok = false; v = v * 16 + h; }
-          i += 4;
-          if (v >= 0xD800 && v <= 0xDFFF) return ok = false;        // surrogates: never part of a number or a field name here
-          if (v < 0x80) out->push_back((char)v);
-          else if (v < 0x800) { out->push_back((char)(0xC0 | (v >> 6))); out->push_back((char)(0x80 | (v & 63))); }
-          else { out->push_back((char)(0xE0 | (v >> 12))); out->push_back((char)(0x80 | ((v >> 6) & 63))); out->push_back((char)(0x80 | (v & 63))); }
-          break;
-        }
-        default: return ok = false;
-      }
-    }
-    return true;
-  }
-  // a string VALUE to be converted on the GPU: (text offset, length); strings with escapes are decoded into *extra
-  bool str(uint64_t* off, uint32_t* len) {
-    uint64_t o; uint32_t l; bool esc;
-    if (!raw_str(&o, &l, &esc)) return false;
-    if (!esc) { *off = o; *len = l; return true; }
-    const size_t at = extra->size();
-    if (!decode(o, l, extra)) return false;
-    *off = EXTRA_FLAG | at; *len = (uint32_t)(extra->size() - at);
-    return true;
-  }
-  bool name(std::string* out) {                  // a field name, decoded
-    uint64_t o; uint32_t l; bool esc;
-    out->clear();
-    if (!raw_str(&o, &l, &esc)) return false;
-    if (esc) return decode(o, l, out);
-    out->assign(t + o, l);
-    return true;
-  }
-  bool uint(uint64_t* v) {
-    ws();
-    if (p >= end || t[p] < '0' || t[p] > '9') return ok = false;
-    if (t[p] == '0' && p + 1 < end && t[p + 1] >= '0' && t[p + 1] <= '9') return ok = false;    // JSON has no leading zeros
-    uint64_t x = 0; int nd = 0;
-    while (p < end && t[p] >= '0' && t[p] <= '9') { x = x * 10 + (uint64_t)(t[p] - '0'); p++; if (++nd > 18) return ok = false; }
-    if (p < end && (t[p] == '.' || t[p] == 'e' || t[p] == 'E')) return ok = false;                // not an integer
-    *v = x;
-    return true;
-  }
-  // any JSON value, skipped (the value of an unknown field)
-  bool skip_value(int depth = 0) {
-    if (depth > 64) return ok = false;
-    ws();
-    if (p >= end) return ok = false;
-    const char ch = t[p];
-    if (ch == '"') { uint64_t o; uint32_t l; bool e; return raw_str(&o, &l, &e); }
-    if (ch == '{' || ch == '[') {
-      const char close = ch == '{' ? '}' : ']';
-      p++;
-      if (eat(close)) return true;
-      do {
-        if (ch == '{') { uint64_t o; uint32_t l; bool e; if (!raw_str(&o, &l, &e) || !expect(':')) return false; }
-        if (!skip_value(depth + 1)) return false;
-      } while (eat(','));
-      return expect(close);
-    }
-    auto lit = [&](const char* w) { const size_t n = strlen(w); if (p + n <= end && memcmp(t + p, w, n) == 0) { p += n; return true; } return false; };
-    if (lit("true") || lit("false") || lit("null")) return true;
-    if (ch == '-' || (ch >= '0' && ch <= '9')) {
-      if (ch == '-') p++;
-      const uint64_t b0 = p;
-      while (p < end && ((t[p] >= '0' && t[p] <= '9') || t[p] == '.' || t[p] == 'e' || t[p] == 'E' || t[p] == '+' || t[p] == '-')) p++;
-      return p > b0 ? true : (ok = false);
-    }
-    return ok = false;
-  }
-  // {"name": value, ...}: f(name) consumes the value and returns true, or returns false for a field it does not know (skipped)
-  template <class F> bool object(F f) {
-    if (!expect('{')) return false;
-    if (eat('}')) return ok;
-    std::string nm;
-    do {
-      if (!name(&nm) || !expect(':')) return false;
-      if (!f(nm)) { if (!ok || !skip_value()) return ok = false; }
-    } while (ok && eat(','));
-    return expect('}');
-  }
-  bool done() { ws(); return ok && p == end; }
-};
-
-struct ItemList { std::vector<zkp_dec_item> items; std::vector<uint32_t> doc; };
-
-// per-thread document loop
-template <class F> void for_docs(uint64_t B, F f) {
-  unsigned nt = std::thread::hardware_concurrency();
-  nt = std::max(1u, std::min(nt, 16u));
-  if (B < 64) nt = 1;
-  std::vector<std::thread> th;
-  for (unsigned k = 0; k < nt; k++) th.emplace_back([=]() { for (uint64_t b = B * k / nt; b < B * (k + 1) / nt; b++) f(b, k); });
-  for (auto& t : th) t.join();
-}
-
-// upload the text span covered by the documents; returns device pointer biased so that absolute offsets work
-// The decoded copies of strings that had escapes (one buffer per parser thread) follow the span on the device: thread k's
-// buffer starts at text offset extra_base[k].
-struct TextSpan { char* d = nullptr; uint64_t lo = 0, hi = 0; std::vector<uint64_t> extra_base; };
-int32_t upload_text(zkp_ctx* c, const char* text, const uint64_t* off, const uint64_t* len, uint64_t B, const std::vector<std::string>& extras, TextSpan* o) {
-  uint64_t lo = ~0ull, hi = 0;
-  for (uint64_t b = 0; b < B; b++) { lo = std::min(lo, off[b]); hi = std::max(hi, off[b] + len[b]); }
-  o->lo = lo; o->hi = hi;
-  uint64_t extra_total = 0;
-  for (auto& e : extras) { o->extra_base.push_back(hi + extra_total); extra_total += e.size(); }
-  HIPCHK(c, hipMalloc((void**)&o->d, std::max<uint64_t>(hi - lo + extra_total, 16)));
-  HIPCHK(c, hipMemcpyAsync(o->d, text + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
-  for (size_t k = 0; k < extras.size(); k++)
-    if (!extras[k].empty()) HIPCHK(c, hipMemcpyAsync(o->d + (o->extra_base[k] - lo), extras[k].data(), extras[k].size(), hipMemcpyHostToDevice, c->stream));
-  return ZKP_OK;
-}
-
-// pass 0: a number the fixed width cannot carry (negative, too wide) sends its document to the caller's host path; pass 1 (a later
-// launch on the same stream, so it always wins): a string that is no integer at all is a serde error
-__global__ void k_mark_docs(const uint8_t* __restrict__ item_status, const uint32_t* __restrict__ item_doc, uint64_t count, uint8_t* __restrict__ doc_status, int pass) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= count) return;
-  const uint8_t st = item_status[i];
-  if (pass == 0 && (st == ZKP_DEC_NEGATIVE || st == ZKP_DEC_OVERFLOW) && doc_status[item_doc[i]] == ZKP_DOC_OK) doc_status[item_doc[i]] = ZKP_DOC_HOST_PATH;
-  if (pass == 1 && st == ZKP_DEC_INVALID) doc_status[item_doc[i]] = ZKP_DOC_INVALID;
-}
-
-// "Its rows here are zero": whatever was converted of a document that ends up ZKP_DOC_INVALID or ZKP_DOC_HOST_PATH is cleared again, so
-// that a caller who ignores the status never verifies a half-read proof
-template <class T> __global__ void k_clear_failed_docs(const uint8_t* __restrict__ doc_status, T* __restrict__ dst, uint64_t units_per_doc, uint64_t docs) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < docs * units_per_doc && doc_status[i / units_per_doc] != ZKP_DOC_OK) dst[i] = 0;
-}
-template <class T> static void clear_failed_docs(zkp_ctx* c, const uint8_t* dstat, T* dst, uint64_t units_per_doc, uint64_t docs) {
+template <class T> void clear_failed_docs(zkp_ctx* c, const uint8_t* dstat, T* dst, uint64_t units_per_doc, uint64_t docs) {
   const uint64_t total = docs * units_per_doc;
   if (total) hipLaunchKernelGGL(k_clear_failed_docs<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, dstat, dst, units_per_doc, docs);
 }
 
-// convert one target array's item lists (one per thread) on the GPU and fold the item statuses into the documents'
-int32_t convert_lists(zkp_ctx* c, const TextSpan& ts, std::vector<ItemList>& lists, uint32_t* dst, uint32_t max_words, uint8_t* d_doc_status,
-                      std::vector<void*>& to_free) {
+// The documents' text as the flags-0 readers upload it: byte `a` of the caller's text is d[a - lo].  The decoded copies of strings that had
+// escapes (one buffer per parser thread) follow the span on the device: thread k's buffer starts at text offset extra_base[k].
+struct HostText { char* d; uint64_t lo; uint64_t extra_base[READER_THREADS]; };
+
+// convert target array q's item lists (one per thread) on the GPU and fold the item statuses into the documents'
+int32_t convert_lists(zkp_ctx* c, Stage& s, const HostText& ht, const std::vector<ReaderThread>& threads, int q, uint32_t* dst, uint32_t max_words, uint8_t* d_doc_status) {
   size_t total = 0;
-  for (auto& l : lists) total += l.items.size();
+  for (auto& t : threads) total += t.L[q].items.size();
   if (total == 0) return ZKP_OK;
   std::vector<zkp_dec_item> items; items.reserve(total);
   std::vector<uint32_t> doc; doc.reserve(total);
-  for (size_t k = 0; k < lists.size(); k++) {
-    for (auto it : lists[k].items) {
-      if (it.text_off & EXTRA_FLAG) it.text_off = ts.extra_base[k] + (it.text_off & ~EXTRA_FLAG);
-      it.text_off -= ts.lo;
+  for (size_t k = 0; k < threads.size(); k++) {
+    for (auto it : threads[k].L[q].items) {
+      if (it.text_off & EXTRA_FLAG) it.text_off = ht.extra_base[k] + (it.text_off & ~EXTRA_FLAG);
+      it.text_off -= ht.lo;
       items.push_back(it);
     }
-    doc.insert(doc.end(), lists[k].doc.begin(), lists[k].doc.end());
+    doc.insert(doc.end(), threads[k].L[q].doc.begin(), threads[k].L[q].doc.end());
   }
-  zkp_dec_item* di = nullptr; uint32_t* dd = nullptr; uint8_t* dst_status = nullptr;
-  HIPCHK(c, hipMalloc((void**)&di, total * sizeof(zkp_dec_item))); to_free.push_back(di);
-  HIPCHK(c, hipMalloc((void**)&dd, total * 4)); to_free.push_back(dd);
-  HIPCHK(c, hipMalloc((void**)&dst_status, total)); to_free.push_back(dst_status);
-  HIPCHK(c, hipMemcpyAsync(di, items.data(), total * sizeof(zkp_dec_item), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dd, doc.data(), total * 4, hipMemcpyHostToDevice, c->stream));
+  const zkp_dec_item* di = s.host_in(items.data(), total);
+  const uint32_t* dd = s.host_in(doc.data(), total);
+  uint8_t* item_status = (uint8_t*)s.take(total);
+  if (s.st) return s.st;
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the host vectors go out of scope
-  int32_t st = launch_dec2bin(c, ts.d, di, total, dst, dst_status, max_words);
+  int32_t st = launch_dec2bin(c, ht.d, di, total, dst, item_status, max_words);
   if (st) return st;
   for (int pass = 0; pass < 2; pass++)
-    hipLaunchKernelGGL(k_mark_docs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, dst_status, dd, total, d_doc_status, pass);
+    hipLaunchKernelGGL(k_mark_docs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)item_status, dd, total, d_doc_status, pass);
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
+}
+
+// The flags-0 reader of the annotated types, on host pointers: tok(b, thread, kinds, js) tokenises document b (json_host.hpp) and returns its
+// status; every number it lists is converted on the GPU into tgt[q] ([B][per_doc] numbers of `words` limbs, q < ntgt), the item statuses are
+// folded into the documents', and (clear) whatever was converted of a document that is not ZKP_DOC_OK is zero again.  resp_kind, resp_j: the
+// [B][per_doc] row variants of a Proof, or null.  Every device block is the stage's: whatever ends the call returns them to the ctx.
+template <class Tok>
+int32_t json_read_host(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, int ntgt, uint32_t* const* tgt, uint32_t words, uint64_t per_doc,
+                       uint8_t* resp_kind, uint8_t* resp_j, bool clear, uint8_t* out_status, Tok tok) {
+  const uint64_t rows = B * per_doc;
+  std::vector<uint8_t> status(B, 0), kinds(resp_kind ? rows : 0, 0), js(resp_kind ? rows : 0, 0);
+  std::vector<ReaderThread> threads(READER_THREADS);
+  for_docs(B, [&](uint64_t b, unsigned k) { status[b] = tok(b, threads[k], kinds.data(), js.data()); });
+  Stage s(c, 0);
+  uint8_t* dstat = s.out(out_status, B);
+  uint32_t* dt[4] = {};
+  for (int q = 0; q < ntgt; q++) dt[q] = s.out(tgt[q], rows * words);       // (zeroed: a document that lists no number for a row leaves it so)
+  uint8_t* dkind = s.out(resp_kind, rows);
+  uint8_t* dj = s.out(resp_j, rows);
+  HostText ht{};
+  uint64_t hi = 0, extra_total = 0;
+  ht.lo = ~0ull;
+  for (uint64_t b = 0; b < B; b++) { ht.lo = std::min(ht.lo, doc_off[b]); hi = std::max(hi, doc_off[b] + doc_len[b]); }
+  for (unsigned k = 0; k < READER_THREADS; k++) { ht.extra_base[k] = hi + extra_total; extra_total += threads[k].extra.size(); }
+  ht.d = (char*)s.take(std::max<uint64_t>(hi - ht.lo + extra_total, 16));
+  int32_t st = s.st;
+  auto h2d = [&](void* dst, const void* src, uint64_t bytes) {
+    if (!st && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "H2D copy"; }
+  };
+  h2d(ht.d, text + ht.lo, hi - ht.lo);
+  for (unsigned k = 0; k < READER_THREADS; k++) h2d(ht.d + (ht.extra_base[k] - ht.lo), threads[k].extra.data(), threads[k].extra.size());
+  h2d(dstat, status.data(), B);
+  if (resp_kind) { h2d(dkind, kinds.data(), rows); h2d(dj, js.data(), rows); }
+  for (int q = 0; q < ntgt && !st; q++) st = convert_lists(c, s, ht, threads, q, dt[q], words, dstat);
+  if (!st && clear) {
+    for (int q = 0; q < ntgt; q++) clear_failed_docs(c, dstat, dt[q], per_doc * words, B);
+    if (resp_kind) { clear_failed_docs(c, dstat, dkind, per_doc, B); clear_failed_docs(c, dstat, dj, per_doc, B); }
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_clear_failed_docs"; }
+  }
+  return call_end(c, s, st, true);
 }
 }  // namespace
 
 // With ZKP_F_DEVICE_PTRS every reader goes through the device scanner (json_scan, further down): the text is uploaded once and tokenised
 // there, and only the documents it leaves come back to the reader's flags-0 path, as a sub-batch.
 namespace {
-// the text of a call that scans twice (zkp_dlog_verify_json_batch), uploaded by the caller: byte `a` of the caller's text is d[a - lo], and
-// 16 bytes '0' follow the span
-struct ScanText { char* d; uint64_t lo, span; };
-int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits = 0, const ScanText* pre = nullptr, uint32_t* const* head_dst = nullptr);
 int32_t json_scan_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                        const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* out_status, uint32_t y_bits = 0, uint32_t* const* head_dst = nullptr) {
-  Stage s(c, ZKP_F_DEVICE_PTRS);
-  int32_t st = json_scan(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, sigma, out_status, y_bits, nullptr, head_dst);
-  if (st && !s.st) s.st = st;
-  const int32_t fin = s.finish();
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-  return st ? st : fin;
-}
+                        const zkp_range_ni_proofs& d, uint32_t* const* head_dst, uint8_t* out_status, uint32_t y_bits = 0);
 }  // namespace
 
 // kind: 0 = EncryptedPairs -> c1, c2; 1 = Proof -> resp_*
@@ -296,143 +175,17 @@ static int32_t json_range_entry(zkp_ctx* c, const char* name, int kind, const ch
   if (!p || p->batch == 0) return ZKP_OK;
   const uint64_t B = p->batch, EF = p->error_factor;
   const uint32_t kw = p->n_bits / 32;
-  if (!text || !doc_off || !doc_len || !out_status || (p->n_bits != 1024 && p->n_bits != 2048 && p->n_bits != 4096) || EF == 0 || EF > 256 || B > (1ull << 24) ||
+  if (!text || !doc_off || !doc_len || !out_status || !key_bits_ok(p->n_bits) || EF == 0 || EF > 256 || B > (1ull << 24) ||
       (kind == 0 && (!p->c1 || !p->c2)) || (kind == 1 && (!p->resp_kind || !p->resp_j || !p->resp_w1 || !p->resp_r1 || !p->resp_w2 || !p->resp_r2))) {
     c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL;
   }
   HIPCHK(c, hipSetDevice(c->device));
   if (flags & ZKP_F_DEVICE_PTRS) return json_scan_entry(c, name, kind == 0 ? W_DOC_PAIRS : W_DOC_PROOF, text, doc_off, doc_len, 0, *p, nullptr, out_status);
-  const uint64_t rows = B * EF;
-  std::vector<uint8_t> status(B, 0), kinds, js;
-  if (kind == 1) { kinds.assign(rows, 0); js.assign(rows, 0); }
-  const unsigned NT = 16;
-  std::vector<ItemList> L[4];
-  for (auto& l : L) l.resize(NT);
-  std::vector<std::string> extras(NT);
-  for_docs(B, [&](uint64_t b, unsigned k) {
-    JCur j{text, doc_off[b], doc_off[b] + doc_len[b]};
-    j.extra = &extras[k];
-    const size_t extra_mark = extras[k].size();
-    bool other_count = false;       // a well-formed document with another number of rows: a valid value of the reference's type, outside this batch layout
-    auto push = [&](int which, uint64_t row, uint32_t words) {
-      uint64_t o; uint32_t l;
-      if (!j.str(&o, &l)) return;
-      L[which][k].items.push_back({o, row * words, l, words});
-      L[which][k].doc.push_back((uint32_t)b);
-    };
-    const size_t mark[4] = {L[0][k].items.size(), L[1][k].items.size(), L[2][k].items.size(), L[3][k].items.size()};
-    auto skip_str = [&]() { uint64_t o; uint32_t l; bool e; j.raw_str(&o, &l, &e); };
-    if (kind == 0) {
-      // {"c1":[...],"c2":[...]}  (range_proof.rs:32-39), fields in any order
-      bool seen[2] = {false, false};
-      j.object([&](const std::string& nm) {
-        const int which = nm == "c1" ? 0 : nm == "c2" ? 1 : -1;
-        if (which < 0) return false;
-        if (seen[which]) { j.ok = false; return true; }                    // duplicate field
-        seen[which] = true;
-        j.expect('[');
-        uint64_t cnt = 0;
-        if (j.ok && !j.eat(']')) {
-          do { if (cnt < EF) push(which, b * EF + cnt, 2 * kw); else skip_str(); cnt++; } while (j.ok && j.eat(','));
-          j.expect(']');
-        }
-        if (cnt != EF) other_count = true;
-        return true;
-      });
-      if (!seen[0] || !seen[1]) j.ok = false;                               // missing field
-    } else {
-      // [{"Open":{"w1":..,"r1":..,"w2":..,"r2":..}},{"Mask":{"j":1,"masked_x":..,"masked_r":..}},...]  (range_proof.rs:53-81):
-      // externally tagged enum = an object with exactly one key, the variant name
-      j.expect('[');
-      uint64_t cnt = 0;
-      if (j.ok && !j.eat(']')) {
-        do {
-          const uint64_t row = b * EF + (cnt < EF ? cnt : EF - 1);
-          int variants = 0;
-          j.object([&](const std::string& vn) {
-            if (++variants > 1) { j.ok = false; return true; }
-            if (vn == "Open") {
-              static const char* names[4] = {"w1", "r1", "w2", "r2"};
-              unsigned seen = 0;
-              j.object([&](const std::string& nm) {
-                int f = -1;
-                for (int q = 0; q < 4; q++) if (nm == names[q]) f = q;
-                if (f < 0) return false;
-                if (seen & (1u << f)) { j.ok = false; return true; }
-                seen |= 1u << f;
-                if (cnt < EF) push(f, row, kw); else skip_str();
-                return true;
-              });
-              if (seen != 15u) j.ok = false;
-              if (cnt < EF) { kinds[row] = ZKP_RESP_OPEN; js[row] = 0; }
-            } else if (vn == "Mask") {
-              uint64_t jv = 0;
-              unsigned seen = 0;
-              j.object([&](const std::string& nm) {
-                const int f = nm == "j" ? 0 : nm == "masked_x" ? 1 : nm == "masked_r" ? 2 : -1;
-                if (f < 0) return false;
-                if (seen & (1u << f)) { j.ok = false; return true; }
-                seen |= 1u << f;
-                if (f == 0) { j.uint(&jv); if (jv > 255) j.ok = false; }
-                else if (cnt < EF) push(f - 1, row, kw);
-                else skip_str();
-                return true;
-              });
-              if (seen != 7u) j.ok = false;
-              if (cnt < EF) { kinds[row] = ZKP_RESP_MASK; js[row] = (uint8_t)jv; }
-            } else {
-              j.ok = false;                                                 // unknown variant
-            }
-            return true;
-          });
-          if (variants != 1) j.ok = false;
-          cnt++;
-        } while (j.ok && j.eat(','));
-        j.expect(']');
-      }
-      if (cnt != EF) other_count = true;
-    }
-    if (!j.done() || other_count) {
-      status[b] = !j.done() ? ZKP_DOC_INVALID : ZKP_DOC_HOST_PATH;
-      for (int q = 0; q < 4; q++) { L[q][k].items.resize(mark[q]); L[q][k].doc.resize(mark[q]); }   // nothing of a malformed document is converted
-      extras[k].resize(extra_mark);
-      if (kind == 1) for (uint64_t i = 0; i < EF; i++) { kinds[b * EF + i] = 0; js[b * EF + i] = 0; }
-    }
-  });
-  Stage s(c, flags);
-  uint8_t* dstat = s.out(out_status, B);
-  uint32_t* tgt[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint8_t *dkind = nullptr, *dj = nullptr;
-  if (kind == 0) { tgt[0] = s.out(p->c1, rows * 2 * kw); tgt[1] = s.out(p->c2, rows * 2 * kw); }
-  else {
-    tgt[0] = s.out(p->resp_w1, rows * kw); tgt[1] = s.out(p->resp_r1, rows * kw); tgt[2] = s.out(p->resp_w2, rows * kw); tgt[3] = s.out(p->resp_r2, rows * kw);
-    dkind = s.out(p->resp_kind, rows); dj = s.out(p->resp_j, rows);
-  }
-  int32_t st = s.st;
-  TextSpan ts;
-  std::vector<void*> to_free;
-  if (!st) st = upload_text(c, text, doc_off, doc_len, B, extras, &ts);
-  if (!st) {
-    const uint32_t words = kind == 0 ? 2 * kw : kw;
-    const int ntgt = kind == 0 ? 2 : 4;
-    for (int q = 0; q < ntgt && !st; q++) if (hipMemsetAsync(tgt[q], 0, rows * words * 4, c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "memset"; }
-    if (!st && hipMemcpyAsync(dstat, status.data(), B, hipMemcpyHostToDevice, c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "H2D status"; }
-    if (!st && kind == 1) {
-      if (hipMemcpyAsync(dkind, kinds.data(), rows, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-          hipMemcpyAsync(dj, js.data(), rows, hipMemcpyHostToDevice, c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "H2D kinds"; }
-    }
-    for (int q = 0; q < ntgt && !st; q++) st = convert_lists(c, ts, L[q], tgt[q], words, dstat, to_free);
-    if (!st) {
-      for (int q = 0; q < ntgt; q++) clear_failed_docs(c, dstat, tgt[q], EF * words, B);
-      if (kind == 1) { clear_failed_docs(c, dstat, dkind, EF, B); clear_failed_docs(c, dstat, dj, EF, B); }
-      if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_clear_failed_docs"; }
-    }
-  }
-  const int32_t fin = s.finish();
-  (void)hipStreamSynchronize(c->stream);
-  if (ts.d) (void)hipFree(ts.d);
-  for (void* q : to_free) (void)hipFree(q);
-  return st ? st : fin;
+  uint32_t* const pairs[2] = {p->c1, p->c2};
+  uint32_t* const resp[4] = {p->resp_w1, p->resp_r1, p->resp_w2, p->resp_r2};
+  auto tok = [&](uint64_t b, ReaderThread& T, uint8_t* kinds, uint8_t* js) { return json_range_doc(kind, text, doc_off[b], doc_len[b], b, EF, kw, T, kinds, js); };
+  return kind == 0 ? json_read_host(c, text, doc_off, doc_len, B, 2, pairs, 2 * kw, EF, nullptr, nullptr, true, out_status, tok)
+                   : json_read_host(c, text, doc_off, doc_len, B, 4, resp, kw, EF, p->resp_kind, p->resp_j, true, out_status, tok);
 }
 
 extern "C" int32_t zkp_json_encrypted_pairs_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len,
@@ -448,134 +201,23 @@ extern "C" int32_t zkp_json_correct_key_proof_batch(zkp_ctx* c, const char* text
                                                     uint64_t B, uint32_t* out_sigma, uint8_t* out_status, uint32_t flags) try {
   if (!c) return ZKP_EINVAL;
   if (B == 0) return ZKP_OK;
-  if (!text || !doc_off || !doc_len || !out_sigma || !out_status || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24)) {
+  if (!text || !doc_off || !doc_len || !out_sigma || !out_status || !key_bits_ok(n_bits) || B > (1ull << 24)) {
     c->err = "zkp_json_correct_key_proof_batch: invalid argument"; return ZKP_EINVAL;
   }
   HIPCHK(c, hipSetDevice(c->device));
   if (flags & ZKP_F_DEVICE_PTRS) {
     zkp_range_ni_proofs d{};
-    d.n_bits = n_bits; d.batch = B;
-    return json_scan_entry(c, "zkp_json_correct_key_proof_batch", W_DOC_CK, text, doc_off, doc_len, 0, d, out_sigma, out_status);
+    d.n_bits = n_bits; d.batch = B; d.resp_w1 = out_sigma;
+    return json_scan_entry(c, "zkp_json_correct_key_proof_batch", W_DOC_CK, text, doc_off, doc_len, 0, d, nullptr, out_status);
   }
+  // Two things set this reader apart from the range kinds, and both stay: the sigma rows of a document that fails are NOT cleared (clear = false:
+  // an over-wide entry is zero, the others stay converted), and the status of a malformed document is written as ZKP_VERDICT_MALFORMED.
+  static_assert(ZKP_VERDICT_MALFORMED == ZKP_DOC_INVALID, "the tokeniser's ZKP_DOC_INVALID is the byte this reader documents as ZKP_VERDICT_MALFORMED");
   const uint32_t kw = n_bits / 32;
-  const uint64_t M2 = ZKP_CORRECT_KEY_M2;
-  std::vector<uint8_t> status(B, 0);
-  const unsigned NT = 16;
-  std::vector<ItemList> L(NT);
-  std::vector<std::string> extras(NT);
-  for_docs(B, [&](uint64_t b, unsigned k) {
-    JCur j{text, doc_off[b], doc_off[b] + doc_len[b]};
-    const size_t mark = L[k].items.size();
-    // {"sigma_vec":[...]}  (correct_key_ni.rs:35-39); a vector of another length is a valid NiCorrectKeyProof whose verify() panics
-    // or ignores the tail (sigma_vec[i], :90): outside the fixed layout -> malformed here
-    j.extra = &extras[k];
-    const size_t extra_mark = extras[k].size();
-    bool seen = false;
-    uint64_t cnt = 0;
-    j.object([&](const std::string& nm) {
-      if (nm != "sigma_vec") return false;
-      if (seen) { j.ok = false; return true; }
-      seen = true;
-      j.expect('[');
-      if (j.ok && !j.eat(']')) {
-        do {
-          uint64_t o; uint32_t l;
-          if (j.str(&o, &l) && cnt < M2) { L[k].items.push_back({o, (b * M2 + cnt) * kw, l, kw}); L[k].doc.push_back((uint32_t)b); }
-          cnt++;
-        } while (j.ok && j.eat(','));
-        j.expect(']');
-      }
-      return true;
-    });
-    if (!seen || cnt != M2) j.ok = false;
-    if (!j.ok) extras[k].resize(extra_mark);
-    if (!j.done()) { status[b] = ZKP_VERDICT_MALFORMED; L[k].items.resize(mark); L[k].doc.resize(mark); }
-  });
-  Stage s(c, flags);
-  uint8_t* dstat = s.out(out_status, B);
-  uint32_t* dsig = s.out(out_sigma, B * M2 * kw);
-  int32_t st = s.st;
-  TextSpan ts;
-  std::vector<void*> to_free;
-  if (!st) st = upload_text(c, text, doc_off, doc_len, B, extras, &ts);
-  if (!st) {
-    if (hipMemsetAsync(dsig, 0, B * M2 * kw * 4, c->stream) != hipSuccess || hipMemcpyAsync(dstat, status.data(), B, hipMemcpyHostToDevice, c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "H2D"; }
-    if (!st) st = convert_lists(c, ts, L, dsig, kw, dstat, to_free);
-  }
-  const int32_t fin = s.finish();
-  (void)hipStreamSynchronize(c->stream);
-  if (ts.d) (void)hipFree(ts.d);
-  for (void* q : to_free) (void)hipFree(q);
-  return st ? st : fin;
+  uint32_t* const sigma[1] = {out_sigma};
+  return json_read_host(c, text, doc_off, doc_len, B, 1, sigma, kw, ZKP_CORRECT_KEY_M2, nullptr, nullptr, false, out_status,
+                        [&](uint64_t b, ReaderThread& T, uint8_t*, uint8_t*) { return json_sigma_vec_doc(text, doc_off[b], doc_len[b], b, kw, T); });
 } ZKP_CATCH(c)
-
-// ---- whole RangeProofNi documents (range_proof_ni.rs:36-44): {"ek":..,"range":..,"ciphertext":..,"encrypted_pairs":..,"proof":..,"error_factor":..}
-// encrypted_pairs / proof are the annotated types above (serialize::{vecbigint,bigint}: decimal strings, serialize.rs:1-78) and go
-// through the same GPU conversion; ek, range and ciphertext are UN-annotated (EncryptionKey of kzen-paillier, bare curv BigInt):
-// their text form is fixed by crates that are not in the tree, so the caller names it — the sample a Rust build writes
-// (tools/reference_vectors: "serde" section) decides which one is real:
-//   ZKP_BIGINT_DEC   "1234"            decimal string (what serialize::bigint writes)
-//   ZKP_BIGINT_HEX   "04d2"            hex string of the big-endian magnitude (either case, odd length allowed)
-//   ZKP_BIGINT_BYTES [4,210]           array of big-endian byte values (serde_json's rendering of serialize_bytes)
-// EncryptionKey: an object with a field "n" in that form (other fields, e.g. "nn", are skipped).  This is the host-pointer reader (flags 0);
-// with ZKP_F_DEVICE_PTRS the documents go through the device scanner first (json_scan below) and only its fall-backs come here.
-namespace {
-// -> 0 converted; ZKP_DOC_HOST_PATH: an integer this width cannot carry (negative or too wide; the token is consumed, dst is zero);
-// ZKP_DOC_INVALID: not an integer of this text form (j.ok = false)
-int parse_bigint_value(JCur& j, uint32_t enc, uint32_t* dst, uint32_t words) {
-  memset(dst, 0, (size_t)words * 4);
-  auto invalid = [&]() { j.ok = false; return (int)ZKP_DOC_INVALID; };
-  auto unrepresentable = [&]() { memset(dst, 0, (size_t)words * 4); return (int)ZKP_DOC_HOST_PATH; };
-  if (enc == ZKP_BIGINT_BYTES) {
-    std::vector<uint8_t> bytes;
-    if (!j.expect('[')) return invalid();
-    if (!j.eat(']')) {
-      do { uint64_t v; if (!j.uint(&v) || v > 255) return invalid(); bytes.push_back((uint8_t)v); } while (j.eat(','));
-      if (!j.expect(']')) return invalid();
-    }
-    size_t lead = 0;
-    while (lead < bytes.size() && bytes[lead] == 0) lead++;
-    if (bytes.size() - lead > (size_t)words * 4) return unrepresentable();
-    for (size_t i = lead; i < bytes.size(); i++) { const size_t pos = bytes.size() - 1 - i; dst[pos / 4] |= (uint32_t)bytes[i] << (8 * (pos % 4)); }
-    return 0;
-  }
-  uint64_t off; uint32_t len; bool esc;
-  if (!j.raw_str(&off, &len, &esc) || esc || len == 0) return invalid();
-  const char* t = j.t + off;
-  const bool minus = t[0] == '-';
-  if (minus) { t++; len--; if (len == 0) return invalid(); }
-  bool nonzero = false, too_wide = false;
-  if (enc == ZKP_BIGINT_HEX) {
-    uint32_t lead = 0;
-    while (lead + 1 < len && t[lead] == '0') lead++;
-    for (uint32_t i = lead; i < len; i++) {
-      const int h = JCur::hexv(t[i]);
-      if (h < 0) return invalid();
-      nonzero |= h != 0;
-      const uint32_t pos = len - 1 - i;
-      if (pos / 8 >= words) { too_wide |= h != 0; continue; }
-      dst[pos / 8] |= (uint32_t)h << (4 * (pos % 8));
-    }
-  } else {
-    // decimal: 9 digits at a time, x = x * 10^9 + chunk (BigInt::from_str_radix accepts leading zeros)
-    uint32_t used = 0;
-    for (uint32_t i = 0; i < len;) {
-      const uint32_t take = std::min<uint32_t>(9, len - i);
-      uint64_t chunk = 0, mul = 1;
-      for (uint32_t k = 0; k < take; k++) { const char ch = t[i + k]; if (ch < '0' || ch > '9') return invalid(); chunk = chunk * 10 + (uint64_t)(ch - '0'); mul *= 10; }
-      nonzero |= chunk != 0;
-      if (!too_wide) {
-        uint64_t carry = chunk;
-        for (uint32_t w = 0; w < used; w++) { const uint64_t v = (uint64_t)dst[w] * mul + carry; dst[w] = (uint32_t)v; carry = v >> 32; }
-        while (carry) { if (used == words) { too_wide = true; break; } dst[used++] = (uint32_t)carry; carry >>= 32; }
-      }
-      i += take;
-    }
-  }
-  if (too_wide || (minus && nonzero)) return unrepresentable();
-  return 0;
-}
-}  // namespace
 
 // ---- the same documents through the device scanner (kernels_serde_scan.hpp): the text is uploaded once and tokenised there; what the
 // scanner does not take byte for byte goes through the host reader above, unchanged, and is merged into the same device arrays.
@@ -595,20 +237,19 @@ template <class T> int32_t scan_merge(zkp_ctx* c, Stage& s, const std::vector<T>
   return ZKP_OK;
 }
 
-// One batch of documents of one kind (W_DOC_*) into device memory.  d: the arrays of the kind (RangeProofNi: every one; EncryptedPairs: c1, c2;
-// Proof: resp_*; NiCorrectKeyProof: none of them — `sigma` [B][11][kw] instead, with d.n_bits and d.batch); d.n is the verifier's key when
-// d.n_stride == 0 (an input), else it receives the documents' keys.
-// Statuses and arrays are what the kind's reader gives with flags == 0 on host arrays, byte for byte:
-//   - a scanned document has no malformed number and no sign, so the only status left is k_dec2bin's overflow (ZKP_DOC_HOST_PATH);
-//   - RangeProofNi: the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader
-//     decides before it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH;
-//   - what was converted of a document that ends up unconverted is cleared where the host reader clears it: everywhere but in sigma.
-int32_t json_heads_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t key_form, uint32_t bare_form, uint32_t kw,
-                        uint32_t yw, uint32_t* const* out, uint8_t* out_status);
+// the text of a call as the scanner reads it, uploaded by the caller: byte `a` of the caller's text is d[a - lo], and 16 bytes '0' follow the span
+struct ScanText { char* d; uint64_t lo, span; };
 void scan_span(const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint64_t* lo, uint64_t* hi) {
   for (uint64_t b = 0; b < B; b++) if (doc_len[b]) { *lo = std::min(*lo, doc_off[b]); *hi = std::max(*hi, doc_off[b] + doc_len[b]); }
 }
-int32_t scan_upload(zkp_ctx* c, Stage& s, const char* text, uint64_t lo, uint64_t hi, ScanText* o) {
+// The start of every call that scans: the counters of zkp_diag_last_json_scan start over, event 0, and the span of the call's one or two lists
+// of documents (off2 / len2 nullable) goes to the device
+int32_t scan_begin(zkp_ctx* c, Stage& s, const char* text, const uint64_t* off1, const uint64_t* len1, const uint64_t* off2, const uint64_t* len2, uint64_t B, ScanText* o) {
+  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
+  if (const int32_t st = scan_event(c, 0)) return st;
+  uint64_t lo = ~0ull, hi = 0;
+  scan_span(off1, len1, B, &lo, &hi);
+  if (off2) scan_span(off2, len2, B, &lo, &hi);
   if (hi == 0) lo = 0;
   o->lo = lo; o->span = hi - lo;
   o->d = (char*)s.take(o->span + 16);
@@ -617,29 +258,31 @@ int32_t scan_upload(zkp_ctx* c, Stage& s, const char* text, uint64_t lo, uint64_
   HIPCHK(c, hipMemsetAsync(o->d + o->span, '0', 16, c->stream));
   return ZKP_OK;
 }
-// The heads-only kinds: head_dst[i] is the destination of head i of w_doc_spec(doc_kind) (the two DLog kinds may name N, g, ni / x, y as d.n, d.range,
-// d.ciphertext instead; y: y_bits / 32 words), d.n_stride = kw, forms is ZKP_BIGINT_FORMS(key, bare) (the DLog kinds have no key: the bare form
-// alone), and nothing is cleared afterwards: as with sigma, an over-wide field is zero and the others stay converted.
-// pre: the text is already on the device (the caller also keeps the diagnostics: events and counters of BOTH scans of its call).
-int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
-                  const zkp_range_ni_proofs& d, uint32_t* sigma, uint8_t* dstat, uint32_t y_bits, const ScanText* pre, uint32_t* const* head_dst) {
+
+// One batch of documents of one kind (W_DOC_*) into device memory, from text the caller has uploaded (scan_begin).  Every kind takes d.n_bits and
+// d.batch; its destinations are
+//   RangeProofNi        every array of d; d.n is the verifier's key when d.n_stride == 0 (an input), else it receives the documents' keys
+//   EncryptedPairs      d.c1, d.c2                      Proof   d.resp_*
+//   NiCorrectKeyProof   d.resp_w1: sigma [B][11][kw] (the writer's W_ARR_W1)
+//   a heads-only kind   head_dst[i]: head i of w_doc_spec(doc_kind), one number per document (CompositeDLogProof.y: y_bits / 32 words)
+// forms is ZKP_BIGINT_FORMS(key, bare) (the DLog kinds have no key: the bare form alone).
+// Statuses and arrays are what the kind's reader gives with flags == 0 on host arrays, byte for byte:
+//   - a scanned document has no malformed number and no sign, so the only status left is k_dec2bin's overflow (ZKP_DOC_HOST_PATH);
+//   - RangeProofNi: the head is converted and marked first, then compared with the verifier's key (ZKP_DOC_INVALID, as the host reader
+//     decides before it looks at the rows), then the rows: k_mark_docs only ever turns ZKP_DOC_OK into ZKP_DOC_HOST_PATH;
+//   - what was converted of a document that ends up unconverted is cleared where the host reader clears it: everywhere but in sigma and in
+//     the heads-only kinds, where an over-wide field is zero and the others stay converted.
+// marks: the call scans once, and events 1 and 2 of zkp_diag_last_json_scan_ms lie around the scan kernel (the caller records 0 and 3).
+int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const ScanText& up, const char* text, const uint64_t* doc_off, const uint64_t* doc_len,
+                  uint32_t forms, const zkp_range_ni_proofs& d, uint32_t* const* head_dst, uint8_t* dstat, uint32_t y_bits, bool marks) {
   const bool ni = doc_kind == W_DOC_NI, ck = doc_kind == W_DOC_CK, has_pairs = ni || doc_kind == W_DOC_PAIRS, has_rows = ni || doc_kind == W_DOC_PROOF;
   const WDocSpec& spec = w_doc_spec(doc_kind);
   const bool dl = spec.heads_only, heads = spec.n_heads != 0;
   const uint64_t B = d.batch, EF = ck ? ZKP_CORRECT_KEY_M2 : dl ? 0 : d.error_factor, rows = B * EF;
   const uint32_t kw = d.n_bits / 32, yw = y_bits / 32;
-  const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
-  const bool per_key = d.n_stride != 0;
+  const uint32_t key_form = decode_forms(forms).key, bare_form = decode_forms(forms).bare;
+  const bool per_key = !ni || d.n_stride != 0;      // head 0 is one number per document and a destination (not the batch's one key)
   int32_t st = ZKP_OK;
-  ScanText up{};
-  if (pre) up = *pre;
-  else {
-    c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
-    if ((st = scan_event(c, 0))) return st;
-    uint64_t lo = ~0ull, hi = 0;
-    scan_span(doc_off, doc_len, B, &lo, &hi);
-    if ((st = scan_upload(c, s, text, lo, hi, &up))) return st;
-  }
   const uint64_t lo = up.lo, span = up.span;
   ScanJob J{};
   char* dtext = up.d;
@@ -648,10 +291,10 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
   J.max_len = zkp_json_doc_bound(doc_kind, d.n_bits, d.error_factor, forms);
   J.doc_kind = doc_kind; J.ef = (uint32_t)EF; J.kw = kw; J.key_form = key_form; J.bare_form = bare_form;
   J.dig_n = zkp_decimal_pitch(kw) - 1; J.dig_c = zkp_decimal_pitch(2 * kw) - 1;      // (max_digits below)
-  // the heads: the table's rows with this batch's widths, forms and destinations
-  uint32_t* const legacy_dst[3] = {heads ? (per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4)) : nullptr, const_cast<uint32_t*>(d.range),
-                                   const_cast<uint32_t*>(d.ciphertext)};
-  if (!head_dst) head_dst = legacy_dst;
+  // the heads: the table's rows with this batch's widths, forms and destinations (a RangeProofNi under the verifier's key reads its own into a block)
+  uint32_t* const ni_dst[3] = {!ni ? nullptr : per_key ? const_cast<uint32_t*>(d.n) : (uint32_t*)s.take(B * kw * 4), const_cast<uint32_t*>(d.range),
+                               const_cast<uint32_t*>(d.ciphertext)};
+  if (ni) head_dst = ni_dst;
   J.n_heads = spec.n_heads; J.heads_only = spec.heads_only;
   struct Target { int arr; uint32_t* dst; uint32_t words; };      // arr < W_ARR_C1: head `arr`, one number per document; else EF
   std::vector<Target> targets;
@@ -665,7 +308,7 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
   if (has_rows) { J.kind = d.resp_kind; J.j = d.resp_j; }
   if (has_pairs) targets.insert(targets.end(), {{W_ARR_C1, d.c1, 2 * kw}, {W_ARR_C2, d.c2, 2 * kw}});
   if (has_rows) targets.insert(targets.end(), {{W_ARR_W1, d.resp_w1, kw}, {W_ARR_R1, d.resp_r1, kw}, {W_ARR_W2, d.resp_w2, kw}, {W_ARR_R2, d.resp_r2, kw}});
-  if (ck) targets.push_back({W_ARR_W1, sigma, kw});
+  if (ck) targets.push_back({W_ARR_W1, d.resp_w1, kw});
   for (const Target& t : targets) {
     const bool head = t.arr < W_ARR_C1;
     if (head && J.head[t.arr].form != ZKP_BIGINT_DEC) continue;
@@ -681,10 +324,10 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     HIPCHK(c, hipMemsetAsync(d.resp_kind, 0, rows, c->stream));
     HIPCHK(c, hipMemsetAsync(d.resp_j, 0, rows, c->stream));
   }
-  if (!pre && (st = scan_event(c, 1))) return st;
+  if (marks && (st = scan_event(c, 1))) return st;
   hipLaunchKernelGGL(k_json_scan, dim3((unsigned)B), dim3(64), 0, c->stream, J);
   HIPCHK(c, hipGetLastError());
-  if (!pre && (st = scan_event(c, 2))) return st;
+  if (marks && (st = scan_event(c, 2))) return st;
   auto convert = [&](const Target& t) -> int32_t {
     if (!J.items[t.arr]) return ZKP_OK;                      // a head integer in hex / byte-array form: the scanner wrote its limbs
     const bool head = t.arr < W_ARR_C1;
@@ -752,11 +395,47 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     if (st) return st;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the host vectors go out of scope
   }
-  return pre ? ZKP_OK : scan_event(c, 3);
+  return ZKP_OK;
+}
+// a call that scans ONE list of documents; the phases of zkp_diag_last_json_scan_ms: upload | scan | convert and merge | (a verify: the rest)
+int32_t scan_one(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                 const zkp_range_ni_proofs& d, uint32_t* const* head_dst, uint8_t* dstat, uint32_t y_bits = 0) {
+  ScanText up{};
+  int32_t st = scan_begin(c, s, text, doc_off, doc_len, nullptr, nullptr, d.batch, &up);
+  if (!st) st = json_scan(c, s, name, doc_kind, up, text, doc_off, doc_len, forms, d, head_dst, dstat, y_bits, true);
+  return st ? st : scan_event(c, 3);
+}
+// The prelude of a verify of (statement, proof) pairs: two lists of documents in one text, uploaded once; the statements are scanned into st_dst
+// with their statuses in dstat, the proofs into pf_dst with theirs in dstat2.  The phases: upload | statements read | proofs read | (the rest)
+int32_t scan_pairs(zkp_ctx* c, Stage& s, const char* name, const char* text, uint32_t st_kind, const uint64_t* st_off, const uint64_t* st_len, uint32_t* const* st_dst,
+                   uint8_t* dstat, uint32_t pf_kind, const uint64_t* pf_off, const uint64_t* pf_len, uint32_t* const* pf_dst, uint8_t* dstat2, uint64_t B, uint32_t n_bits,
+                   uint32_t y_bits, uint32_t forms) {
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.batch = B;
+  ScanText up{};
+  int32_t st = scan_begin(c, s, text, st_off, st_len, pf_off, pf_len, B, &up);
+  if (!st) st = scan_event(c, 1);
+  if (!st) st = json_scan(c, s, name, st_kind, up, text, st_off, st_len, forms, d, st_dst, dstat, y_bits, false);
+  if (!st) st = scan_event(c, 2);
+  if (!st) st = json_scan(c, s, name, pf_kind, up, text, pf_off, pf_len, forms, d, pf_dst, dstat2, y_bits, false);
+  return st ? st : scan_event(c, 3);
+}
+// The end of every verify on documents: the verdicts of the documents that were not converted are masked, event 4, the call's end
+int32_t verify_end(zkp_ctx* c, Stage& s, int32_t st, const uint8_t* dstat, uint8_t* dv, uint64_t B) {
+  if (!st) {
+    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, dstat, dv, B);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
+  }
+  if (!st) st = scan_event(c, 4);
+  return call_end(c, s, st, true);
+}
+int32_t json_scan_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t forms,
+                        const zkp_range_ni_proofs& d, uint32_t* const* head_dst, uint8_t* out_status, uint32_t y_bits) {
+  Stage s(c, ZKP_F_DEVICE_PTRS);
+  return call_end(c, s, scan_one(c, s, name, doc_kind, text, doc_off, doc_len, forms, d, head_dst, out_status, y_bits), true);
 }
 bool json_ni_common_args_ok(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t n_bits, uint32_t ef, uint32_t forms) {
-  return text && doc_off && doc_len && B <= (1ull << 24) && (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && ef != 0 && ef <= 256 && !(forms >> 8) &&
-         ((forms >> 4) & 15u) <= ZKP_BIGINT_BYTES && (forms & 15u) <= ZKP_BIGINT_BYTES;
+  return text && doc_off && doc_len && B <= (1ull << 24) && key_bits_ok(n_bits) && ef != 0 && ef <= 256 && decode_forms(forms).ok;
 }
 }  // namespace
 
@@ -799,19 +478,11 @@ extern "C" int32_t zkp_range_ni_verify_json_batch(zkp_ctx* c, const char* text, 
   d.resp_w1 = (uint32_t*)s.take(rows * kw * 4); d.resp_r1 = (uint32_t*)s.take(rows * kw * 4);
   d.resp_w2 = (uint32_t*)s.take(rows * kw * 4); d.resp_r2 = (uint32_t*)s.take(rows * kw * 4);
   int32_t st = s.st;
-  if (!st) st = json_scan(c, s, "zkp_range_ni_verify_json_batch", W_DOC_NI, text, doc_off, doc_len, bigint_forms, d, nullptr, dstat);
+  if (!st) st = scan_one(c, s, "zkp_range_ni_verify_json_batch", W_DOC_NI, text, doc_off, doc_len, bigint_forms, d, nullptr, dstat);
   // The whole batch is verified and the verdicts of the documents that were not converted are masked afterwards: their rows are zero, and
   // with verify_self so is their key, which the verify kernels answer with a verdict of that proof alone (never an error of the call).
   if (!st) st = zkp_range_ni_verify_batch(c, &d, dv, ZKP_F_DEVICE_PTRS);
-  if (!st) {
-    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
-    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
-  }
-  if (!st) st = scan_event(c, 4);
-  if (st && !s.st) s.st = st;
-  const int32_t fin = s.finish();
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-  return st ? st : fin;
+  return verify_end(c, s, st, dstat, dv, B);
 } ZKP_CATCH(c)
 
 // NiCorrectKeyProof::verify on documents: the same three steps with sigma in a block the call owns.  An unread document leaves zero (or, where
@@ -822,7 +493,7 @@ extern "C" int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* c, const char* 
   if (!c) return ZKP_EINVAL;
   if (B == 0) return ZKP_OK;
   if ((flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !text || !doc_off || !doc_len || !n || !out_status || !out_verdict || (salt_len && !salt) ||
-      (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24)) {
+      !key_bits_ok(n_bits) || B > (1ull << 24)) {
     c->err = "zkp_correct_key_ni_verify_json_batch: invalid argument"; return ZKP_EINVAL;
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -833,21 +504,23 @@ extern "C" int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* c, const char* 
   const uint32_t* dn = s.in(n, B * kw);
   uint32_t* dsig = (uint32_t*)s.take(B * ZKP_CORRECT_KEY_M2 * kw * 4);
   zkp_range_ni_proofs d{};
-  d.n_bits = n_bits; d.batch = B;
+  d.n_bits = n_bits; d.batch = B; d.resp_w1 = dsig;
   int32_t st = s.st;
-  if (!st) st = json_scan(c, s, "zkp_correct_key_ni_verify_json_batch", W_DOC_CK, text, doc_off, doc_len, 0, d, dsig, dstat);
+  if (!st) st = scan_one(c, s, "zkp_correct_key_ni_verify_json_batch", W_DOC_CK, text, doc_off, doc_len, 0, d, nullptr, dstat);
   if (!st) st = zkp_correct_key_ni_verify_batch(c, n_bits, B, dn, dsig, salt, salt_len, dv, ZKP_F_DEVICE_PTRS);
-  if (!st) {
-    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
-    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
-  }
-  if (!st) st = scan_event(c, 4);
-  if (st && !s.st) s.st = st;
-  const int32_t fin = s.finish();
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-  return st ? st : fin;
+  return verify_end(c, s, st, dstat, dv, B);
 } ZKP_CATCH(c)
 
+// ---- whole RangeProofNi documents (range_proof_ni.rs:36-44): {"ek":..,"range":..,"ciphertext":..,"encrypted_pairs":..,"proof":..,"error_factor":..}
+// encrypted_pairs / proof are the annotated types above (serialize::{vecbigint,bigint}: decimal strings, serialize.rs:1-78) and go
+// through the same GPU conversion; ek, range and ciphertext are UN-annotated (EncryptionKey of kzen-paillier, bare curv BigInt):
+// their text form is fixed by crates that are not in the tree, so the caller names it — the sample a Rust build writes
+// (tools/reference_vectors: "serde" section) decides which one is real:
+//   ZKP_BIGINT_DEC   "1234"            decimal string (what serialize::bigint writes)
+//   ZKP_BIGINT_HEX   "04d2"            hex string of the big-endian magnitude (either case, odd length allowed)
+//   ZKP_BIGINT_BYTES [4,210]           array of big-endian byte values (serde_json's rendering of serialize_bytes)
+// EncryptionKey: an object with a field "n" in that form (other fields, e.g. "nn", are skipped).  This is the host-pointer reader (flags 0);
+// with ZKP_F_DEVICE_PTRS the documents go through the device scanner first (json_scan below) and only its fall-backs come here.
 extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t bigint_forms,
                                                  const zkp_range_ni_proofs* p, uint8_t* out_status, uint32_t flags) try {
   if (!c) return ZKP_EINVAL;
@@ -863,9 +536,9 @@ extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, c
   }
   const uint64_t B = p->batch;
   const uint32_t kw = p->n_bits / 32;
-  const uint32_t key_form = (bigint_forms >> 4) & 15u, bare_form = bigint_forms & 15u;
-  if (flags != 0 || !text || !doc_off || !doc_len || !out_status || !p->n || !p->range || !p->ciphertext || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES ||
-      (bigint_forms >> 8) || (p->n_stride != 0 && p->n_stride != kw) || (p->n_bits != 1024 && p->n_bits != 2048 && p->n_bits != 4096)) {
+  const BigintForms forms = decode_forms(bigint_forms);
+  if (flags != 0 || !text || !doc_off || !doc_len || !out_status || !p->n || !p->range || !p->ciphertext || !forms.ok || (p->n_stride != 0 && p->n_stride != kw) ||
+      !key_bits_ok(p->n_bits)) {
     c->err = "zkp_json_range_proof_ni_batch: invalid argument"; return ZKP_EINVAL;
   }
   // (range and ciphertext — and n with one key per proof — are inputs of every other entry point, hence const in the struct; here
@@ -876,35 +549,9 @@ extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, c
   std::vector<uint64_t> ep_off(B), ep_len(B), pr_off(B), pr_len(B);
   std::vector<uint32_t> keys((size_t)B * kw, 0);
   for_docs(B, [&](uint64_t b, unsigned) {
-    JCur j{text, doc_off[b], doc_off[b] + doc_len[b]};
-    std::string none;
-    j.extra = &none;
-    unsigned seen = 0;
-    bool host = false;
-    ep_off[b] = pr_off[b] = doc_off[b]; ep_len[b] = pr_len[b] = 0;
-    auto once = [&](unsigned bit) { if (seen & bit) { j.ok = false; return false; } seen |= bit; return true; };
-    j.object([&](const std::string& nm) {
-      if (nm == "ek") {
-        if (!once(1)) return true;
-        bool has_n = false;
-        j.object([&](const std::string& f) {
-          if (f != "n") return false;
-          if (has_n) { j.ok = false; return true; }
-          has_n = true;
-          host |= parse_bigint_value(j, key_form, &keys[b * kw], kw) == ZKP_DOC_HOST_PATH;
-          return true;
-        });
-        if (!has_n) j.ok = false;
-      } else if (nm == "range") { if (once(2)) host |= parse_bigint_value(j, bare_form, out_range + b * kw, kw) == ZKP_DOC_HOST_PATH; }
-      else if (nm == "ciphertext") { if (once(4)) host |= parse_bigint_value(j, bare_form, out_ct + b * 2 * kw, 2 * kw) == ZKP_DOC_HOST_PATH; }
-      else if (nm == "encrypted_pairs") { if (once(8)) { j.ws(); ep_off[b] = j.p; j.skip_value(); ep_len[b] = j.p - ep_off[b]; } }
-      else if (nm == "proof") { if (once(16)) { j.ws(); pr_off[b] = j.p; j.skip_value(); pr_len[b] = j.p - pr_off[b]; } }
-      else if (nm == "error_factor") { uint64_t ef = 0; if (once(32)) { j.uint(&ef); if (ef != p->error_factor) host = true; } }   // any usize is a valid RangeProofNi
-      else return false;
-      return true;
-    });
-    if (seen != 63u) j.ok = false;
-    top[b] = !j.done() ? ZKP_DOC_INVALID : host ? ZKP_DOC_HOST_PATH : ZKP_DOC_OK;
+    NiSpans sp;
+    top[b] = json_range_ni_top(text, doc_off[b], doc_len[b], forms.key, forms.bare, kw, p->error_factor, &keys[b * kw], out_range + b * kw, out_ct + b * 2 * kw, &sp);
+    ep_off[b] = sp.ep_off; ep_len[b] = sp.ep_len; pr_off[b] = sp.pr_off; pr_len[b] = sp.pr_len;
   });
   if (p->n_stride) {
     // one key per proof: the documents' keys are the output (verify_self semantics, range_proof_ni.rs:109-128)
@@ -916,10 +563,12 @@ extern "C" int32_t zkp_json_range_proof_ni_batch(zkp_ctx* c, const char* text, c
   } else {
     // RangeProofNi::verify(ek, ..) asserts that the proof was made under the verifier's key (range_proof_ni.rs:86): a document
     // under another key is a panic there, ZKP_DOC_INVALID here — and no document can change the key the batch is verified under
-    for (uint64_t b = 0; b < B; b++) if (!top[b] && memcmp(&keys[b * kw], p->n, (size_t)kw * 4) != 0) top[b] = ZKP_DOC_INVALID;
+    for (uint64_t b = 0; b < B; b++)
+      if (!top[b] && memcmp(&keys[b * kw], p->n, (size_t)kw * 4) != 0) {
+        top[b] = ZKP_DOC_INVALID;
+        memset(out_range + b * kw, 0, (size_t)kw * 4); memset(out_ct + b * 2 * kw, 0, (size_t)kw * 8); ep_off[b] = pr_off[b] = doc_off[b]; ep_len[b] = pr_len[b] = 0;
+      }
   }
-  for (uint64_t b = 0; b < B; b++)
-    if (top[b]) { memset(out_range + b * kw, 0, (size_t)kw * 4); memset(out_ct + b * 2 * kw, 0, (size_t)kw * 8); ep_off[b] = pr_off[b] = doc_off[b]; ep_len[b] = pr_len[b] = 0; }
   std::vector<uint8_t> s1(B, 0), s2(B, 0);
   int32_t st = json_range_entry(c, "zkp_json_range_proof_ni_batch", 0, text, ep_off.data(), ep_len.data(), p, s1.data(), 0);
   if (!st) st = json_range_entry(c, "zkp_json_range_proof_ni_batch", 1, text, pr_off.data(), pr_len.data(), p, s2.data(), 0);
@@ -953,11 +602,11 @@ constexpr uint64_t cstrlen(const char* s) { return *s ? 1 + cstrlen(s + 1) : 0; 
 }  // namespace
 
 extern "C" uint64_t zkp_json_doc_bound(uint32_t doc_kind, uint32_t n_bits, uint32_t error_factor, uint32_t bigint_forms) {
-  const uint32_t key_form = (bigint_forms >> 4) & 15u, bare_form = bigint_forms & 15u;
+  const BigintForms forms = decode_forms(bigint_forms);
+  const uint32_t key_form = forms.key, bare_form = forms.bare;
   const WDocSpec& spec = w_doc_spec(doc_kind);
   const bool dl = spec.heads_only;
-  if ((n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || (doc_kind > ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl) || (bigint_forms >> 8) ||
-      key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (doc_kind != ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl && error_factor == 0))
+  if (!key_bits_ok(n_bits) || (doc_kind > ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl) || !forms.ok || (doc_kind != ZKP_JSON_DOC_CORRECT_KEY_PROOF && !dl && error_factor == 0))
     return 0;
   const uint32_t kw = n_bits / 32;
   if (dl) {
@@ -988,13 +637,13 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
                                const uint32_t* sigma, uint32_t forms, char* out_text, uint64_t text_cap, uint64_t* out_doc_off, uint8_t* out_status, uint32_t flags,
                                const WHeads* hd = nullptr) {
   if (!c) return ZKP_EINVAL;
-  const uint32_t key_form = (forms >> 4) & 15u, bare_form = forms & 15u;
+  const uint32_t key_form = decode_forms(forms).key, bare_form = decode_forms(forms).bare;
   const bool ck = doc_kind == W_DOC_CK, ni = doc_kind == W_DOC_NI, has_pairs = doc_kind == W_DOC_PAIRS || ni, has_proof = doc_kind == W_DOC_PROOF || ni;
   const WDocSpec& spec = w_doc_spec(doc_kind);
   const bool dl = spec.heads_only;
   const uint32_t kw = n_bits / 32;
-  bool bad = !out_doc_off || (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || (n_bits != 1024 && n_bits != 2048 && n_bits != 4096) || B > (1ull << 24) ||
-             (forms >> 8) || key_form > ZKP_BIGINT_BYTES || bare_form > ZKP_BIGINT_BYTES || (!ck && !dl && !p) || (!ck && !dl && (EF == 0 || EF > 256));
+  bool bad = !out_doc_off || (flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !key_bits_ok(n_bits) || B > (1ull << 24) || !decode_forms(forms).ok ||
+             (!ck && !dl && !p) || (!ck && !dl && (EF == 0 || EF > 256));
   if (!bad && B) {
     if (dl) { bad = !hd; for (uint32_t i = 0; !bad && i < w_heads(doc_kind); i++) bad = !hd->a[i]; }
     else if (ck) bad = !sigma;
@@ -1066,8 +715,7 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
   if (!st && out_text && text_cap < total) {
     st = ZKP_EINVAL;
     c->err = std::string(name) + ": text_cap " + std::to_string(text_cap) + " is less than the " + std::to_string(total) + " bytes of the documents";
-    const int32_t fin = s.finish();       // (the status bytes are still delivered; finish() returns the sticky status)
-    (void)fin;
+    (void)s.finish();       // (the status bytes are still delivered)
     return ZKP_EINVAL;
   }
   if (!st && out_text && total) {
@@ -1104,10 +752,7 @@ static int32_t json_write_impl(zkp_ctx* c, const char* name, uint32_t doc_kind, 
     const int32_t pf = pipe.finish();
     if (!st) st = pf;
   }
-  if (st && !s.st) s.st = st;
-  const int32_t fin = s.finish();
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-  return st ? st : fin;
+  return call_end(c, s, st, true);
 }
 
 extern "C" int32_t zkp_json_write_encrypted_pairs_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, char* out_text, uint64_t text_cap, uint64_t* out_doc_off,
@@ -1133,47 +778,6 @@ extern "C" int32_t zkp_json_write_correct_key_proof_batch(zkp_ctx* c, uint32_t n
 // ---- CompositeDLogProof and DLogStatement (wi_dlog_proof.rs:32-43): {"x":X,"y":X} and {"N":X,"g":X,"ni":X}, every X an un-annotated curv BigInt
 // in the one form the caller names.
 namespace {
-// The flags-0 reader of every heads-only kind: the tolerant tokeniser, every number converted on the host (parse_bigint_value, as for the head
-// of a RangeProofNi document).  The fields are the rows of w_doc_spec(doc_kind); a key row is the object "ek" with a field "n" (its other
-// fields are skipped, as for a RangeProofNi).  out[i]: [B][words of field i].  An invalid document leaves zero rows; an over-wide or negative
-// field is zero, the others converted.
-int32_t json_heads_host(const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t doc_kind, uint32_t key_form, uint32_t bare_form, uint32_t kw,
-                        uint32_t yw, uint32_t* const* out, uint8_t* out_status) {
-  const WDocSpec& spec = w_doc_spec(doc_kind);
-  const unsigned nf = spec.n_heads;
-  uint32_t words[W_MAX_HEADS] = {};
-  for (unsigned f = 0; f < nf; f++) words[f] = w_head_words(spec.h[f], kw, yw);
-  for (unsigned f = 0; f < nf; f++) memset(out[f], 0, (size_t)B * words[f] * 4);
-  for_docs(B, [&](uint64_t b, unsigned) {
-    JCur j{text, doc_off[b], doc_off[b] + doc_len[b]};
-    unsigned seen = 0;
-    bool host = false;
-    j.object([&](const std::string& nm) {
-      int f = -1;
-      for (unsigned q = 0; q < nf; q++) if (nm == spec.h[q].name) f = (int)q;
-      if (f < 0) return false;
-      if (seen & (1u << f)) { j.ok = false; return true; }                      // duplicate field
-      seen |= 1u << f;
-      if (!spec.h[f].key) { host |= parse_bigint_value(j, bare_form, out[f] + b * words[f], words[f]) == ZKP_DOC_HOST_PATH; return true; }
-      bool has_n = false;
-      j.object([&](const std::string& k) {
-        if (k != "n") return false;
-        if (has_n) { j.ok = false; return true; }
-        has_n = true;
-        host |= parse_bigint_value(j, key_form, out[f] + b * words[f], words[f]) == ZKP_DOC_HOST_PATH;
-        return true;
-      });
-      if (!has_n) j.ok = false;
-      return true;
-    });
-    if (seen != (1u << nf) - 1) j.ok = false;                                   // missing field
-    const uint8_t st = !j.done() ? ZKP_DOC_INVALID : host ? ZKP_DOC_HOST_PATH : ZKP_DOC_OK;
-    out_status[b] = st;
-    if (st == ZKP_DOC_INVALID) for (unsigned f = 0; f < nf; f++) memset(out[f] + b * words[f], 0, (size_t)words[f] * 4);
-  });
-  return ZKP_OK;
-}
-
 int32_t json_dlog_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,
                         uint32_t y_bits, uint64_t B, uint32_t bare_form, uint32_t* const* out, uint8_t* out_status, uint32_t flags) {
   if (!c) return ZKP_EINVAL;
@@ -1185,9 +789,8 @@ int32_t json_dlog_entry(zkp_ctx* c, const char* name, uint32_t doc_kind, const c
   if (!(flags & ZKP_F_DEVICE_PTRS)) return json_heads_host(text, doc_off, doc_len, B, doc_kind, 0, bare_form, kw, y_bits / 32, out, out_status);
   HIPCHK(c, hipSetDevice(c->device));
   zkp_range_ni_proofs d{};
-  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
-  d.n = out[0]; d.range = out[1]; d.ciphertext = out[2];
-  return json_scan_entry(c, name, doc_kind, text, doc_off, doc_len, bare_form, d, nullptr, out_status, y_bits);
+  d.n_bits = n_bits; d.batch = B;
+  return json_scan_entry(c, name, doc_kind, text, doc_off, doc_len, bare_form, d, out, out_status, y_bits);
 }
 }  // namespace
 
@@ -1238,7 +841,6 @@ extern "C" int32_t zkp_dlog_verify_json_batch(zkp_ctx* c, const char* text, cons
   }
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t kw = n_bits / 32, yw = y_bits / 32;
-  const char* name = "zkp_dlog_verify_json_batch";
   Stage s(c, flags);
   uint8_t* dstat = s.out(out_status, B);
   uint8_t* dv = s.out(out_verdict, B);
@@ -1246,40 +848,17 @@ extern "C" int32_t zkp_dlog_verify_json_batch(zkp_ctx* c, const char* text, cons
   for (auto& a : arr) a = (uint32_t*)s.take(B * kw * 4);
   uint32_t* dy = (uint32_t*)s.take(B * yw * 4);
   uint8_t* dstat2 = (uint8_t*)s.take(B);
+  uint32_t* const pf[2] = {arr[3], dy};      // (arr[0 .. 2]: N, g, ni)
   int32_t st = s.st;
-  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
-  if (!st) st = scan_event(c, 0);
-  ScanText up{};
-  if (!st) {
-    uint64_t lo = ~0ull, hi = 0;
-    scan_span(st_off, st_len, B, &lo, &hi);
-    scan_span(pf_off, pf_len, B, &lo, &hi);
-    st = scan_upload(c, s, text, lo, hi, &up);
-  }
-  if (!st) st = scan_event(c, 1);
-  zkp_range_ni_proofs d{};
-  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
-  d.n = arr[0]; d.range = arr[1]; d.ciphertext = arr[2];
-  if (!st) st = json_scan(c, s, name, W_DOC_DLOG_STATEMENT, text, st_off, st_len, bare_form, d, nullptr, dstat, y_bits, &up);
-  if (!st) st = scan_event(c, 2);
-  d.n = arr[3]; d.range = dy; d.ciphertext = nullptr;
-  if (!st) st = json_scan(c, s, name, W_DOC_DLOG_PROOF, text, pf_off, pf_len, bare_form, d, nullptr, dstat2, y_bits, &up);
-  if (!st) st = scan_event(c, 3);
+  if (!st) st = scan_pairs(c, s, "zkp_dlog_verify_json_batch", text, W_DOC_DLOG_STATEMENT, st_off, st_len, arr, dstat, W_DOC_DLOG_PROOF, pf_off, pf_len, pf, dstat2, B, n_bits,
+                           y_bits, bare_form);
   if (!st) {
     hipLaunchKernelGGL(k_dlog_domain_check, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, arr[0], arr[1], arr[2], arr[3], dy, (uint32_t)kw, (uint32_t)yw, B,
                        (const uint8_t*)dstat2, dstat);
     if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_dlog_domain_check launch"; }
   }
   if (!st) st = zkp_dlog_verify_batch(c, n_bits, y_bits, B, arr[0], arr[1], arr[2], arr[3], dy, dv, ZKP_F_DEVICE_PTRS);
-  if (!st) {
-    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
-    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
-  }
-  if (!st) st = scan_event(c, 4);
-  if (st && !s.st) s.st = st;
-  const int32_t fin = s.finish();
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-  return st ? st : fin;
+  return verify_end(c, s, st, dstat, dv, B);
 } ZKP_CATCH(c)
 
 // ---- ZeroProof, CiphertextProof, VerlinProof, MulProof and their statements (zero_enc_proof.rs:26-41, correct_ciphertext.rs:22-39,
@@ -1291,8 +870,7 @@ struct SigmaFieldList {
   explicit SigmaFieldList(const zkp_sigma_fields* p) { if (p) { f[0] = p->f0; f[1] = p->f1; f[2] = p->f2; f[3] = p->f3; f[4] = p->f4; } }
 };
 bool sigma_json_args_ok(uint32_t doc_kind, uint32_t n_bits, uint64_t B, uint32_t forms) {
-  return w_sigma_kind(doc_kind) && (n_bits == 1024 || n_bits == 2048 || n_bits == 4096) && B <= (1ull << 24) && !(forms >> 8) && ((forms >> 4) & 15u) <= ZKP_BIGINT_BYTES &&
-         (forms & 15u) <= ZKP_BIGINT_BYTES;
+  return w_sigma_kind(doc_kind) && key_bits_ok(n_bits) && B <= (1ull << 24) && decode_forms(forms).ok;
 }
 }  // namespace
 
@@ -1305,11 +883,11 @@ extern "C" int32_t zkp_json_sigma_batch(zkp_ctx* c, uint32_t doc_kind, const cha
   for (unsigned f = 0; !bad && f < w_heads(doc_kind); f++) bad = !o.f[f];
   if (bad) { c->err = "zkp_json_sigma_batch: invalid argument"; return ZKP_EINVAL; }
   const uint32_t kw = n_bits / 32;
-  if (!(flags & ZKP_F_DEVICE_PTRS)) return json_heads_host(text, doc_off, doc_len, B, doc_kind, (bigint_forms >> 4) & 15u, bigint_forms & 15u, kw, 0, o.f, out_status);
+  if (!(flags & ZKP_F_DEVICE_PTRS)) return json_heads_host(text, doc_off, doc_len, B, doc_kind, decode_forms(bigint_forms).key, decode_forms(bigint_forms).bare, kw, 0, o.f, out_status);
   HIPCHK(c, hipSetDevice(c->device));
   zkp_range_ni_proofs d{};
-  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
-  return json_scan_entry(c, "zkp_json_sigma_batch", doc_kind, text, doc_off, doc_len, bigint_forms, d, nullptr, out_status, 0, o.f);
+  d.n_bits = n_bits; d.batch = B;
+  return json_scan_entry(c, "zkp_json_sigma_batch", doc_kind, text, doc_off, doc_len, bigint_forms, d, o.f, out_status);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_json_write_sigma_batch(zkp_ctx* c, uint32_t doc_kind, uint32_t n_bits, uint64_t batch, const zkp_sigma_fields* in, uint32_t bigint_forms, char* out_text,
@@ -1340,7 +918,6 @@ extern "C" int32_t zkp_sigma_verify_json_batch(zkp_ctx* c, uint32_t proof_kind, 
     c->err = "zkp_sigma_verify_json_batch: invalid argument"; return ZKP_EINVAL;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  const char* name = "zkp_sigma_verify_json_batch";
   const uint32_t st_kind = proof_kind - 1;
   const WDocSpec &ss = w_doc_spec(st_kind), &ps = w_doc_spec(proof_kind);
   const uint64_t kw = n_bits / 32;
@@ -1364,22 +941,7 @@ extern "C" int32_t zkp_sigma_verify_json_batch(zkp_ctx* c, uint32_t proof_kind, 
   uint32_t* nn = (uint32_t*)s.take(B * 2 * kw * 4);
   uint8_t* dstat2 = (uint8_t*)s.take(B);
   int32_t st = s.st;
-  c->scan_fast = c->scan_fallback = 0; c->scan_phases = 0;
-  if (!st) st = scan_event(c, 0);
-  ScanText up{};
-  if (!st) {
-    uint64_t lo = ~0ull, hi = 0;
-    scan_span(st_off, st_len, B, &lo, &hi);
-    scan_span(pf_off, pf_len, B, &lo, &hi);
-    st = scan_upload(c, s, text, lo, hi, &up);
-  }
-  if (!st) st = scan_event(c, 1);
-  zkp_range_ni_proofs d{};
-  d.n_bits = n_bits; d.batch = B; d.n_stride = kw;
-  if (!st) st = json_scan(c, s, name, st_kind, text, st_off, st_len, bigint_forms, d, nullptr, dstat, 0, &up, S);
-  if (!st) st = scan_event(c, 2);
-  if (!st) st = json_scan(c, s, name, proof_kind, text, pf_off, pf_len, bigint_forms, d, nullptr, dstat2, 0, &up, P);
-  if (!st) st = scan_event(c, 3);
+  if (!st) st = scan_pairs(c, s, "zkp_sigma_verify_json_batch", text, st_kind, st_off, st_len, S, dstat, proof_kind, pf_off, pf_len, P, dstat2, B, n_bits, 0, bigint_forms);
   if (!st) {
     hipLaunchKernelGGL(k_square_words, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, c->stream, (const uint32_t*)S[0], kw, (int)kw, B, nn);
     dom.kw = (uint32_t)kw; dom.nn = nn; dom.B = B; dom.proof_status = dstat2; dom.status = dstat;
@@ -1395,13 +957,5 @@ extern "C" int32_t zkp_sigma_verify_json_batch(zkp_ctx* c, uint32_t proof_kind, 
       default: st = zkp_mul_proof_verify_batch(c, n_bits, B, S[0], kw, S[1], S[2], S[3], P[0], P[1], P[2], P[3], P[4], dv, F); break;
     }
   }
-  if (!st) {
-    hipLaunchKernelGGL(k_scan_mask_verdicts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)dstat, dv, B);
-    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_mask_verdicts launch"; }
-  }
-  if (!st) st = scan_event(c, 4);
-  if (st && !s.st) s.st = st;
-  const int32_t fin = s.finish();
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !st) { st = ZKP_EDEVICE; c->err = "stream sync"; }
-  return st ? st : fin;
+  return verify_end(c, s, st, dstat, dv, B);
 } ZKP_CATCH(c)
