@@ -69,3 +69,51 @@ def test_dlog_matches_oracle(ctx, oracle, n_bits):
     vb = np.full((B + 2) * tiles, 9, np.uint8)
     ctx.dlog_verify(n_bits, yb, (B + 2) * tiles, *big, vb)
     assert np.array_equal(vb, np.tile(vo, tiles))
+
+
+# ---- the shapes the tests above leave out (tests/dlog_cases.py; the cases themselves are checked on the CPU by tests/test_dlog_cases.py) ----
+# One batch of 70 rows per shape: honest proofs under several keys and at the prover's arithmetic edges, verify-only edits, the rows the
+# reference panics on, N = 2^128 + 1.  Responses of length 0, 1, ~513 and y_bits sit side by side in every claim of the first 32 rows, and
+# rows 64 ... 69 — the second block of k_dlog_hash, the last and ragged claim of the merged launch — hold all three verdicts.
+
+import dlog_cases as D  # noqa: E402
+
+
+@pytest.mark.parametrize("n_bits,y_bits", D.SHAPES)
+def test_dlog_prove_cases(ctx, oracle, n_bits, y_bits):
+    """x = g^r mod N and y = r + e*s of every row with a witness, byte for byte the oracle's; every word of both outputs is written"""
+    N, g, ni, s, r, xo, yo = D.witness_arrays(D.build(n_bits, y_bits, oracle), n_bits, y_bits)
+    B = N.shape[0]
+    xg = np.full_like(xo, 0xA5A5A5A5); yg = np.full_like(yo, 0xA5A5A5A5)
+    ctx.dlog_prove(n_bits, y_bits, B, N, g, ni, s, r, xg, yg)
+    bad = [b for b in range(B) if not (np.array_equal(xo[b], xg[b]) and np.array_equal(yo[b], yg[b]))]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("n_bits,y_bits", D.SHAPES)
+def test_dlog_verify_cases(ctx, oracle, n_bits, y_bits):
+    """the verdicts of the whole batch (two blocks of k_dlog_hash, a ragged last claim of both segments of the merged launch) and of its
+    prefixes one item past one claim — claims are 32 / 16 / 8 / 4 items up to 2048 bits, 16 / 8 / 4 / 2 at 4096 — and of one proof alone"""
+    rows = D.build(n_bits, y_bits, oracle)
+    arrs = D.arrays(rows, n_bits, y_bits)
+    vo = D.oracle_verdicts(n_bits, y_bits, oracle)
+    for B in (D.ROWS, 17 if n_bits == 4096 else 33, 1):
+        vg = np.full(B, 9, np.uint8)
+        ctx.dlog_verify(n_bits, y_bits, B, *(a[:B] for a in arrs), vg)
+        assert np.array_equal(vo[:B], vg), (B, [(rows[b][0], int(vo[b]), int(vg[b])) for b in range(B) if vo[b] != vg[b]])
+
+
+def test_dlog_verify_cases_one_stream(ctx, oracle):
+    """4096-bit keys on the path of a call that fills the GPU (batch > 16 CUs): pre-checks and challenge in one k_dlog_hash launch on the one
+    stream, one launch per exponentiation.  The smallest number of tiles of the batch of 70 that crosses that bound on this board."""
+    import torch
+    n_bits, y_bits = 4096, 768
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tiles = 16 * cus // D.ROWS + 1
+    assert tiles * D.ROWS > 16 * cus >= (tiles - 1) * D.ROWS
+    big = [np.tile(a, (tiles, 1)) for a in D.arrays(D.build(n_bits, y_bits, oracle), n_bits, y_bits)]
+    vo = np.tile(D.oracle_verdicts(n_bits, y_bits, oracle), tiles)
+    vg = np.full(tiles * D.ROWS, 9, np.uint8)
+    ctx.dlog_verify(n_bits, y_bits, tiles * D.ROWS, *big, vg)
+    bad = np.nonzero(vo != vg)[0]
+    assert bad.size == 0, (bad.size, [(int(b), int(vo[b]), int(vg[b])) for b in bad[:8]])
