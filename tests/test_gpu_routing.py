@@ -1,13 +1,13 @@
 """The library's OWN choice of kernels — nothing pinned, $ZKP_BASEN not set — at the batch sizes where it flips, against the oracle.
 
-A RangeProofNi call at n = 2048 under one key is served by one of these kernel families (csrc/zkp_api.hip: route_latency, launch_basen):
+A RangeProofNi call at n = 2048 under one key is served by one of these kernel families (csrc/route_plan.hpp: route_engine, basen_plan):
   * the latency engine (9 limbs per lane, libzkp_hip_lat.so) up to 96 proofs: ONE Enc per wavefront on the five-group base-n ladder
     (k_enc_basen_r2l) up to 8 proofs, the window ladder on the n^2-sized product up to 16, 8 Enc per wavefront in base-n form
     (k_enc_basen<8>) from there on — except
   * 41 ... 64 and 129 ... 192 proofs: the mid engine (18 limbs per lane, libzkp_hip_mid.so), 16 Enc per wavefront in base-n form,
   * 65 ... 96 proofs: TWO concurrent calls — up to 64 proofs on the mid engine, at least 16 on a second ctx of the latency engine —,
     and 17 ... 20 proofs: 16 on the latency engine's window ladder, the rest beside them on its one-Enc-per-wavefront ladder
-    (csrc/zkp_api_proofs.inc: range_split_plan / range_split_run; zkp_diag_last_split),
+    (csrc/route_plan.hpp: range_split, csrc/zkp_api_proofs.inc: range_split_run; zkp_diag_last_split),
   * the throughput engine's base-n kernels (k_enc_basen<2>, 32 Enc per wavefront) beyond,
   * its n^2-sized kernels (k_enc<4, .>) for keys the form does not take and for launches pinned to that engine that leave SIMDs idle.
 The parity suites pin each family in turn (tests/conftest.py: ctx); this file lets the library choose, says which family it expects for
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import routing_model as R
 from helpers import L
 
 zkp = H.zkp
@@ -42,37 +43,12 @@ def compute_units():
 
 
 def expected_family(c, items, listed=False):
-    """what csrc/zkp_api.hip is expected to pick for a Paillier launch of `items` Enc under ONE 2048-bit key that the base-n form takes
-    (route_latency with one_key_paillier, launch_basen of either engine).  listed: `items` is the bound of a verify's work list — three
-    quarters of it (+ 3 %) are expected to exist, and the mid engine's one-round window is judged by that (csrc/zkp_api.hip expected_items)"""
-    lat, mid = c.latency_limbs_per_lane(), c.mid_limbs_per_lane()
-    simds = 4 * compute_units()
-    one_round = items <= 16 * simds or (listed and (3 * items + 3) // 4 + items // 32 <= 16 * simds)
-    lat_round = listed and (3 * items + 3) // 4 + items // 32 <= 8 * simds      # a verify that fits one round of the latency engine's k_enc_basen<8>
-    if lat == 9 and mid == 18 and ((16 * simds < items <= 24 * simds and not one_round) or 4 * simds < items <= 5 * simds or (8 * simds < items <= 9 * simds and not lat_round)
-                                  or (not listed and 32 * simds < items <= 40 * simds)):
-        return "split"                                         # two concurrent calls (expected_tail below)
-    if mid == 18 and ((10 * simds < items and one_round) or 32 * simds < items <= 48 * simds):
-        return "mid-basen"                                     # 16 Enc per wavefront: one (two) wavefronts per SIMD of the mid engine
-    if lat == 9 and items <= 3 * simds * 8:                    # the latency engine: up to three wavefronts per SIMD at 8 Enc per wavefront
-        if (min(items, (3 * items + 3) // 4 + items // 32) if listed else items) <= 2 * simds:
-            return "lat-r2l"                                   # one Enc per wavefront, the five-group ladder (kernels_basen_r2l.hpp); a verify by its expected items (9, 10 proofs)
-        return "lat-basen" if items > simds * 4 else "lat-n2"
-    return "base-n" if items > simds * 16 else "n2"
+    """tests/routing_model.py for the device and the engines of this ctx"""
+    return R.expected_family(compute_units(), c.latency_limbs_per_lane(), c.mid_limbs_per_lane(), items, listed)
 
 
 def expected_tail(B):
-    """proofs of a split call that run on the second latency-engine ctx (csrc/zkp_api_proofs.inc: range_split_plan; 256 Enc per proof)"""
-    simds = 4 * compute_units()
-    full, least = 16 * simds // 256, 4 * simds // 256
-    if B * 256 <= 5 * simds:
-        return B - least                                       # 17 ... 20 proofs: 16 on the window ladder, the rest on the one-Enc-per-wavefront ladder
-    if B * 256 <= 9 * simds:
-        return B - 8 * simds // 256                            # 33 ... 36 proofs (prove): 32 on k_enc_basen<8>, the rest on the one-Enc-per-wavefront ladder
-    if B * 256 > 32 * simds:
-        t = B - 32 * simds // 256                              # 129 ... 160 proofs (prove): 128 on the throughput engine, the rest beside them on the latency engine
-        return 2 * simds // 256 + 1 if 3 * simds // 2 < t * 256 <= 2 * simds else t      # (not 7 or 8 proofs: the r2l ladder's workgroups would not fit beside the head)
-    return B - full if B - full >= least else least            # 65 ... 96: 64 on the mid engine | at least 16 on the latency engine
+    return R.expected_tail(compute_units(), B)
 
 
 def family_that_ran(c):
@@ -191,8 +167,7 @@ def test_enc_launch_threshold(actx):
         actx.set_geometry(0)
 
 
-def expected_family_throughput(cus, items):
-    return "base-n" if items > 4 * cus * 16 else "n2"
+expected_family_throughput = R.expected_family_throughput
 
 
 def test_the_environment_is_read_once_at_ctx_create(actx):
@@ -276,7 +251,7 @@ def test_one_proof_verify_carries_its_transcript_hash_inside_the_enc_launch(actx
     actx.set_enc_form("auto")
     for B, ef in ((1, 128), (3, 40), (2, 64), (2, 128), (4, 128), (5, 128), (6, 128), (8, 128), (10, 128), (60, 4), (200, 1)):      # (the last two: many short transcripts — many hash workgroups in front of few Enc workgroups)
         five = 2 * ef * B <= compute_units()                       # k_enc_basen_r2l5; beyond: one wavefront per Enc, hashes aboard up to one per SIMD
-        bound = 2 * ef * B                                         # (csrc/zkp_api.hip r2l_one_per_simd: three quarters of the bound exist, + 3 %)
+        bound = 2 * ef * B                                         # (csrc/route_plan.hpp r2l_one_per_simd: three quarters of the bound exist, + 3 %)
         one_per_simd = (3 * bound + 3) // 4 + bound // 32 + B <= 4 * compute_units()
         takes = five or one_per_simd or min(bound, (3 * bound + 3) // 4 + bound // 32) <= 8 * compute_units()      # (two wavefronts per SIMD: the hashes aboard at 16 blocks per batch)
         cases = H.build_range_case(b"fused-hash-%d-%d" % (B, ef), [n], n_bits, B, ef=ef)

@@ -1,6 +1,6 @@
 """RangeProofNi prove / verify (device-resident, n = 2048, one key) from 1 to 1024 proofs under every kernel family the library has — the
 throughput engine (36 limbs per lane) and the latency engine (9), each with the n^2-sized kernels and in base-n form — and under the
-library's own choice.  One JSON line per size: the table behind the routing rules of csrc/zkp_api.hip (route_latency, launch_basen).
+library's own choice.  One JSON line per size: the table behind the routing rules of csrc/route_plan.hpp (route_engine, basen_plan).
 python tools/dev/size_sweep.py [sizes ...]"""
 import importlib
 import json

@@ -26,15 +26,11 @@
 #include "kernels_serde_scan.hpp"
 #include "kernels_sample.hpp"
 #include "kernels_coprime.hpp"
+#include "route_plan.hpp"             // every size-based decision of this file and of zkp_api_proofs.inc
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
 #include "kernels_basen.hpp"
-#ifndef ZKP_R2L5_ITEMS_PER_CU
-#define ZKP_R2L5_ITEMS_PER_CU 1ull      /* launches of up to this many Enc per compute unit take five wavefronts per Enc (k_enc_basen_r2l5): one proof 13.3 / 9.3 -> 10.2 / 6.0 ms;
-                                           two proofs (two workgroups per CU) 13.8 / 9.6 against 13.9 / 9.7 on one wavefront per Enc, but the verify time is bimodal there (9.6 or 12.4 ms:
-                                           a transcript-hash wavefront that shares its SIMD with three others); three: 17.7 / 13.4 against 13.9 / 9.9 (profiles/r05/r2l5/) */
-#endif
-#include "kernels_basen_r2l.hpp"      // (W = 9 only: one Enc per wavefront, the five-group right-to-left ladder of calls of a few proofs)          // the Paillier kernels in base-n form: 2 / 4 lanes per n-sized integer in the throughput engine (W = 36), 8 / 16 in the latency engine (W = 9)
+#include "kernels_basen_r2l.hpp"     // (W = 9 only: one Enc per wavefront, the five-group right-to-left ladder of calls of a few proofs)          // the Paillier kernels in base-n form: 2 / 4 lanes per n-sized integer in the throughput engine (W = 36), 8 / 16 in the latency engine (W = 9)
 #else
 #define ZKP_HAS_BASEN 0
 #endif
@@ -96,7 +92,7 @@ struct zkp_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = true;
-  int cus = 0;
+  RouteKnobs route;                    // the switches and sizes every routing rule reads (route_plan.hpp): compute units, geometry, enc_form, r2l, ...
   // the latency engine's twin of this ctx (same device, same stream); null in the latency engine itself or when it is not loaded
   // (two secondary engines: [0] libzkp_hip_lat.so, 9 limbs per lane — calls of a few proofs; [1] libzkp_hip_mid.so, 18 — mid-size Paillier
   //  calls under one key.  `lat` / `lat_ctx` name the one the current — or most recent — routed call runs on)
@@ -104,7 +100,6 @@ struct zkp_ctx {
   zkp_ctx* eng_ctx[2] = {nullptr, nullptr};
   const struct LatEngine* lat = nullptr;
   zkp_ctx* lat_ctx = nullptr;
-  int geometry = 0;                    // 0 = automatic, else the limbs per lane every call must run on
   int last_geometry = 0;
   // second stream + fork / join events for calls of a few proofs (hash next to the Enc checks); created on first use
   hipStream_t side = nullptr;
@@ -120,34 +115,26 @@ struct zkp_ctx {
   uint64_t scan_fast = 0, scan_fallback = 0;
   hipEvent_t ev_scan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int scan_phases = 0;           // events of ev_scan recorded by that call
-  // A RangeProofNi call of 65 ... 96 proofs under one 2048-bit key runs as TWO concurrent calls (range_split in zkp_api_proofs.inc): one
-  // wavefront per SIMD of the mid engine (64 proofs) on this ctx's stream, the rest on a second ctx of the latency engine with a stream of
-  // its own — created on first use.  $ZKP_SPLIT=0 at zkp_ctx_create / zkp_diag_set_split turn it off.
+  // A RangeProofNi call that route_plan.hpp's range_split cuts runs as TWO concurrent calls (range_split_run in zkp_api_proofs.inc): the head
+  // on this ctx's stream, the rest on a second ctx of the latency engine with a stream of its own — created on first use.
   zkp_ctx* split_ctx = nullptr;
   hipStream_t split_stream = nullptr;
   hipEvent_t ev_split[2] = {nullptr, nullptr};
-  int split_calls = 1;
   int last_split = 0;            // proofs the most recent RangeProofNi call sent to the latency engine beside the mid engine (0: it was not split)
   int key_cache = 1;             // keep the constants of the ONE key of a shared-key call across calls (setup_tag below); $ZKP_KEY_CACHE=0 at zkp_ctx_create or zkp_diag_set_key_cache turn it off
   int host_chunks = -1;          // $ZKP_HOST_CHUNKS at zkp_ctx_create: unset (-1) or 1 = a host-pointer call is one block, N = N equal blocks, 0 = uneven blocks (host_blocks)
   std::string err;
   DevBuf consts, consts2, table, scratch[S_COUNT];
   DevBuf bn_ncst, bn_consts, bn_table, bn_expected, bn_raw, bn_left;
-  int enc_form = ZKP_ENC_FORM_AUTO;    // which Paillier launches take the base-n form (zkp_diag_set_enc_form; $ZKP_BASEN is read ONCE, at zkp_ctx_create)
   int bn_occ[2][2] = {{0, 0}, {0, 0}}; // resident workgroups per CU of k_enc_basen<G> / k_enc_basen_keys<G> ([per-key][n = 4096]; 0: not asked yet)
   int bn_last_g = 0;                   // lanes per n-sized integer of the most recent base-n launch (0: none yet)
   bool bn_last_per_key = false;        // ... and whether it ran under per-proof keys
   bool bn_last_r2l = false;            // ... and whether it was the one-Enc-per-wavefront ladder of the latency engine (kernels_basen_r2l.hpp)
-  int bn_r2l_lanes = 0;                // ... its lane geometry: 0 = the library's rule (five wavefronts of 36 lanes x 2 limbs per Enc while every Enc finds a CU's worth of
-                                       // SIMDs, else one wavefront of five groups of 12 lanes x 6 limbs); 36 / 12 / 8 (x 9 limbs) pin one ($ZKP_R2L_LANES at ctx create, zkp_diag_set_r2l_lanes)
-  int bn_last_r2l_lanes = 0;           // ... and the geometry the most recent such launch ran on
-  int bn_r2l = 1;                      // that ladder: 0 = never, 1 = the library's rule (launches of up to two wavefronts per SIMD), 2 = whenever it can run (tests); $ZKP_R2L at ctx create
+  int bn_last_r2l_lanes = 0;           // ... and the lane geometry (36 / 12 / 8) it ran on
   // The transcript hashes of a verify call of a few proofs as workgroups of its Enc launch (k_enc_basen_r2l5): range_verify_impl names them here
-  // before launch_k_enc, the launch that takes them says so; $ZKP_FUSE_HASH=0 at zkp_ctx_create keeps them in a launch of their own on `side`.
+  // before launch_k_enc, the launch that takes them says so (route.fuse_hash_on = 0 keeps them in a launch of their own on `side`).
   const RangeHashArgs* fuse_hash = nullptr;
   bool fuse_hash_taken = false;
-  int fuse_hash_on = 1;
-  int grid_expected = 1;               // the base-n launch of a verify sized by the items expected, not by the bound (launch_basen); $ZKP_GRID_EXPECTED=0 at zkp_ctx_create: A/B runs
   DevBuf bn_flag;                      // device word: every key of the last batched base-n set-up qualified   // base-n form (kernels_basen.hpp): set-up record of n, its base-n constants, window tables, Mask-row products
   // timing of the dominant kernels
   bool timing = false;
@@ -210,18 +197,6 @@ static int32_t lat_forward_plain(zkp_ctx* c, int32_t st) {
   return st;
 }
 
-// the items a verify's work list is expected to hold when the launch is sized for `bound` (2 per row: an Open row has two Enc checks, a Mask
-// row one, the challenge bits are fair): three quarters, + 3 % (5 proofs: 960 + 40 of 1280; the spread of 5 proofs is 13).
-// A PERFORMANCE assumption only: the prover chooses the response kinds, and the kind-derived list of the two-stream shape holds up to the
-// whole bound — crafted all-Open proofs, about 1.33x the items planned here.  Every launch sized by it claims until the list is empty, so
-// such a verify is slower, its verdicts the same (tests/test_gpu_verify_crafted.py).
-static uint64_t expected_items(uint64_t bound) { return (3 * bound + 3) / 4 + bound / 32; }
-// which of the ctx's secondary engines has this many limbs per lane (-1: none; always -1 inside a secondary engine)
-static int engine_with(const zkp_ctx* c, int limbs_per_lane) {
-  for (int k = 0; k < 2; k++) if (c->eng_ctx[k] && c->eng[k]->limbs_per_lane == limbs_per_lane) return k;
-  return -1;
-}
-
 #ifndef ZKP_SECONDARY_ENGINE
 // directory of this shared library, resolved when it is loaded (a relative load path stops meaning anything once the process
 // changes its working directory)
@@ -267,52 +242,12 @@ static void select_engine(zkp_ctx* c, int k) {
   c->last_geometry = c->lat->limbs_per_lane;
 }
 
-// does this call (items independent modexp chains under mod_bits-bit moduli) go to the latency engine?
-// one_key_paillier: the items are Paillier Enc under ONE 2048-bit key — the latency engine then runs them in base-n form, 8 Enc per wavefront
-// (k_enc_basen<8>), and stays ahead of the throughput engine up to three wavefronts per SIMD.  Measured round 5 (tools/dev/size_sweep.py,
-// profiles/r05/size_sweep.jsonl, prove / verify ms): 48 proofs 43.9 / 43.5 against 49.3 / 44.2 on the n^2-sized throughput kernels, 64 proofs
-// 45.1 / 44.3 against 51.0 / 44.3, 96 proofs 60.7 / 59.7 against 64.9 / 61.6 on the throughput engine's base-n kernels, 128 proofs 76.7 / 74.5
-// against 66.7 / 61.7: the hand-over is at 96 proofs.
-// With the mid engine loaded (18 limbs per lane: 16 Enc per wavefront in base-n form, k_enc_basen<4>) the one-key Paillier calls are cut
-// three ways (same sweep, profiles/r05/size_sweep_w18.jsonl): up to 40 proofs the latency engine (32 proofs 33.1 / 29.5 ms against 40.0 / 38.3),
-// from there to 64 proofs — one wavefront per SIMD at 16 Enc each — the mid engine (64 proofs 41.4 / 38.5 against 45.9 / 44.4), the latency
-// engine again up to 96 (80 proofs 61.1 / 59.7 against 65.2 / 63.9), the throughput engine beyond — except 129 ... 192 proofs, where two mid
-// wavefronts per SIMD beat its second round of 32-Enc claims (160 proofs 90.7 / 67.7 against 111.7 / 66.1, 192: 93.2 / 89.8 against 113.6 / 111.2).
-// `listed`: the items are the bound of a verify's work list (2 per row; about three quarters exist): the mid engine's one-wavefront-per-SIMD
-// window is then judged by the items EXPECTED — its grid is sized by them too (launch_basen) — so that 65 ... 81 proofs verify in one round
-// there (37.4 ms) instead of as two concurrent calls (46.3; tools/dev/two_streams_sweep.py with the engine pinned, profiles/r06/expected_items/).
+// does this call go to a secondary engine (route_plan.hpp: route_engine)?  Then c->lat / c->lat_ctx name it.
 static bool route_latency(zkp_ctx* c, uint64_t items, uint32_t mod_bits, bool one_key_paillier = false, bool listed = false) {
   c->last_geometry = W;
-  if (!c->eng_ctx[0] && !c->eng_ctx[1]) return false;
-  if (c->geometry == W || items == 0) return false;
-  if (c->geometry) {                                              // pinned to a secondary engine
-    const int k = engine_with(c, c->geometry);
-    if (k < 0) return false;
-    select_engine(c, k);
-    return true;
-  }
-  const uint64_t simds = 4 * (uint64_t)c->cus;
-  if (one_key_paillier && mod_bits == 4096 && c->enc_form != ZKP_ENC_FORM_N2) {
-    const int lat9 = engine_with(c, 9), mid18 = engine_with(c, 18);
-    const bool fits_one_round = items <= 16 * simds || (listed && c->grid_expected && expected_items(items) <= 16 * simds);
-    if (mid18 >= 0 && ((items > 10 * simds && fits_one_round) || (items > 32 * simds && items <= 48 * simds))) { select_engine(c, mid18); return true; }
-    if (lat9 >= 0 && items <= 3 * simds * 8) { select_engine(c, lat9); return true; }
-    if (lat9 >= 0) return false;
-  }
-  if (!c->eng_ctx[0]) return false;
-  {
-    // automatic: the latency engine wins while its launch stays within a few wavefronts per SIMD — measured on MI355X
-    // (tools/dev/sweep.py, both engines pinned): RangeProofNi n = 2048 (16 lanes per integer) 48 proofs = 3 waves per SIMD:
-    // 56 ms against 62 ms, 64 proofs: 70 against 63; NiCorrectKeyProof (2048-bit moduli, 8 lanes) 4096 keys = 5.5 per SIMD:
-    // 62 against 70 ms, 8192 keys: 101 against 96; CompositeDLogProof 16384 proofs = 4 per SIMD: 11 against 18 ms
-    const uint64_t limbs = mod_bits <= 2048 ? 72 : mod_bits <= 4096 ? 144 : 288;
-    const uint64_t lanes = limbs / (uint64_t)c->eng[0]->limbs_per_lane;
-    // (round 3, both engines with squarings where their product allows: RangeProofNi n = 2048 32 proofs 40.7 / 37.5 ms against 49.2 / 44.4,
-    // 48 proofs 55.3 / 54.9 against 49.5 / 44.2 -> 2.5 waves per SIMD; NiCorrectKeyProof 4096 keys 56.9 against 59.0 ms, 8192 keys 90 against 81)
-    const uint64_t half_waves_per_simd = mod_bits <= 2048 ? 12 : 5;
-    if (2 * items <= (half_waves_per_simd * 4 * (uint64_t)c->cus * 64) / lanes) { select_engine(c, 0); return true; }
-  }
-  return false;
+  const int k = route_engine(c->route, items, mod_bits, one_key_paillier, listed);
+  if (k >= 0) select_engine(c, k);
+  return k >= 0;
 }
 #define ZKP_ROUTE(c, items, mod_bits, fn, ...)                                              \
   if ((c) && route_latency((c), (items), (mod_bits))) return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__));
@@ -322,7 +257,7 @@ static bool route_latency(zkp_ctx* c, uint64_t items, uint32_t mod_bits, bool on
   if ((c) && route_latency((c), (items), (mod_bits), (one_key), true)) return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__));
 // (diagnostics: only when the caller PINNED the latency engine)
 #define ZKP_ROUTE_PINNED(c, fn, ...)                                                        \
-  if ((c) && (c)->geometry && engine_with((c), (c)->geometry) >= 0) { select_engine((c), engine_with((c), (c)->geometry)); return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__)); }
+  if ((c) && engine_with((c)->route, (c)->route.geometry) >= 0) { select_engine((c), engine_with((c)->route, (c)->route.geometry)); return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__)); }
 #else
 #define ZKP_ROUTE(c, items, mod_bits, fn, ...)
 #define ZKP_ROUTE_ENC(c, items, mod_bits, one_key, fn, ...)
@@ -573,7 +508,7 @@ template <int G> constexpr int N_GROUP = G == GC ? GB : GA;
 template <int G, class K> static int resident_blocks(zkp_ctx* c, K kernel) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, LdsLayout<G>::BYTES_PER_BLOCK) != hipSuccess || per_cu < 1) per_cu = 1;
-  return per_cu * c->cus;
+  return per_cu * c->route.cus;
 }
 
 static int32_t setup_tag(zkp_ctx* c, DevBuf& b, uint64_t count, uint32_t** out) {
@@ -658,17 +593,7 @@ template <int G, class K> static int32_t table_for(zkp_ctx* c, K kernel, uint64_
   return ensure(c, c->table, (size_t)blocks * LL::GROUPS_PER_BLOCK * TAB * Geo<G>::L * sizeof(uint32_t));
 }
 
-// may `items` exponentiations take the pair ladder (two groups of G lanes each)?  Latency engine only, and only while the
-// launch with twice the lanes still leaves every SIMD at most one wavefront (tools/dev/pair_sweep.py on MI355X, RangeProofNi
-// n = 2048: 8 proofs 24.0 / 22.2 ms either way; 12 proofs 27.2 / 22.8 ms on the window ladder, 34.6 / 29.2 ms on pairs that
-// share SIMDs two by two).
-constexpr bool PAIR_LADDER_BUILD = ZKP_W <= 9;            // the pair kernels are instantiated in the latency engine only
-template <int G> static bool pair_ladder(const zkp_ctx* c, uint64_t items) {
-  if (c->enc_form == ZKP_ENC_FORM_ALWAYS) return false;      // (tests that pin the base-n kernels of the latency engine on small batches: they need the window script)
-  if constexpr (PAIR_LADDER_BUILD && 2 * G <= 64) return items * 2 * G <= 4ull * (uint64_t)c->cus * 64;
-  (void)c; (void)items;
-  return false;
-}
+constexpr bool PAIR_LADDER_BUILD = ZKP_W <= 9;            // the pair kernels (route_plan.hpp: pair_ladder) are instantiated in the latency engine only
 
 // k_enc is instantiated per ladder kind: one shared exponent n (sliding-window script) or one key per item (fixed windows).
 // The latency engine has a third: the right-to-left ladder on pairs of groups (kernels_modexp.hpp: powm_pair), taken while a
@@ -693,12 +618,8 @@ extern template __global__ void zkp::k_diag_basen<BN_GA>(const uint32_t*, int, c
 extern template __global__ void zkp::k_diag_basen<BN_GB>(const uint32_t*, int, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, uint32_t*);
 #endif
 constexpr size_t BASEN_DIAG_LDS = 4096;
-// Which Paillier launches take the base-n form is a property of the ctx (include/zkp_hip_diag.h: zkp_diag_set_enc_form):
-//   AUTO   the library's own rule — every launch that fills the chip (launch_basen below), under one key or under per-proof keys
-//   N2     none: every launch stays on the n^2-sized kernels (A/B runs, the parity tests that pin the two forms against each other)
-//   SHARED as AUTO, but launches under per-proof keys stay on the n^2-sized kernels
-//   ALWAYS also the launches too small to gain from it (the parity tests of the small shapes)
-// $ZKP_BASEN (0 | shared | always) presets it when the ctx is created; nothing reads the environment after that.
+// $ZKP_BASEN (0 | shared | always) presets which Paillier launches take the base-n form (route_plan.hpp: basen_plan) when the ctx is created;
+// nothing reads the environment after that.
 static int enc_form_from_env() {
   const char* e = std::getenv("ZKP_BASEN");
   if (e && e[0] == '0') return ZKP_ENC_FORM_N2;
@@ -725,45 +646,36 @@ template <int G> static int32_t basen_prepare(zkp_ctx* c, const uint32_t* n, uin
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
 }
-// Does a launch of the one-wavefront-per-Enc ladder over at most `count` items (`listed`: a verify's work list, of which about three quarters
-// exist) fit one wavefront per SIMD together with `hashes` transcript-hash wavefronts?
-static bool r2l_one_per_simd(const zkp_ctx* c, uint64_t count, bool listed, uint64_t hashes) {
-  const uint64_t simds = 4ull * (uint64_t)c->cus;
-  const uint64_t expect = (listed && c->grid_expected) ? expected_items(count) : count;
-  return hashes < simds && expect + hashes <= simds;
+// resident workgroups per compute unit of k_enc_basen<G> / k_enc_basen_keys<G>: per ctx and per kernel (the two differ in registers, and contexts run on threads of their own)
+template <int G> static int basen_occupancy(zkp_ctx* c, bool per_key) {
+  int& per_cu = c->bn_occ[per_key ? 1 : 0][G == BN_GB ? 1 : 0];
+  if (!per_cu) {
+    const hipError_t e = per_key ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_enc_basen_keys<G>, 256, BnLds<G>::BYTES_PER_BLOCK)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_enc_basen<G>, 256, BnLds<G>::BYTES_PER_BLOCK);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+  }
+  return per_cu;
 }
-// The base-n launch of an Enc call (GS: lanes per n^2-sized integer of the k_enc launch it stands in for).  It claims work from the SAME
-// counter as the k_enc launch that follows it: when the keys qualify it leaves nothing to claim, when they do not it returns at once
-// and k_enc runs as before.  Returns false when nothing was launched.
+// The base-n launch of an Enc call (GS: lanes per n^2-sized integer of the k_enc launch it stands in for), as route_plan.hpp's basen_plan
+// decides it.  It claims work from the SAME counter as the k_enc launch that follows it: when the keys qualify it leaves nothing to claim, when
+// they do not it returns at once and k_enc runs as before.  Returns false when nothing was launched.
 template <int GS> static bool launch_basen(zkp_ctx* c, const EncArgs& a_in, EncArgs* rest) {
   if constexpr (GS != 2 * BN_GA && GS != 2 * BN_GB) { (void)c; (void)a_in; (void)rest; return false; }
   else {
     constexpr int G = GS / 2;
     using BL = BnLds<G>;
+    static_assert(HASH_WAVE_BLOCKS == HW_BLOCKS, "route_plan.hpp names the wave hash's full footprint");
     EncArgs a = a_in;
     const int kw = a.n_bits / 32;
     const bool per_key = a.n_stride != 0;
     c->bn_last_g = 0;                                             // (zkp_diag_basen_last: this launch has not taken the form yet)
-    const int mode = c->enc_form;
-    if (mode == ZKP_ENC_FORM_N2 || (per_key && mode == ZKP_ENC_FORM_SHARED) || a.n_bits != (G == BN_GA ? 2048 : 4096)) return false;
-    // The latency engine's smallest calls — up to two wavefronts per SIMD at ONE Enc per wavefront: 8 proofs at n = 2048 — take the five-group
-    // right-to-left ladder (kernels_basen_r2l.hpp): half the chain of the pair ladder that served them (the launch behind this one, which then
-    // finds nothing to claim).  c->bn_r2l: 0 = never, 1 = the library's rule, 2 = whenever the kernel can take the launch (tests).
-    bool r2l_launch = false;
-    // (a verify's work list: judged by the items expected — 9 and 10 proofs, 2304 / 2560 by the bound, still fit two wavefronts per SIMD: 14.5 ms
-    //  there against 19.2 on the window ladder)
-    const uint64_t r2l_items = (a.count_ptr && a.mode == 1 && c->grid_expected) ? std::min<uint64_t>(a.count, expected_items(a.count)) : a.count;
-#if ZKP_W == 9
-    if constexpr (G == 8)
-      r2l_launch = !per_key && c->bn_r2l && a.n_bits == 2048 && (c->bn_r2l == 2 || (mode != ZKP_ENC_FORM_ALWAYS && r2l_items <= 2ull * 4 * (uint64_t)c->cus));
-#endif
-    if (!per_key && !a.sched && !r2l_launch) return false;       // (a shared key whose launch takes the pair ladder of the latency engine)
-    if (per_key && a.n_stride != (uint64_t)kw) return false;
-    if (a.mode == 0 && ((a.m_words > kw) || (a.r_words > kw))) return false;
-    // A launch whose n^2-sized wavefronts (64 / GS items each) all find a SIMD of their own is a single chain per wavefront either way,
-    // and the base-n chain is the longer one (27.4 M against 22.3 M VALU instructions per claim, for twice the items): measured at
-    // n = 2048, 64 proofs: prove 51 -> 64 ms, verify 45 -> 61 ms; from 96 proofs on: 88 -> 65 ms (profiles/r04/basen/midsize_sweep.jsonl)
-    if (mode != ZKP_ENC_FORM_ALWAYS && !r2l_launch && a.count <= 4ull * (uint64_t)c->cus * (64 / GS)) return false;
+    BasenShape shape;
+    shape.lanes = G; shape.per_key = per_key; shape.key_stride_fits = a.n_stride == (uint64_t)kw; shape.n_bits = a.n_bits; shape.mode = a.mode;
+    shape.count = a.count; shape.listed = a.count_ptr != nullptr; shape.has_sched = a.sched != nullptr; shape.operands_fit = a.m_words <= kw && a.r_words <= kw;
+    shape.hashes_offered = c->fuse_hash != nullptr; shape.hashes = c->fuse_hash ? c->fuse_hash->batch : 0;
+    shape.groups_per_block = BL::GROUPS_PER_BLOCK; shape.per_cu = basen_occupancy<G>(c, per_key);
+    const BasenPlan plan = basen_plan(c->route, shape);
+    if (!plan.take) return false;
     uint64_t nkeys = 1;
     if (per_key) {
       const uint64_t items = (a.mode == 0 && a.half) ? a.half : a.count;
@@ -773,27 +685,9 @@ template <int GS> static bool launch_basen(zkp_ctx* c, const EncArgs& a_in, EncA
     // (any failure below — out of memory for the form's tables — leaves the launch to the n^2-sized kernel behind this one: not an error)
     auto give_up = [&]() { c->err.clear(); *rest = a_in; return false; };      // (`rest`: nothing was taken off the launch behind this one)
     if (basen_prepare<G>(c, a.n, a.n_stride, nkeys, (uint32_t)a.n_bits)) return give_up();
-    int& per_cu = c->bn_occ[per_key ? 1 : 0][G == BN_GB ? 1 : 0];     // per ctx and per kernel: the two differ in registers, and contexts run on threads of their own
-    if (!per_cu) {
-      const hipError_t e = per_key ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_enc_basen_keys<G>, 256, BL::BYTES_PER_BLOCK)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_enc_basen<G>, 256, BL::BYTES_PER_BLOCK);
-      if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    }
     const uint64_t need = (a.count + BL::GROUPS_PER_BLOCK - 1) / BL::GROUPS_PER_BLOCK;
-    uint64_t grid = std::min<uint64_t>(need, (uint64_t)per_cu * c->cus);
-    // A verify's work list (a.count_ptr) holds 128 + the Open rows of every proof — about three quarters — of the 2 Enc per row the launch is
-    // sized for.  A workgroup claims until nothing is left, so the grid only has to hold the items EXPECTED: when those need fewer workgroups
-    // per compute unit than the bound, the launch stops there (40 proofs on the latency engine: 320 workgroups of 32 Enc for 7680 items gave
-    // a quarter of the units a second workgroup, and three calls of six took 27 ... 37 ms instead of 26; 65 ... 81 proofs on the mid engine:
-    // one round, 37.3 ms — profiles/r06/expected_items/).  expected_items: 3 % above the mean.
-    if (a.count_ptr && a.mode == 1 && c->grid_expected) {
-      const uint64_t need_e = (expected_items(a.count) + BL::GROUPS_PER_BLOCK - 1) / BL::GROUPS_PER_BLOCK;
-      const uint64_t per_cu_e = (need_e + (uint64_t)c->cus - 1) / (uint64_t)c->cus;
-      grid = std::min<uint64_t>(grid, per_cu_e * (uint64_t)c->cus);
-    }
-    const unsigned blocks = (unsigned)std::max<uint64_t>(1, grid);
     const size_t entries = per_key ? BN_KEYS_TAB_ENTRIES : BN_TAB_ENTRIES;
-    if (!r2l_launch && ensure(c, c->bn_table, (size_t)blocks * BL::GROUPS_PER_BLOCK * entries * 2 * Geo<G>::L * sizeof(uint32_t))) return give_up();
+    if (!plan.r2l && ensure(c, c->bn_table, (size_t)plan.blocks * BL::GROUPS_PER_BLOCK * entries * 2 * Geo<G>::L * sizeof(uint32_t))) return give_up();
     if (ensure(c, c->bn_raw, (size_t)a.count * 2 * Geo<G>::L * sizeof(uint32_t))) return give_up();
     // the word that says "this launch runs in base-n form": the key's own flag under one key; under per-proof keys the launch always runs
     // (the constant 1 behind the batch's flag) and partitions its items key by key: those of keys the form does not take go on a list that
@@ -812,72 +706,37 @@ template <int GS> static bool launch_basen(zkp_ctx* c, const EncArgs& a_in, EncA
       if (ensure(c, c->bn_expected, (size_t)a.count * 2 * kw * sizeof(uint32_t))) return give_up();
       using LS = LdsLayout<GS>;
       const uint64_t eneed = (a.count + LS::GROUPS_PER_BLOCK - 1) / LS::GROUPS_PER_BLOCK;
-      const unsigned eblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(eneed, 2ull * c->cus));
+      const unsigned eblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(eneed, 2ull * c->route.cus));
       hipLaunchKernelGGL(k_expected<GS>, dim3(eblocks), dim3(256), LS::BYTES_PER_BLOCK, c->stream, a, (uint32_t*)c->bn_expected.p, ok);
     }
-    c->bn_last_g = G; c->bn_last_per_key = per_key; c->bn_last_r2l = r2l_launch;
+    c->bn_last_g = G; c->bn_last_per_key = per_key; c->bn_last_r2l = plan.r2l;
 #if ZKP_W == 9
-    if (r2l_launch) {
+    if (plan.r2l) {
       if constexpr (G == 8) {
-        const unsigned waves = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(a.count, r2l_items < a.count ? std::max<uint64_t>(r2l_items, 2ull * 4 * (uint64_t)c->cus) : 8ull * 4 * (uint64_t)c->cus));
-        // five wavefronts per Enc (36 lanes x 2 limbs each, k_enc_basen_r2l5) while the launch leaves a CU to every Enc: one proof;
-        // one wavefront of five groups of 12 lanes x 6 limbs beyond; 8 lanes x 9 limbs only when pinned (A/B runs)
-        const int lanes = c->bn_r2l_lanes ? c->bn_r2l_lanes : (a.count <= ZKP_R2L5_ITEMS_PER_CU * (uint64_t)c->cus ? 36 : 12);
-        c->bn_last_r2l_lanes = lanes;
-        if (lanes == 36) {
-          // (with the call's transcript hashes aboard: one workgroup each in front of the Enc workgroups, the launch as a whole within one workgroup per
-          //  compute unit — an Enc workgroup claims items until none is left, so fewer of them than items is only a longer loop for some)
-          RangeHashArgs h{};
-          uint64_t enc_wgs = std::max<uint64_t>(1, std::min<uint64_t>(a.count, 4ull * (uint64_t)c->cus));
-          size_t dyn = 0;
-          if (c->fuse_hash && c->fuse_hash->batch < (uint64_t)c->cus) {
-            h = *c->fuse_hash;
-            c->fuse_hash_taken = true;
-            enc_wgs = std::max<uint64_t>(1, std::min<uint64_t>(enc_wgs, (uint64_t)c->cus - h.batch));
-            dyn = (size_t)hw_lds_words((int)h.kw) * sizeof(uint32_t);
-          }
-          hipLaunchKernelGGL(k_enc_basen_r2l5, dim3((unsigned)(h.batch + enc_wgs)), dim3(320), dyn, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_raw.p, h);
+        c->bn_last_r2l_lanes = plan.r2l_lanes;
+        // the call's transcript hashes aboard, one workgroup each in front of the Enc workgroups, where the plan places them
+        RangeHashArgs h{};
+        size_t dyn = 0;
+        if (plan.hash_blocks) {
+          h = *c->fuse_hash;
+          c->fuse_hash_taken = true;
+          if (plan.r2l_lanes != 36) h.wave_blocks = (uint32_t)plan.hash_blocks;
+          dyn = (size_t)(plan.hash_blocks == 16 ? hw_lds_words<16>((int)h.kw) : hw_lds_words<HW_BLOCKS>((int)h.kw)) * sizeof(uint32_t);
         }
-        else {
-          // one wavefront per Enc: the call's transcript hashes aboard — at 64 blocks per batch while the launch as a whole stays within one
-          // wavefront per SIMD (2 - 5 proofs), at 16 (6.6 KB of LDS on every workgroup) beyond (6 - 8 proofs: two wavefronts per SIMD)
-          // (a verify's work list holds 128 + the Open rows of every proof — about 192 — of the 256 Enc per proof the launch is sized for: while the
-          //  items EXPECTED fit one wavefront per SIMD the grid stops there — five proofs: 960 of 1280 — and a wavefront claims until none is left)
-          RangeHashArgs h{};
-          uint64_t enc_wgs = waves;
-          size_t dyn = 0;
-          const uint64_t simds = 4ull * (uint64_t)c->cus;
-          const uint64_t hashes = c->fuse_hash ? c->fuse_hash->batch : 0;
-          if (r2l_one_per_simd(c, a.count, a.count_ptr != nullptr, hashes)) {
-            enc_wgs = std::max<uint64_t>(1, std::min<uint64_t>(enc_wgs, simds - hashes));
-            if (c->fuse_hash) {
-              h = *c->fuse_hash;
-              h.wave_blocks = HW_BLOCKS;
-              c->fuse_hash_taken = true;
-              dyn = (size_t)hw_lds_words<HW_BLOCKS>((int)h.kw) * sizeof(uint32_t);
-            }
-          } else if (c->fuse_hash && hashes < simds && r2l_items <= 2 * simds) {
-            // two wavefronts per SIMD: the hashes among them (the first workgroups) instead of beside them — with the small LDS footprint
-            h = *c->fuse_hash;
-            h.wave_blocks = 16;
-            c->fuse_hash_taken = true;
-            enc_wgs = std::max<uint64_t>(1, std::min<uint64_t>(enc_wgs, 2 * simds - hashes));
-            dyn = (size_t)hw_lds_words<16>((int)h.kw) * sizeof(uint32_t);
-          }
-          const dim3 grid((unsigned)(h.batch + enc_wgs));
-          if (lanes == 8) hipLaunchKernelGGL(k_enc_basen_r2l<9>, grid, dim3(64), dyn, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_raw.p, h);
-          else hipLaunchKernelGGL(k_enc_basen_r2l<6>, grid, dim3(64), dyn, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_raw.p, h);
-        }
+        const dim3 grid((unsigned)(h.batch + plan.enc_wgs));
+        if (plan.r2l_lanes == 36) hipLaunchKernelGGL(k_enc_basen_r2l5, grid, dim3(320), dyn, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_raw.p, h);
+        else if (plan.r2l_lanes == 8) hipLaunchKernelGGL(k_enc_basen_r2l<9>, grid, dim3(64), dyn, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_raw.p, h);
+        else hipLaunchKernelGGL(k_enc_basen_r2l<6>, grid, dim3(64), dyn, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_raw.p, h);
       }
     } else
 #endif
     if (per_key)
-      hipLaunchKernelGGL(k_enc_basen_keys<G>, dim3(blocks), dim3(256), BL::BYTES_PER_BLOCK, c->stream, a, (const uint32_t*)c->bn_consts.p, (const uint32_t*)c->bn_consts.p + (size_t)nkeys * BnConst<G>::STRIDE, (uint32_t*)c->bn_table.p,
+      hipLaunchKernelGGL(k_enc_basen_keys<G>, dim3(plan.blocks), dim3(256), BL::BYTES_PER_BLOCK, c->stream, a, (const uint32_t*)c->bn_consts.p, (const uint32_t*)c->bn_consts.p + (size_t)nkeys * BnConst<G>::STRIDE, (uint32_t*)c->bn_table.p,
                          (uint32_t*)c->bn_raw.p);
     else
-      hipLaunchKernelGGL(k_enc_basen<G>, dim3(blocks), dim3(256), BL::BYTES_PER_BLOCK, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_table.p,
+      hipLaunchKernelGGL(k_enc_basen<G>, dim3(plan.blocks), dim3(256), BL::BYTES_PER_BLOCK, c->stream, a, (const uint32_t*)c->bn_consts.p, (uint32_t*)c->bn_table.p,
                          (uint32_t*)c->bn_raw.p);
-    const unsigned fblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(need, 8ull * c->cus));
+    const unsigned fblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(need, 8ull * c->route.cus));
     hipLaunchKernelGGL(k_basen_finish<G>, dim3(fblocks), dim3(256), BL::BYTES_PER_BLOCK, c->stream, a, (const uint32_t*)c->bn_consts.p, ok, per_key ? 1 : 0,
                        (const uint32_t*)c->bn_raw.p, (const uint32_t*)c->bn_expected.p, (const uint32_t*)c->bn_consts.p + (size_t)nkeys * BnConst<G>::STRIDE);
     return true;
@@ -885,22 +744,11 @@ template <int GS> static bool launch_basen(zkp_ctx* c, const EncArgs& a_in, EncA
 }
 #endif
 
-// Will launch_basen<GS> hand a verify launch of at most `count` Enc under the key of this call to k_enc_basen_r2l5 (five wavefronts per Enc, one
-// workgroup per compute unit) or to k_enc_basen_r2l at one wavefront per SIMD — the launches that take the call's transcript hashes aboard?  The same conditions as below, asked ahead of the launch by range_verify_impl; a launch that then does not take
-// the call's transcript hashes aboard (out of memory for the form's buffers) leaves them to a launch of their own.
+// Will launch_basen<GS> take the transcript hashes of a verify launch of at most `count` Enc under the key of this call aboard?  Asked ahead of
+// the launch by range_verify_impl — the SAME plan, of the same shape; a launch that then does not take them (out of memory for the form's
+// buffers) leaves them to a launch of their own.
 template <int GS> static bool basen_r2l_takes_hashes(const zkp_ctx* c, uint64_t n_stride, uint32_t n_bits, uint64_t count, uint64_t hashes) {
-#if ZKP_W == 9
-  if constexpr (GS == 2 * BN_GA) {
-    const int mode = c->enc_form;
-    if (mode == ZKP_ENC_FORM_N2 || n_stride != 0 || n_bits != 2048 || !c->bn_r2l) return false;
-    const uint64_t items = c->grid_expected ? std::min<uint64_t>(count, expected_items(count)) : count;      // (as launch_basen judges a verify's work list)
-    if (!(c->bn_r2l == 2 || (mode != ZKP_ENC_FORM_ALWAYS && items <= 2ull * 4 * (uint64_t)c->cus))) return false;
-    const bool five = c->bn_r2l_lanes ? c->bn_r2l_lanes == 36 : count <= ZKP_R2L5_ITEMS_PER_CU * (uint64_t)c->cus;
-    return five || r2l_one_per_simd(c, count, true, hashes) || (hashes < 4ull * (uint64_t)c->cus && items <= 8ull * (uint64_t)c->cus);  // k_enc_basen_r2l5, or one wavefront per Enc at one or two per SIMD
-  }
-#endif
-  (void)c; (void)n_stride; (void)n_bits; (void)count; (void)hashes;
-  return false;
+  return basen_plan(c->route, verify_shape(c->route, GS / 2, n_stride, n_bits, count, true, hashes)).hash_blocks;
 }
 template <int G> static void launch_k_enc(zkp_ctx* c, unsigned blocks, const EncArgs& a_in) {
   using LL = LdsLayout<G>;
@@ -909,7 +757,7 @@ template <int G> static void launch_k_enc(zkp_ctx* c, unsigned blocks, const Enc
   (void)launch_basen<G>(c, a_in, &a);      // (under per-proof keys `a` now names the items the base-n launch leaves to this one)
 #endif
   if constexpr (PAIR_LADDER_BUILD && 2 * G <= 64) {
-    if (pair_ladder<G>(c, a.count)) {                     // (a.count: an upper bound when the count is device resident, verify work list)
+    if (pair_ladder(c->route, G, a.count)) {                     // (a.count: an upper bound when the count is device resident, verify work list)
       const unsigned pair_blocks = (unsigned)std::max<uint64_t>(1, (a.count + LL::GROUPS_PER_BLOCK / 2 - 1) / (LL::GROUPS_PER_BLOCK / 2));
       hipLaunchKernelGGL((k_enc<G, false, true>), dim3(pair_blocks), dim3(256), LL::BYTES_PER_BLOCK, c->stream, a);
       return;
@@ -931,18 +779,19 @@ static int32_t ctx_create(int32_t device_id, hipStream_t stream, bool own_stream
   if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0) return ZKP_EDEVICE;   // kernels are built for gfx950 only
   zkp_ctx* c = new zkp_ctx();
   c->device = device_id;
-  c->cus = p.multiProcessorCount;
+  c->route.w = W;
+  c->route.cus = p.multiProcessorCount;
   c->last_geometry = W;
 #if ZKP_HAS_BASEN
-  c->enc_form = enc_form_from_env();
+  c->route.enc_form = enc_form_from_env();
 #endif
   if (const char* hc = std::getenv("ZKP_HOST_CHUNKS")) c->host_chunks = std::atoi(hc);
   if (const char* kc = std::getenv("ZKP_KEY_CACHE")) c->key_cache = std::atoi(kc) != 0;
-  if (const char* sp = std::getenv("ZKP_SPLIT")) c->split_calls = std::atoi(sp) != 0;
-  if (const char* rl = std::getenv("ZKP_R2L")) c->bn_r2l = std::atoi(rl);
-  if (const char* fh = std::getenv("ZKP_FUSE_HASH")) c->fuse_hash_on = std::atoi(fh);
-  if (const char* ge = std::getenv("ZKP_GRID_EXPECTED")) c->grid_expected = std::atoi(ge);
-  if (const char* rl = std::getenv("ZKP_R2L_LANES")) { const int v = std::atoi(rl); c->bn_r2l_lanes = (v == 8 || v == 12 || v == 36) ? v : 0; }
+  if (const char* sp = std::getenv("ZKP_SPLIT")) c->route.split_calls = std::atoi(sp) != 0;
+  if (const char* rl = std::getenv("ZKP_R2L")) c->route.r2l = std::atoi(rl);
+  if (const char* fh = std::getenv("ZKP_FUSE_HASH")) c->route.fuse_hash_on = std::atoi(fh);
+  if (const char* ge = std::getenv("ZKP_GRID_EXPECTED")) c->route.grid_expected = std::atoi(ge);
+  if (const char* rl = std::getenv("ZKP_R2L_LANES")) { const int v = std::atoi(rl); c->route.r2l_lanes = (v == 8 || v == 12 || v == 36) ? v : 0; }
   c->owns_stream = own_stream;
   c->stream = stream;
   if (own_stream && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return ZKP_EDEVICE; }
@@ -955,6 +804,7 @@ static int32_t ctx_create(int32_t device_id, hipStream_t stream, bool own_stream
       const int32_t st = eng->p_zkp_ctx_create_on_stream(device_id, (void*)c->stream, &c->eng_ctx[k]);
       if (st) { (void)zkp_ctx_destroy(c); return st; }
       c->eng[k] = eng;
+      c->route.eng_w[k] = eng->limbs_per_lane;
       if (!c->lat_ctx) { c->lat = eng; c->lat_ctx = c->eng_ctx[k]; }
     }
   if (const char* g = std::getenv("ZKP_GEOMETRY")) {                        // testing aid: the same as zkp_ctx_set_geometry
@@ -976,11 +826,11 @@ extern "C" int32_t zkp_ctx_create_on_stream(int32_t device_id, void* hip_stream,
 
 extern "C" int32_t zkp_ctx_set_geometry(zkp_ctx* c, int32_t limbs_per_lane) try {
   if (!c) return ZKP_EINVAL;
-  if (limbs_per_lane != 0 && limbs_per_lane != W && engine_with(c, limbs_per_lane) < 0) {
+  if (limbs_per_lane != 0 && limbs_per_lane != W && engine_with(c->route, limbs_per_lane) < 0) {
     c->err = "zkp_ctx_set_geometry: no engine with " + std::to_string(limbs_per_lane) + " limbs per lane is loaded";
     return ZKP_EINVAL;
   }
-  c->geometry = limbs_per_lane;
+  c->route.geometry = limbs_per_lane;
   return ZKP_OK;
 } ZKP_CATCH(c)
 extern "C" int32_t zkp_ctx_last_geometry(zkp_ctx* c) { return c ? c->last_geometry : 0; }
@@ -1119,19 +969,19 @@ extern "C" int32_t zkp_diag_basen(zkp_ctx* c, uint32_t, const uint32_t*, int32_t
 // which Paillier launches take the base-n form (include/zkp_hip_diag.h); the twin ctx of the latency engine follows
 extern "C" int32_t zkp_diag_set_enc_form(zkp_ctx* c, int32_t form) try {
   if (!c || form < ZKP_ENC_FORM_AUTO || form > ZKP_ENC_FORM_ALWAYS) return ZKP_EINVAL;
-  c->enc_form = form;
+  c->route.enc_form = form;
 #ifndef ZKP_SECONDARY_ENGINE
   for (int k = 0; k < 2; k++) if (c->eng_ctx[k]) (void)c->eng[k]->p_zkp_diag_set_enc_form(c->eng_ctx[k], form);
 #endif
   return ZKP_OK;
 } ZKP_CATCH(c)
-extern "C" int32_t zkp_diag_enc_form(zkp_ctx* c) { return c ? c->enc_form : -1; }
+extern "C" int32_t zkp_diag_enc_form(zkp_ctx* c) { return c ? c->route.enc_form : -1; }
 extern "C" int32_t zkp_diag_last_host_blocks(zkp_ctx* c) { return c ? c->last_host_blocks : -1; }
 extern "C" int32_t zkp_diag_mid_limbs_per_lane(zkp_ctx* c) { return (c && c->eng[1]) ? c->eng[1]->limbs_per_lane : 0; }
 // the one-Enc-per-wavefront ladder of the latency engine (kernels_basen_r2l.hpp): 0 = never, 1 = the library's rule, 2 = whenever it can run
 extern "C" int32_t zkp_diag_set_r2l(zkp_ctx* c, int32_t mode) try {
   if (!c || mode < 0 || mode > 2) return ZKP_EINVAL;
-  c->bn_r2l = mode;
+  c->route.r2l = mode;
 #ifndef ZKP_SECONDARY_ENGINE
   for (int k = 0; k < 2; k++) if (c->eng_ctx[k]) (void)c->eng[k]->p_zkp_diag_set_r2l(c->eng_ctx[k], mode);
 #endif
@@ -1142,7 +992,7 @@ extern "C" int32_t zkp_diag_set_r2l(zkp_ctx* c, int32_t mode) try {
 // did the most recent verify call of the ctx run that way?
 extern "C" int32_t zkp_diag_set_fuse_hash(zkp_ctx* c, int32_t on) try {
   if (!c) return ZKP_EINVAL;
-  c->fuse_hash_on = on != 0;
+  c->route.fuse_hash_on = on != 0;
 #ifndef ZKP_SECONDARY_ENGINE
   for (int k = 0; k < 2; k++) if (c->eng_ctx[k]) (void)c->eng[k]->p_zkp_diag_set_fuse_hash(c->eng_ctx[k], on);
 #endif
@@ -1158,7 +1008,7 @@ extern "C" int32_t zkp_diag_last_fused_hash(zkp_ctx* c) {
 // ... and its lane geometry: 0 = the library's rule, 36 = five wavefronts per Enc, 12 / 8 = one wavefront of five 12- / 8-lane groups
 extern "C" int32_t zkp_diag_set_r2l_lanes(zkp_ctx* c, int32_t lanes) try {
   if (!c || (lanes != 0 && lanes != 8 && lanes != 12 && lanes != 36)) return ZKP_EINVAL;
-  c->bn_r2l_lanes = lanes;
+  c->route.r2l_lanes = lanes;
 #ifndef ZKP_SECONDARY_ENGINE
   for (int k = 0; k < 2; k++) if (c->eng_ctx[k]) (void)c->eng[k]->p_zkp_diag_set_r2l_lanes(c->eng_ctx[k], lanes);
 #endif
@@ -1200,7 +1050,7 @@ extern "C" int32_t zkp_diag_key_cache_state(zkp_ctx* c, int32_t which, uint32_t*
 } ZKP_CATCH(c)
 // calls of 65 ... 96 proofs as two concurrent calls on two engines (range_split): on / off; how many proofs of the most recent
 // RangeProofNi call went to the latency engine beside the mid engine (0: the call was not split)
-extern "C" int32_t zkp_diag_set_split(zkp_ctx* c, int32_t on) { if (!c) return ZKP_EINVAL; c->split_calls = on != 0; return ZKP_OK; }
+extern "C" int32_t zkp_diag_set_split(zkp_ctx* c, int32_t on) { if (!c) return ZKP_EINVAL; c->route.split_calls = on != 0; return ZKP_OK; }
 extern "C" int32_t zkp_diag_last_split(zkp_ctx* c) { return c ? c->last_split : -1; }
 // did the most recent Paillier launch of this ctx run on it?
 extern "C" int32_t zkp_diag_r2l_last(zkp_ctx* c) {
@@ -1263,7 +1113,7 @@ static int32_t modexp_core(zkp_ctx* c, uint32_t exp_bits, uint64_t count, const 
   unsigned blocks = 0;
   int32_t st;
   if constexpr (PAIR_LADDER_BUILD && 2 * G <= 64) {
-    if (pair_ladder<G>(c, count)) {                       // a few items on the latency engine: right-to-left ladder on pairs of groups
+    if (pair_ladder(c->route, G, count)) {                       // a few items on the latency engine: right-to-left ladder on pairs of groups
       unsigned long long* wcp = nullptr;
       if ((st = fresh_work_counter(c, &wcp))) return st;
       ModexpArgs pa{base, exp, exp_stride, (const uint32_t*)c->consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, out, nullptr, count, (int)exp_bits, io_words,
@@ -1313,7 +1163,7 @@ static int32_t modexp_multi(zkp_ctx* c, uint64_t count, bool per_item_mod, std::
   for (const ModexpCall& k : calls) if (k.exp_stride == 0) { c->err = "modexp_multi: per-item exponents only"; return ZKP_EINVAL; }
   int32_t st;
   bool pair = false;
-  if constexpr (PAIR_LADDER_BUILD && 2 * G <= 64) pair = pair_ladder<G>(c, count * calls.size());
+  if constexpr (PAIR_LADDER_BUILD && 2 * G <= 64) pair = pair_ladder(c->route, G, count * calls.size());
   const uint64_t IPW = pair ? 64 / (2 * G) : 64 / G;      // items per claim, as the kernel counts them
   const uint64_t claims = (count + IPW - 1) / IPW * IPW * calls.size();
   if (!pair && (calls.size() == 1 || claims > (uint64_t)resident_blocks<G>(c, k_modexp<G, false, true>) * LL::GROUPS_PER_BLOCK)) {
@@ -1448,7 +1298,7 @@ static int32_t enc_launch(zkp_ctx* c, uint32_t n_bits, uint64_t count, const uin
   a.table = (uint32_t*)c->table.p; a.count = count; a.n_bits = (int)n_bits; a.mode = out ? 0 : 2;
   a.m = m; a.r = r; a.out = out; a.items_per_key = n_stride ? 1 : count; a.m_words = m_words; a.r_words = r_words;
   a.c1 = c1; a.cipher_x = cipher_x; a.verdict = verdict;
-  if (n_stride == 0 && !pair_ladder<G>(c, a.count) && (st = build_schedule(c, n, n_bits, &a.sched))) return st;   // (the pair ladder reads n itself)
+  if (n_stride == 0 && !pair_ladder(c->route, G, a.count) && (st = build_schedule(c, n, n_bits, &a.sched))) return st;   // (the pair ladder reads n itself)
   if ((st = fresh_work_counter(c, &a.work_counter))) return st;
   {
     TimedRegion tr(c, count);

@@ -44,7 +44,7 @@ static int32_t range_hash(zkp_ctx* c, const zkp_range_ni_proofs& p, uint8_t* e, 
   RangeHashArgs a{p.n, p.n_stride, p.c1, p.c2, p.range, kw, p.error_factor, p.batch, e, elen,
                   (uint32_t*)c->scratch[S_T1].p, (uint32_t*)c->scratch[S_T2].p, verdict, ok_value, e_in, e_len_in};
   if (args_only) { *args_only = a; return ZKP_OK; }          // (the caller launches it: the hashes travel with its Enc launch)
-  if (!e_in && p.batch <= 4ull * (uint64_t)c->cus) {
+  if (!e_in && p.batch <= 4ull * (uint64_t)c->route.cus) {
     // a few proofs: one wavefront per proof, the message schedule spread over its lanes (kernels_proofs.hpp: WaveSha)
     hipLaunchKernelGGL(k_range_hash_wave, dim3((unsigned)p.batch), dim3(64), hw_lds_words((int)kw) * sizeof(uint32_t), stream ? stream : c->stream, a);
   } else {
@@ -72,7 +72,7 @@ static int32_t range_prove_impl(zkp_ctx* c, const zkp_range_ni_proofs& p, const 
   unsigned blocks = 0;
   if ((st = table_for<G>(c, k_enc<G, true>, 2 * items, &blocks))) return st;
   const uint8_t* sched = nullptr;
-  if (p.n_stride == 0 && !pair_ladder<G>(c, 2 * items) && (st = build_schedule(c, p.n, p.n_bits, &sched))) return st;   // (the pair ladder reads n itself)
+  if (p.n_stride == 0 && !pair_ladder(c->route, G, 2 * items) && (st = build_schedule(c, p.n, p.n_bits, &sched))) return st;   // (the pair ladder reads n itself)
   {
     // ONE launch over the 2 * B * EF encryptions of both halves: a group takes ~0.1 s per Enc, so every launch
     // ramps up and drains with idle lanes; one ramp instead of two (measured +1.2 % proofs/s)
@@ -196,56 +196,10 @@ static int32_t range_prove_entry(zkp_ctx* c, const char* name, const zkp_range_n
   return st ? st : fin;
 }
 
-// ---- a call of 65 ... 96 proofs under one 2048-bit key as TWO concurrent calls ---------------------------------------------------------
-// The mid engine serves 64 proofs with ONE wavefront per SIMD (16 Enc each: 41 / 39 ms); the 65th proof gives a SIMD its second wavefront
-// and the call 60 ms on whichever engine runs it.  The chip is not full at that point — a lone wavefront leaves a third of its SIMD's
-// issue slots unused — so the call is cut at proof 64: the head runs on the mid engine on the ctx's stream, the tail (1 ... 32 proofs) on a
-// SECOND ctx of the latency engine with a stream of its own, issued from a helper thread (a host-pointer call blocks its thread).  Measured
-// (tools/dev/split_probe.py, one board each): 72 proofs 58.2 / 57.1 -> 53.2 / 41.4 ms prove / verify, 80 proofs 58.6 / 58.0 -> 49.1 / 43.7,
-// 96 proofs 59.5 / 58.6 -> 53.4 / 52.9; beyond 96 proofs two wavefronts per SIMD of one engine are the better deal.  Proofs are
-// independent: the bytes are those of one call (tests/test_gpu_routing.py).
+// ---- a RangeProofNi call as TWO concurrent calls: where route_plan.hpp's range_split cuts it ------------------------------------------------
 #ifndef ZKP_SECONDARY_ENGINE
-struct RangeSplit { uint64_t head = 0; int head_engine = 1; };      // head == 0: the call is not cut
 static RangeSplit range_split_plan(zkp_ctx* c, const zkp_range_ni_proofs* p, uint64_t rows_per_proof, bool listed = false) {
-  RangeSplit none;
-  if (!c || !p || !c->split_calls || c->geometry || c->enc_form != ZKP_ENC_FORM_AUTO || p->n_stride || p->n_bits != 2048 || rows_per_proof == 0) return none;
-  const int lat9 = engine_with(c, 9), mid18 = engine_with(c, 18);
-  if (lat9 != 0 || mid18 != 1) return none;
-  const uint64_t simds = 4 * (uint64_t)c->cus, items = p->batch * rows_per_proof;
-  RangeSplit r;
-  // (a verify whose EXPECTED items fit one wavefront per SIMD of the mid engine is not cut: route_latency sends the whole call there)
-  if (listed && c->grid_expected && items > 16 * simds && expected_items(items) <= 16 * simds) return none;
-  if (items > 16 * simds && items <= 24 * simds) {
-    // head: one wavefront per SIMD of the mid engine at most (16 Enc each); tail: at least one wavefront per SIMD of the latency engine's
-    // window ladder (4 Enc each: 16 proofs) — a tail of a few proofs would run on the one-Enc-per-wavefront ladder, whose 60-lane wavefronts
-    // are the worse neighbours (72 proofs as 64 + 8: 53.0 / 41.4 ms, 80 as 64 + 16: 48.9 / 43.3)
-    const uint64_t full = 16 * simds / rows_per_proof, least_tail = 4 * simds / rows_per_proof;
-    r.head = p->batch - full >= least_tail ? full : (p->batch > least_tail ? p->batch - least_tail : 0);
-    r.head_engine = 1;
-  } else if (items > 8 * simds && items <= 9 * simds && !(listed && c->grid_expected && expected_items(items) <= 8 * simds)) {
-    // 33 ... 36 proofs: the latency engine's k_enc_basen<8> holds 32 proofs at one wavefront of 8 Enc per SIMD (27.8 ms); the 33rd gave a
-    // quarter of the units a second workgroup and the call 39.8 ms.  The rest — 1 ... 4 proofs: one wavefront per SIMD — runs beside the 32 on
-    // the one-Enc-per-wavefront ladder of a second ctx instead: prove 32.6 ... 33.6 ms (a tail of 5 ... 8 proofs: 39.1 — no better than one call;
-    // a verify of that size fits the one round by its expected items and is not cut).  tools/dev/size_sweep.py, profiles/r06/expected_items/
-    r.head = 8 * simds / rows_per_proof;
-    r.head_engine = 0;
-  } else if (!listed && items > 32 * simds && items <= 40 * simds) {
-    // 129 ... 160 proofs, PROVE: the throughput engine holds 128 proofs at one wavefront of 32 Enc per SIMD (60 ms); the 129th gave some SIMDs a
-    // second one and the call 87 ms on whichever engine ran it.  The head — 128 proofs — stays on this ctx, the rest (up to 32 proofs: one
-    // round of the latency engine's k_enc_basen<8>) runs beside it.  head_engine -1 = the throughput engine itself.
-    // Measured (tools/dev/size_sweep.py, profiles/r06/expected_items/): 129 proofs 86.6 -> 64.8 ms, 132: 70.0, 144: 70.4, 160: 77.3 (one call: 87.4 ... 87.8).
-    // A tail of 7 or 8 proofs — 1792 ... 2048 single-wavefront workgroups of the r2l ladder, 12 KB of LDS each — does not fit beside the head's
-    // 78 KB per unit and waits for it (115 ms): such a call is cut one proof beyond that, where the tail is the window ladder's.
-    r.head = 32 * simds / rows_per_proof;
-    const uint64_t tail_items = (p->batch - r.head) * rows_per_proof;
-    if (tail_items > 3 * simds / 2 && tail_items <= 2 * simds) r.head = p->batch - (2 * simds / rows_per_proof + 1);
-    r.head_engine = -1;
-  } else if (items > 4 * simds && items <= 5 * simds) {
-    // 17 ... 20 proofs: the window ladder's full round (16 proofs) on the latency engine, the rest beside it on the one-Enc-per-wavefront ladder
-    r.head = 4 * simds / rows_per_proof;
-    r.head_engine = 0;
-  }
-  return (r.head > 0 && r.head < p->batch) ? r : none;
+  return (c && p) ? range_split(c->route, p->batch, rows_per_proof, p->n_bits, p->n_stride, listed) : RangeSplit();
 }
 static int32_t range_split_ctx(zkp_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
@@ -256,9 +210,9 @@ static int32_t range_split_ctx(zkp_ctx* c) {
     if (st) { c->split_ctx = nullptr; c->err = "the second latency-engine ctx of a split call could not be created"; return st; }
     if (c->timing) (void)c->eng[0]->p_zkp_timing_reset(c->split_ctx, 1);      // (created inside a timed region: it is timed from its first call)
   }
-  (void)c->eng[0]->p_zkp_diag_set_enc_form(c->split_ctx, c->enc_form);
-  (void)c->eng[0]->p_zkp_diag_set_r2l(c->split_ctx, c->bn_r2l);
-  (void)c->eng[0]->p_zkp_diag_set_r2l_lanes(c->split_ctx, c->bn_r2l_lanes ? c->bn_r2l_lanes : 12);      // (beside a head that fills every SIMD the tail keeps ONE wavefront per Enc: the sizes of range_split_plan were measured that way)
+  (void)c->eng[0]->p_zkp_diag_set_enc_form(c->split_ctx, c->route.enc_form);
+  (void)c->eng[0]->p_zkp_diag_set_r2l(c->split_ctx, c->route.r2l);
+  (void)c->eng[0]->p_zkp_diag_set_r2l_lanes(c->split_ctx, c->route.r2l_lanes ? c->route.r2l_lanes : 12);      // (beside a head that fills every SIMD the tail keeps ONE wavefront per Enc: the sizes of range_split were measured that way)
   (void)c->eng[0]->p_zkp_diag_set_key_cache(c->split_ctx, c->key_cache);
   // (the tail runs BESIDE a head that fills the chip: the transcript hashes stay in a launch of their own there — aboard the tail's Enc launch their
   //  22.8 KB of LDS per workgroup no longer fit beside the head's workgroups: 20 proofs verified in 34.7 ms instead of 22.5)
@@ -526,21 +480,13 @@ static int32_t range_verify_impl(zkp_ctx* c, const zkp_range_ni_proofs& p, uint8
   // kind-derived work list run here (k_verify_plan / k_verdict_merge, kernels_proofs.hpp).  Large batches keep one stream:
   // there k_enc owns every register file and the hash would only delay the groups it displaces (measured, DESIGN.md §8).
   const uint64_t enc_blocks = (2 * rows + LdsLayout<G>::GROUPS_PER_BLOCK - 1) / LdsLayout<G>::GROUPS_PER_BLOCK;
-  // Round 6, throughput engine (tools/dev/two_streams_sweep.py, profiles/r06/two_streams_sweep_w36.txt): the second stream pays up to 192 proofs
-  // (-3 ... -4.5 %) and again from 1536 on (-1.6 %; 4096: -0.4 %: the hash of the whole batch, 10 - 18 ms, hides behind the Enc launch); in
-  // between — 224 ... 384 proofs, where the Enc launch needs every resident workgroup slot for its one round — the hash wavefronts hold
-  // registers the Enc workgroups are waiting for: +5 ... +35 %.  The other engines keep the rule their sweeps were made with.
-  const char* two_env = std::getenv("ZKP_TWO_STREAMS");    // A/B switch: 1 = the two-stream shape for every batch size, 0 = never
-  const uint64_t cus = (uint64_t)c->cus;
-  // (latency engine: up to the 40 proofs the library sends it under one key — 16 proofs' worth of workgroups per compute unit and a half more;
-  //  the rule stopped at 32 until the end of round 6, and 33 - 40 proofs paid the hash in front of their Enc launch: 28.4 against 24.3 - 26.1 ms)
-  const bool two_rule = W == 36 ? (enc_blocks <= 3 * cus / 2 || enc_blocks >= 12 * cus) : W == 9 ? enc_blocks <= 5 * cus / 2 : enc_blocks <= 11 * cus / 4;      // (mid engine: up to the 81 ... 88 proofs whose expected items fit its one round)
-  const bool two = rows != 0 && !e_in && (two_env ? two_env[0] == '1' : two_rule);
+  const char* two_env = std::getenv("ZKP_TWO_STREAMS");    // A/B switch, read on every call: 1 = the two-stream shape for every batch size, 0 = never
+  const bool two = rows != 0 && !e_in && two_streams(c->route, enc_blocks, two_env ? (two_env[0] == '1' ? 1 : 0) : -1);
   // One proof on the latency engine (k_enc_basen_r2l5: a workgroup of five wavefronts per Enc, one per compute unit): the hash wavefront travels
   // WITH the Enc launch, as a workgroup of it — a unit to itself — instead of beside it on the second stream, where it shared a SIMD with two
   // role wavefronts one call in four (verify 6.2 or 8.0 ms: profiles/r06/one_proof/).  The row predicates and the merge follow on this stream.
   // The same for 2 - 4 proofs (k_enc_basen_r2l, one wavefront per Enc and at most one per SIMD: 10.0 or 12.5 ms).
-  const bool fuse = two && c->fuse_hash_on && p.batch < cus && basen_r2l_takes_hashes<G>(c, p.n_stride, p.n_bits, 2 * rows, p.batch);
+  const bool fuse = two && c->route.fuse_hash_on && p.batch < (uint64_t)c->route.cus && basen_r2l_takes_hashes<G>(c, p.n_stride, p.n_bits, 2 * rows, p.batch);
   hipStream_t hs = c->stream;
   uint8_t* enc_verdict = verdict;
   if (two) {
@@ -588,7 +534,7 @@ static int32_t range_verify_impl(zkp_ctx* c, const zkp_range_ni_proofs& p, uint8
   a.resp_w1 = p.resp_w1; a.resp_r1 = p.resp_r1; a.resp_w2 = p.resp_w2; a.resp_r2 = p.resp_r2; a.resp_kind = p.resp_kind; a.resp_j = p.resp_j;
   a.c1 = p.c1; a.c2 = p.c2; a.cipher_x = p.ciphertext; a.verdict = enc_verdict;
   a.count_ptr = (const unsigned long long*)c->scratch[S_COUNTER].p; a.ef = EF;
-  if (p.n_stride == 0 && !pair_ladder<G>(c, a.count) && (st = build_schedule(c, p.n, p.n_bits, &a.sched))) return st;
+  if (p.n_stride == 0 && !pair_ladder(c->route, G, a.count) && (st = build_schedule(c, p.n, p.n_bits, &a.sched))) return st;
   if ((st = fresh_work_counter(c, &a.work_counter))) return st;
   {
     TimedRegion tr(c, 0);
@@ -726,7 +672,7 @@ static int32_t ck_verify_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const
   if ((st = run_setup<G>(c, n, kw, (int)kw, 0, batch, c->consts))) return st;
   if ((st = ensure(c, c->scratch[S_MGF], batch * ZKP_CORRECT_KEY_M2 * (kw + 8) * 4))) return st;
   CkHashArgs h{n, kw, batch, salt, salt_len, (uint32_t*)c->scratch[S_MGF].p, verdict, (const uint32_t*)c->scratch[S_PRIMES].p, nprimes};
-  if (batch <= 4ull * (uint64_t)c->cus) hipLaunchKernelGGL(k_ck_hash_wave, dim3((unsigned)batch), dim3(64), 0, c->stream, h);      // a few keys: one wavefront each
+  if (batch <= 4ull * (uint64_t)c->route.cus) hipLaunchKernelGGL(k_ck_hash_wave, dim3((unsigned)batch), dim3(64), 0, c->stream, h);      // a few keys: one wavefront each
   else hipLaunchKernelGGL(k_ck_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
   HIPCHK(c, hipGetLastError());
   const uint64_t items = batch * ZKP_CORRECT_KEY_M2;
@@ -739,7 +685,7 @@ static int32_t ck_verify_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const
     TimedRegion tr(c, items);
     bool launched = false;
     if constexpr (PAIR_LADDER_BUILD && 2 * G <= 64) {
-      if (pair_ladder<G>(c, items)) {                     // a few keys on the latency engine: right-to-left ladder on pairs of groups
+      if (pair_ladder(c->route, G, items)) {                     // a few keys on the latency engine: right-to-left ladder on pairs of groups
         const unsigned pair_blocks = (unsigned)std::max<uint64_t>(1, (items + LL::GROUPS_PER_BLOCK / 2 - 1) / (LL::GROUPS_PER_BLOCK / 2));
         hipLaunchKernelGGL((k_ck_check<G, true>), dim3(pair_blocks), dim3(256), LL::BYTES_PER_BLOCK, c->stream, a);
         launched = true;
@@ -822,7 +768,7 @@ static int32_t dlog_verify_impl(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, ui
   HIPCHK(c, hipMemsetAsync(c->scratch[S_TMP3].p, 0, batch * kw * 4, c->stream));
   // A call that leaves room on the GPU runs the verifier's pre-checks (N > 2^128 and the two GCDs: ~1 ms on one lane per
   // proof, needed only by the final compare) on the second stream, next to the exponentiations; the challenge stays here.
-  const bool two = batch <= 16ull * (uint64_t)c->cus;      // (64 wavefronts of pre-checks at most)
+  const bool two = batch <= 16ull * (uint64_t)c->route.cus;      // (64 wavefronts of pre-checks at most)
   DlogHashArgs h{N, g, ni, x, kw, batch, (uint32_t*)c->scratch[S_DLOG_E].p, verdict, nullptr, nullptr, nullptr, 0, two ? 1u : 3u};
   const dim3 hash_grid((unsigned)((batch + DLOG_THREADS - 1) / DLOG_THREADS));
   const size_t hash_lds = (16 + 2 * kw) * DLOG_THREADS * 4;
