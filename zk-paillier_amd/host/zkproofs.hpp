@@ -21,7 +21,8 @@
 //
 // Rust panics (assert_eq!, index out of bounds, .expect on Err) become C++ exceptions (Panic).
 // Every modular exponentiation runs on the GPU; this layer only samples, hashes small transcripts
-// (NiCorrectKeyProof::proof's MGF), converts BigInt <-> limbs and flattens proofs into batches.
+// (NiCorrectKeyProof::proof's MGF), converts BigInt <-> limbs and flattens proofs into batches (the layouts: range_batch.hpp; their
+// memory: staging.hpp).
 #pragma once
 #include <sys/mman.h>
 
@@ -40,6 +41,7 @@
 
 #include "../../include/zkp_hip.h"
 #include "bigint.hpp"
+#include "range_batch.hpp"
 #include "staging.hpp"
 
 namespace zkproofs {
@@ -242,15 +244,7 @@ inline BigInt compute_digest(std::initializer_list<const BigInt*> items) { Sha25
 }  // namespace detail
 
 // ------------------------------------------------------------------ RangeProofNi
-struct Response {           // src/zkproofs/range_proof.rs:53-78
-  enum Kind { Open, Mask } kind = Open;
-  BigInt w1, r1, w2, r2;    // Open
-  uint8_t j = 0;            // Mask
-  BigInt masked_x, masked_r;
-};
-struct EncryptedPairs { std::vector<BigInt> c1, c2; };   // range_proof.rs:32-39
-struct Proof { std::vector<Response> responses; };       // range_proof.rs:80-81
-
+// (Response, EncryptedPairs, Proof and the batch layout they are flattened into: host/range_batch.hpp)
 class RangeProofNi {
  public:
   static constexpr size_t SECURITY_PARAMETER = ZKP_SECURITY_PARAMETER;   // range_proof_ni.rs:23
@@ -263,47 +257,26 @@ class RangeProofNi {
   struct Statement { BigInt range, ciphertext, secret_x, secret_r; };
 
   // range_proof_ni.rs:47-82 for many provers sharing one key; randomness sampled as range_proof.rs:133-159.
-  // ONE GPU call per batch (round 5; rounds 3 - 4 ran a pipeline of 4 chunks to hide the rebuild of the proof objects behind the next
-  // chunk's call — and paid a launch tail and a copy per chunk for it: 2022 ms of GPU calls against 1794 ms for one call at B = 4096,
-  // measured on one box).  What made the rebuild expensive was never the copying of 0.8 GB of limbs but the first touch of the heap
-  // they go to (3 million small allocations, a quarter of a million page faults): so the proof objects are ALLOCATED AND TOUCHED WHILE
-  // THE GPU WORKS (`prealloc`: every BigInt of every proof at its full capacity, on a few helper threads under the blocking call), and
-  // after the call `fill` only copies limbs into memory that is already there, on all threads.  ZKP_HOST_PIPELINE=N (N > 1) still cuts
-  // the batch into N calls — the next chunk's sampling and the previous chunk's fill then run under a call as well.
-  // chunks of a pipelined batch call, the same in prove_batch and verify_batch: ZKP_HOST_PIPELINE = 0 / 1 (one call) or N (up to N
-  // chunks of >= 1024 proofs); default `dflt`.  (verify_batch alone also knows ZKP_HOST_PIPELINE=uneven: a quarter, then the rest.)
-  static size_t pipeline_chunks(size_t B, size_t dflt) {
-    const char* pe = std::getenv("ZKP_HOST_PIPELINE");
-    size_t want = dflt;
-    if (pe && pe[0] >= '0' && pe[0] <= '9') want = std::max<size_t>(1, (size_t)std::atoi(pe));
-    return std::max<size_t>(1, std::min<size_t>(want, B / 1024));
+  // ONE GPU call per batch.  (Rounds 3 - 4 ran a pipeline of 4 chunks to hide the rebuild of the proof objects behind the next chunk's
+  // call — and paid a launch tail and a copy per chunk for it: 2022 ms of GPU calls against 1794 ms for one call at B = 4096, measured
+  // on one box; measured again before the chunked path was removed: profiles/host_layer/ab.jsonl.)  What made the rebuild expensive was
+  // never the copying of 0.8 GB of limbs but the first touch of the heap they go to (3 million small allocations, a quarter of a million
+  // page faults): so the proof objects are ALLOCATED AND TOUCHED WHILE THE GPU WORKS (`prealloc`: every BigInt of every proof at its full
+  // capacity, on a few helper threads under the blocking call), and after the call the rebuild only copies limbs into memory that is
+  // already there, on all threads.
+  //
+  // The staging of a finished LARGE call (2.2 GB at B = 4096) goes back to the pool / the OS on a thread of its own: unmapping it is tens
+  // of milliseconds that the caller need not wait for.  Small calls (nothing pooled: a single proof is a batch of one) free theirs inline
+  // — no thread per call.  Secret blocks are wiped by the CALLER before this (RangeWitness::wipe_secrets), never only in the background:
+  // a process that exits right after the call must not leave witnesses behind.
+  template <class Staging> static void release_later(std::unique_ptr<Staging> held, bool large) {
+    if (!large) return;                                                                                       // (freed here, by `held` going out of scope)
+    try { std::thread([h = std::move(held)]() mutable { h.reset(); }).detach(); } catch (...) {}              // (no thread: freed here as well)
   }
-  // The staging buffers of a finished LARGE call (2.2 GB at B = 4096) go back to the pool / the OS on a thread of their own: unmapping
-  // them is tens of milliseconds that the caller need not wait for.  Small calls (nothing pooled: a single proof is a batch of one) free
-  // theirs inline — no thread per call.  Secret blocks are wiped by the CALLER before this (wipe_secrets below), never only in the
-  // background: a process that exits right after the call must not leave witnesses behind.
-  template <class Chunks> static void release_later(Chunks&& chunks, bool large) {
-    if (!large) { chunks.clear(); return; }
-    try { std::thread([held = std::move(chunks)]() mutable { held.clear(); }).detach(); } catch (...) {}     // (no thread: freed here, by `chunks` going out of scope)
-  }
-  struct ProveChunk {
-    size_t lo, hi;
-    RawBuf<uint32_t> range, ct, x, r, w1, w2, r1, r2, c1, c2, rw1, rr1, rw2, rr2;
-    RawBuf<uint8_t> kind, jj;
-    std::vector<uint8_t> status;
-    void wipe_secrets() { for (RawBuf<uint32_t>* b : {&x, &r, &w1, &w2, &r1, &r2}) b->wipe_now(); }
-    bool large() const { return c1.pooled(); }
-    // witness = false (prove_batch_seeded): the GPU expands w1, w2, r1, r2 itself, there are no host buffers for them
-    ProveChunk(size_t lo_, size_t hi_, size_t kw, size_t EF, bool witness = true)
-        : lo(lo_), hi(hi_), range((hi_ - lo_) * kw), ct((hi_ - lo_) * 2 * kw), x((hi_ - lo_) * kw, true), r((hi_ - lo_) * kw, true), w1(witness ? (hi_ - lo_) * EF * kw : 0, true),
-          w2(witness ? (hi_ - lo_) * EF * kw : 0, true), r1(witness ? (hi_ - lo_) * EF * kw : 0, true), r2(witness ? (hi_ - lo_) * EF * kw : 0, true) /* witnesses and nonces: wiped on release */, c1((hi_ - lo_) * EF * 2 * kw), c2((hi_ - lo_) * EF * 2 * kw), rw1((hi_ - lo_) * EF * kw), rr1((hi_ - lo_) * EF * kw),
-          rw2((hi_ - lo_) * EF * kw), rr2((hi_ - lo_) * EF * kw), kind((hi_ - lo_) * EF), jj((hi_ - lo_) * EF), status(hi_ - lo_) {}
-  };
   static std::vector<RangeProofNi> prove_batch(const EncryptionKey& ek, const std::vector<Statement>& st) { return prove_batch_impl(ek, st, false); }
   // The same from what the reference's prove takes — statement and secret, nothing else: a fresh 32-byte seed from the operating system per
   // call, expanded into (w1, w2, r1, r2) ON THE GPU (zkp_range_ni_prove_seeded_batch; the stream is defined in include/zkp_hip.h).  No
   // witness is sampled, flattened, uploaded or kept on the host: HostTiming.sample_flatten_ms covers the flattening of the statements only.
-  // Chunks of a ZKP_HOST_PIPELINE call share the seed; chunk [lo, hi) passes first_index = lo, so the proofs are those of one call.
   static std::vector<RangeProofNi> prove_batch_seeded(const EncryptionKey& ek, const std::vector<Statement>& st) { return prove_batch_impl(ek, st, true); }
   struct SeedGuard {      // the seed is worth the whole witness: wiped on every path out of the call
     uint8_t bytes[32];
@@ -319,109 +292,76 @@ class RangeProofNi {
     ek.n.to_limbs(n.data(), kw);
     HostTiming& tm = last_host_timing();
     tm = HostTiming(); tm.proofs = B; tm.threads = host_threads();
-    const size_t chunks = pipeline_chunks(B, 1);
     std::vector<RangeProofNi> out(B);
+    struct Staging {
+      RangeSlab proofs; RangeWitness witness;
+      Staging(size_t B, size_t EF, size_t kw, bool nonces) : proofs(B, EF, kw, RangeSlab::ALL), witness(B, EF, kw, true, nonces) {}
+    };
+    StopWatch sw;
+    std::unique_ptr<Staging> sg(new Staging(B, EF, kw, !seeded));
+    RangeSlab& s = sg->proofs;
+    RangeWitness& w = sg->witness;
+    std::vector<uint8_t> status(B);
 
-    // stage A: sample (range_proof.rs:133-159) and flatten the statements of a chunk
-    auto sample_flatten = [&](ProveChunk& c, unsigned max_threads) {
-      parallel_for(c.hi - c.lo, [&](size_t k) {
-        const size_t b = c.lo + k;
-        st[b].range.to_limbs(&c.range[k * kw], kw); st[b].ciphertext.to_limbs(&c.ct[k * 2 * kw], 2 * kw);
-        st[b].secret_x.to_limbs(&c.x[k * kw], kw); st[b].secret_r.to_limbs(&c.r[k * kw], kw);
-        if (seeded) return;
-        const BigInt third = st[b].range.div_floor(BigInt(3)), two_thirds = BigInt(2) * third;   // range_proof.rs:133-134
-        for (size_t i = 0; i < EF; i++) {
-          BigInt a = BigInt::sample_range(third, two_thirds), cc = a - third;                     // :136-141
-          if (BigInt::coin()) std::swap(a, cc);                                                    // :144-149
-          a.to_limbs(&c.w1[(k * EF + i) * kw], kw); cc.to_limbs(&c.w2[(k * EF + i) * kw], kw);
-          BigInt::sample_below(ek.n).to_limbs(&c.r1[(k * EF + i) * kw], kw);                      // :151-159
-          BigInt::sample_below(ek.n).to_limbs(&c.r2[(k * EF + i) * kw], kw);
-        }
-      }, max_threads);
-    };
-    // stage B: the chunk's 256 Enc per proof, challenges and responses on the GPU (blocking: host buffers)
-    auto gpu = [&](ProveChunk& c) {
-      zkp_range_ni_proofs p{nb, (uint32_t)EF, c.hi - c.lo, 0, n.data(), c.range.data(), c.ct.data(), c.c1.data(), c.c2.data(), c.kind.data(), c.jj.data(),
-                            c.rw1.data(), c.rr1.data(), c.rw2.data(), c.rr2.data()};
-      if (seeded) {
-        e.check(zkp_range_ni_prove_seeded_batch(e.ctx(), &p, c.x.data(), c.r.data(), seed.bytes, c.lo, nullptr, nullptr, c.status.data(), 0), "zkp_range_ni_prove_seeded_batch");
-        return;
+    // stage A: sample (range_proof.rs:133-159) and flatten the statements
+    parallel_for(B, [&](size_t b) {
+      s.put_statement(b, st[b].range, st[b].ciphertext);
+      w.put_secret(b, st[b].secret_x, st[b].secret_r);
+      if (seeded) return;
+      const BigInt third = st[b].range.div_floor(BigInt(3)), two_thirds = BigInt(2) * third;   // range_proof.rs:133-134
+      for (size_t i = 0; i < EF; i++) {
+        BigInt a = BigInt::sample_range(third, two_thirds), cc = a - third;                     // :136-141
+        if (BigInt::coin()) std::swap(a, cc);                                                    // :144-149
+        const BigInt r1 = BigInt::sample_below(ek.n), r2 = BigInt::sample_below(ek.n);          // :151-159
+        w.put_nonces(b * EF + i, a, cc, r1, r2);
       }
-      zkp_range_ni_witness w{c.x.data(), c.r.data(), c.w1.data(), c.w2.data(), c.r1.data(), c.r2.data()};
-      e.check(zkp_range_ni_prove_batch(e.ctx(), &p, &w, nullptr, nullptr, c.status.data(), 0), "zkp_range_ni_prove_batch");
-    };
-    // stage C1, under the GPU call: the proof objects of the chunk at their final shape — every BigInt allocated at full capacity and
-    // zero-filled (the first touch of its pages).  Which rows will be Open and which Mask is not known yet: every row gets the four
-    // fields of an Open response; `fill` moves two of them over for a Mask row and lets the other two go.
+    });
+    tm.sample_flatten_ms = sw.lap();
+    // stage C1, under the GPU call: the proof objects at their final shape — every BigInt allocated at full capacity and zero-filled (the
+    // first touch of its pages).  Which rows will be Open and which Mask is not known yet: every row gets the four fields of an Open
+    // response; RangeSlab::read_response moves two of them over for a Mask row and lets the other two go.
     // (more than a few threads only contend for the address space: measured round 4, 16 threads 674 ms against one 377 ms)
-    auto prealloc = [&](ProveChunk& c, unsigned max_threads) {
-      parallel_for(c.hi - c.lo, [&](size_t k) {
-        RangeProofNi& o = out[c.lo + k];
-        o.ek = ek; o.range = st[c.lo + k].range; o.ciphertext = st[c.lo + k].ciphertext; o.error_factor = EF;
+    auto prealloc = [&] {
+      parallel_for(B, [&](size_t b) {
+        RangeProofNi& o = out[b];
+        o.ek = ek; o.range = st[b].range; o.ciphertext = st[b].ciphertext; o.error_factor = EF;
         o.encrypted_pairs.c1.resize(EF); o.encrypted_pairs.c2.resize(EF); o.proof.responses.resize(EF);
         for (size_t i = 0; i < EF; i++) {
           o.encrypted_pairs.c1[i].l.resize(2 * kw); o.encrypted_pairs.c2[i].l.resize(2 * kw);
           Response& rs = o.proof.responses[i];
           rs.w1.l.resize(kw); rs.r1.l.resize(kw); rs.w2.l.resize(kw); rs.r2.l.resize(kw);
         }
-      }, max_threads);
+      }, std::max(1u, std::min(4u, host_threads() / 2)));
     };
+    std::exception_ptr helper_error;
+    std::thread helper([&] { try { prealloc(); } catch (...) { helper_error = std::current_exception(); } });
+    // stage B: the 256 Enc per proof, challenges and responses on the GPU (blocking: host buffers)
+    StopWatch g;
+    try {
+      zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
+      if (seeded) e.check(zkp_range_ni_prove_seeded_batch(e.ctx(), &p, w.x(), w.r(), seed.bytes, 0, nullptr, nullptr, status.data(), 0), "zkp_range_ni_prove_seeded_batch");
+      else {
+        zkp_range_ni_witness wt = w.abi();
+        e.check(zkp_range_ni_prove_batch(e.ctx(), &p, &wt, nullptr, nullptr, status.data(), 0), "zkp_range_ni_prove_batch");
+      }
+    } catch (...) { helper.join(); throw; }
+    tm.gpu_ms = g.lap();
+    helper.join();
+    if (helper_error) std::rethrow_exception(helper_error);
     // stage C2, after the call: limbs into the memory that is already there (no allocation, no page fault: a copy at memory bandwidth)
-    auto take = [](BigInt& dst, const uint32_t* p, size_t n) { while (n && p[n - 1] == 0) n--; dst.l.assign(p, p + n); dst.neg = false; };
-    auto fill = [&](ProveChunk& c, unsigned max_threads) {
-      parallel_for(c.hi - c.lo, [&](size_t k) {
-        if (c.status[k] != 0) throw Panic("RangeProofNi::prove: malformed (the reference would panic)");
-        RangeProofNi& o = out[c.lo + k];
-        for (size_t i = 0; i < EF; i++) {
-          const size_t t = k * EF + i;
-          take(o.encrypted_pairs.c1[i], &c.c1[t * 2 * kw], 2 * kw);
-          take(o.encrypted_pairs.c2[i], &c.c2[t * 2 * kw], 2 * kw);
-          Response& rs = o.proof.responses[i];
-          take(rs.w1, &c.rw1[t * kw], kw); take(rs.r1, &c.rr1[t * kw], kw);
-          if (c.kind[t] == ZKP_RESP_OPEN) {
-            rs.kind = Response::Open;
-            take(rs.w2, &c.rw2[t * kw], kw); take(rs.r2, &c.rr2[t * kw], kw);
-          } else {
-            rs.kind = Response::Mask; rs.j = c.jj[t];
-            rs.masked_x = std::move(rs.w1); rs.masked_r = std::move(rs.r1);
-            rs.w1.l.clear(); rs.r1.l.clear(); rs.w2.l.clear(); rs.r2.l.clear();      // (zero; w2 / r2 keep their 2 x 256 B: a free() here goes to the
-                                                                                      //  allocating thread's arena and 16 threads queue for its lock)
-          }
-        }
-      }, max_threads);
-    };
-
-    std::vector<std::unique_ptr<ProveChunk>> ch(chunks);
-    auto bounds = [&](size_t k) { return std::make_pair(B * k / chunks, B * (k + 1) / chunks); };
-    StopWatch sw;
-    ch[0].reset(new ProveChunk(bounds(0).first, bounds(0).second, kw, EF, !seeded));
-    sample_flatten(*ch[0], ~0u);
-    tm.sample_flatten_ms = sw.lap();
-    for (size_t k = 0; k < chunks; k++) {
-      std::exception_ptr helper_error;
-      std::thread helper([&, k] {
-        try {
-          const unsigned few = std::max(1u, std::min(4u, host_threads() / 2));
-          prealloc(*ch[k], few);                    // the objects this call's outputs will go to
-          if (k + 1 < chunks) {                     // next chunk's inputs, on a few threads: the GPU call only waits
-            ch[k + 1].reset(new ProveChunk(bounds(k + 1).first, bounds(k + 1).second, kw, EF, !seeded));
-            sample_flatten(*ch[k + 1], std::max(1u, host_threads() / 2));
-          }
-          if (k > 0) { fill(*ch[k - 1], std::max(1u, host_threads() / 2)); ch[k - 1].reset(); }
-        } catch (...) { helper_error = std::current_exception(); }
-      });
-      StopWatch g;
-      try { gpu(*ch[k]); } catch (...) { helper.join(); throw; }
-      tm.gpu_ms += g.lap();
-      helper.join();
-      if (helper_error) std::rethrow_exception(helper_error);
-    }
     sw.lap();
-    fill(*ch[chunks - 1], ~0u);
+    parallel_for(B, [&](size_t b) {
+      if (status[b] != 0) throw Panic("RangeProofNi::prove: malformed (the reference would panic)");
+      RangeProofNi& o = out[b];
+      for (size_t i = 0; i < EF; i++) {             // row by row, in the order prealloc laid the heap out
+        s.read_pair(b * EF + i, o.encrypted_pairs.c1[i], o.encrypted_pairs.c2[i]);
+        s.read_response(b * EF + i, o.proof.responses[i]);
+      }
+    });
     tm.rebuild_ms = sw.lap();
-    bool large = false;
-    for (auto& c : ch) { c->wipe_secrets(); large = large || c->large(); }      // witnesses and nonces: gone before this call returns
-    release_later(std::move(ch), large);
+    w.wipe_secrets();                                   // witnesses and nonces: gone before this call returns
+    const bool large = s.large();
+    release_later(std::move(sg), large);
     return out;
   }
   static RangeProofNi prove(const EncryptionKey& ek, const BigInt& range, const BigInt& ciphertext, const BigInt& secret_x, const BigInt& secret_r) {
@@ -431,8 +371,8 @@ class RangeProofNi {
   // verify_self for many proofs sharing one key (range_proof_ni.rs:109-128).  Every field of a received proof is prover-chosen: any
   // size, either sign (curv::BigInt over GMP; the decimal serde takes a leading '-').  The fixed-width ABI carries kw / 2kw limbs of
   // non-negative values.  So each proof is classified on the host:
-  //   * CANONICAL (every field non-negative and within its width, exactly error_factor rows stored): flattened into the SoA batch,
-  //     ONE zkp_range_ni_verify_batch for all of them;
+  //   * CANONICAL (range_layout_carries: every field non-negative and within its width, exactly error_factor rows stored): flattened
+  //     into the SoA batch, ONE zkp_range_ni_verify_batch for all of them;
   //   * anything else goes through verify_general below: the reference's row logic verbatim on signed host integers, its modular
   //     exponentiations — the Enc of every row that needs one — still batched on the GPU.  Such a proof gets exactly the verdict,
   //     or the panic, the reference reaches for it (tests/golden/signed_cases.json);
@@ -456,104 +396,38 @@ class RangeProofNi {
       for (const auto& kv : votes) if (kv.second > best && kv.first > 0 && kv.first <= 4096) { best = kv.second; EF = kv.first; }
     }
     std::vector<size_t> fast, general;
-    auto canonical = [&](const RangeProofNi& p) {
-      if (p.error_factor != EF || p.proof.responses.size() != EF || p.encrypted_pairs.c1.size() != EF || p.encrypted_pairs.c2.size() != EF) return false;
-      if (!p.range.fits_limbs(kw) || !p.ciphertext.fits_limbs(2 * kw)) return false;
-      for (size_t i = 0; i < EF; i++) {
-        const Response& rs = p.proof.responses[i];
-        if (!p.encrypted_pairs.c1[i].fits_limbs(2 * kw) || !p.encrypted_pairs.c2[i].fits_limbs(2 * kw)) return false;
-        if (rs.kind == Response::Open ? !(rs.w1.fits_limbs(kw) && rs.r1.fits_limbs(kw) && rs.w2.fits_limbs(kw) && rs.r2.fits_limbs(kw))
-                                      : !(rs.masked_x.fits_limbs(kw) && rs.masked_r.fits_limbs(kw))) return false;
-      }
-      return true;
-    };
     HostTiming& tm = last_host_timing();
     tm = HostTiming(); tm.proofs = B; tm.threads = host_threads();
     StopWatch sw;
     std::vector<char> canon(B);
-    parallel_for(B, [&](size_t b) { canon[b] = canonical(*proofs[b]); });
+    parallel_for(B, [&](size_t b) {
+      const RangeProofNi& p = *proofs[b];
+      canon[b] = p.error_factor == EF && range_layout_carries(kw, EF, p.range, p.ciphertext, p.encrypted_pairs, p.proof, true);
+    });
     for (size_t b = 0; b < B; b++) (canon[b] ? fast : general).push_back(b);
     tm.general_proofs = general.size();
     std::vector<Result> out(B, Result(false));
     if (!fast.empty()) {
-      // ONE GPU call by default.  The batch CAN run as a pipeline of chunks (ZKP_HOST_PIPELINE=N: while the GPU verifies chunk k, a helper
-      // thread flattens chunk k + 1; ZKP_HOST_PIPELINE=uneven: a quarter, then the rest; 0 and 1: one call, as in prove_batch), but what a chunk hides is small — flattening 0.78 GB of
-      // received proofs takes 13 ms on 16 threads now that the staging memory is huge-page backed (95 ms in round 4: first-touch faults) —
-      // and every extra launch has a tail of its own.  B = 4096, one box, round 5: one call 3025 verifies/s, a quarter + the rest 2940,
-      // 2 / 4 equal chunks 2938 / 2650.
+      // ONE GPU call.  What a pipeline of chunks could hide is small — flattening 0.78 GB of received proofs takes 13 ms on 16 threads now
+      // that the staging memory is huge-page backed (95 ms in round 4: first-touch faults) — and every extra launch has a tail of its
+      // own.  B = 4096, one box, round 5: one call 3025 verifies/s, a quarter + the rest 2940, 2 / 4 equal chunks 2938 / 2650.
       const size_t F = fast.size();
-      struct VerifyChunk {
-        size_t lo, hi;
-        RawBuf<uint32_t> range, ct, c1, c2, rw1, rr1, rw2, rr2;
-        RawBuf<uint8_t> kind, jj;
-        std::vector<uint8_t> verdict;
-        VerifyChunk(size_t lo_, size_t hi_, size_t kw, size_t EF)
-            : lo(lo_), hi(hi_), range((hi_ - lo_) * kw), ct((hi_ - lo_) * 2 * kw), c1((hi_ - lo_) * EF * 2 * kw), c2((hi_ - lo_) * EF * 2 * kw), rw1((hi_ - lo_) * EF * kw),
-              rr1((hi_ - lo_) * EF * kw), rw2((hi_ - lo_) * EF * kw), rr2((hi_ - lo_) * EF * kw), kind((hi_ - lo_) * EF), jj((hi_ - lo_) * EF), verdict(hi_ - lo_) {}
-      };
       RawBuf<uint32_t> n(kw);
       ek.n.to_limbs(n.data(), kw);
-      const char* pipe_env = std::getenv("ZKP_HOST_PIPELINE");
-      const bool uneven = pipe_env && pipe_env[0] == 'u' && F >= 2048;
-      const size_t chunks = uneven ? 2 : pipeline_chunks(F, 1);
-      auto flatten = [&](VerifyChunk& c, unsigned max_threads) {
-        parallel_for(c.hi - c.lo, [&](size_t k) {
-          const RangeProofNi& p = *proofs[fast[c.lo + k]];
-          p.range.to_limbs(&c.range[k * kw], kw); p.ciphertext.to_limbs(&c.ct[k * 2 * kw], 2 * kw);
-          for (size_t i = 0; i < EF; i++) {
-            const size_t t = k * EF + i;
-            const Response& rs = p.proof.responses[i];
-            p.encrypted_pairs.c1[i].to_limbs(&c.c1[t * 2 * kw], 2 * kw); p.encrypted_pairs.c2[i].to_limbs(&c.c2[t * 2 * kw], 2 * kw);
-            if (rs.kind == Response::Open) {
-              c.kind[t] = ZKP_RESP_OPEN; c.jj[t] = 0;
-              rs.w1.to_limbs(&c.rw1[t * kw], kw); rs.r1.to_limbs(&c.rr1[t * kw], kw); rs.w2.to_limbs(&c.rw2[t * kw], kw); rs.r2.to_limbs(&c.rr2[t * kw], kw);
-            } else {
-              c.kind[t] = ZKP_RESP_MASK; c.jj[t] = rs.j;
-              rs.masked_x.to_limbs(&c.rw1[t * kw], kw); rs.masked_r.to_limbs(&c.rr1[t * kw], kw);
-              std::fill(&c.rw2[t * kw], &c.rw2[t * kw] + kw, 0u); std::fill(&c.rr2[t * kw], &c.rr2[t * kw] + kw, 0u);
-            }
-          }
-        }, max_threads);
-      };
-      auto gpu = [&](VerifyChunk& c) {
-        zkp_range_ni_proofs p{nb, (uint32_t)EF, c.hi - c.lo, 0, n.data(), c.range.data(), c.ct.data(), c.c1.data(), c.c2.data(), c.kind.data(), c.jj.data(),
-                              c.rw1.data(), c.rr1.data(), c.rw2.data(), c.rr2.data()};
-        e.check(zkp_range_ni_verify_batch(e.ctx(), &p, c.verdict.data(), 0), "zkp_range_ni_verify_batch");
-      };
-      std::vector<std::unique_ptr<VerifyChunk>> ch(chunks);
-      auto bounds = [&](size_t k) {
-        if (uneven) return k == 0 ? std::make_pair(size_t(0), F / 4) : std::make_pair(F / 4, F);
-        return std::make_pair(F * k / chunks, F * (k + 1) / chunks);
-      };
-      ch[0].reset(new VerifyChunk(bounds(0).first, bounds(0).second, kw, EF));
-      flatten(*ch[0], ~0u);
+      std::unique_ptr<RangeSlab> s(new RangeSlab(F, EF, kw, RangeSlab::ALL));
+      std::vector<uint8_t> verdict(F);
+      parallel_for(F, [&](size_t k) {
+        const RangeProofNi& p = *proofs[fast[k]];
+        s->put_statement(k, p.range, p.ciphertext); s->put_pairs(k, p.encrypted_pairs); s->put_proof(k, p.proof);
+      });
       tm.sample_flatten_ms = sw.lap();
-      for (size_t k = 0; k < chunks; k++) {
-        std::exception_ptr helper_error;
-        std::thread helper([&, k] {
-          try {
-            if (k > 0) ch[k - 1].reset();                 // (the release of a quarter of a gigabyte off the critical path as well)
-            if (k + 1 < chunks) {
-              ch[k + 1].reset(new VerifyChunk(bounds(k + 1).first, bounds(k + 1).second, kw, EF));
-              flatten(*ch[k + 1], std::max(1u, host_threads() / 2));
-            }
-          } catch (...) { helper_error = std::current_exception(); }
-        });
-        StopWatch g;
-        try { gpu(*ch[k]); } catch (...) { helper.join(); throw; }
-        tm.gpu_ms += g.lap();
-        helper.join();
-        if (helper_error) std::rethrow_exception(helper_error);
-        const VerifyChunk& c = *ch[k];
-        for (size_t f = c.lo; f < c.hi; f++) {
-          const uint8_t v = c.verdict[f - c.lo];
-          out[fast[f]] = v == ZKP_VERDICT_MALFORMED ? Result::panicked("RangeProofNi::verify: malformed proof (the reference would panic)") : Result(v == ZKP_VERDICT_ACCEPT);
-        }
-      }
-      bool large = false;
-      for (auto& c : ch) large = large || c->c1.pooled();
-      release_later(std::move(ch), large);
-      sw.lap();
+      zkp_range_ni_proofs p = s->abi(nb, n.data(), 0);
+      e.check(zkp_range_ni_verify_batch(e.ctx(), &p, verdict.data(), 0), "zkp_range_ni_verify_batch");
+      tm.gpu_ms = sw.lap();
+      for (size_t k = 0; k < F; k++)
+        out[fast[k]] = verdict[k] == ZKP_VERDICT_MALFORMED ? Result::panicked("RangeProofNi::verify: malformed proof (the reference would panic)") : Result(verdict[k] == ZKP_VERDICT_ACCEPT);
+      const bool large = s->large();
+      release_later(std::move(s), large);
     }
     if (!general.empty()) {
       std::vector<const RangeProofNi*> g;
@@ -697,19 +571,16 @@ struct RangeProof {
       d.w1.push_back(a); d.w2.push_back(c);
       d.r1.push_back(BigInt::sample_below(ek.n)); d.r2.push_back(BigInt::sample_below(ek.n));   // :151-159
     }
-    std::vector<uint32_t> n(kw), w1(EF * kw), w2(EF * kw), r1(EF * kw), r2(EF * kw), c1(EF * 2 * kw), c2(EF * 2 * kw);
+    std::vector<uint32_t> n(kw);
     ek.n.to_limbs(n.data(), kw);
-    for (size_t i = 0; i < EF; i++) {
-      d.w1[i].to_limbs(&w1[i * kw], kw); d.w2[i].to_limbs(&w2[i * kw], kw); d.r1[i].to_limbs(&r1[i * kw], kw); d.r2[i].to_limbs(&r2[i * kw], kw);
-    }
-    zkp_range_ni_proofs p{};
-    p.n_bits = nb; p.error_factor = (uint32_t)EF; p.batch = 1; p.n = n.data(); p.c1 = c1.data(); p.c2 = c2.data();
-    zkp_range_ni_witness w{nullptr, nullptr, w1.data(), w2.data(), r1.data(), r2.data()};
+    RangeSlab s(1, EF, kw, RangeSlab::PAIRS);
+    RangeWitness wt(1, EF, kw, false, true);
+    for (size_t i = 0; i < EF; i++) wt.put_nonces(i, d.w1[i], d.w2[i], d.r1[i], d.r2[i]);
+    const zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
+    const zkp_range_ni_witness w = wt.abi();
     e.check(zkp_range_generate_encrypted_pairs_batch(e.ctx(), &p, &w, 0), "zkp_range_generate_encrypted_pairs_batch");
     EncryptedPairs ep;
-    for (size_t i = 0; i < EF; i++) {
-      ep.c1.push_back(BigInt::from_limbs(&c1[i * 2 * kw], 2 * kw)); ep.c2.push_back(BigInt::from_limbs(&c2[i * 2 * kw], 2 * kw));
-    }
+    s.read_pairs(0, ep);
     return {ep, d};
   }
 
@@ -727,34 +598,21 @@ struct RangeProof {
     const uint32_t nb = width_for(ek.n), kw = nb / 32;
     const size_t EF = error_factor;
     if (d.w1.size() < EF || d.w2.size() < EF || d.r1.size() < EF || d.r2.size() < EF) throw Panic("index out of bounds");   // data.w1[i]
-    std::vector<uint32_t> n(kw), rg(kw), x(kw), r(kw), w1(EF * kw), w2(EF * kw), r1(EF * kw), r2(EF * kw);
-    std::vector<uint32_t> rw1(EF * kw), rr1(EF * kw), rw2(EF * kw), rr2(EF * kw);
-    std::vector<uint8_t> kind(EF), jj(EF);
-    ek.n.to_limbs(n.data(), kw); range.to_limbs(rg.data(), kw); secret_x.to_limbs(x.data(), kw); secret_r.to_limbs(r.data(), kw);
-    for (size_t i = 0; i < EF; i++) {
-      d.w1[i].to_limbs(&w1[i * kw], kw); d.w2[i].to_limbs(&w2[i * kw], kw); d.r1[i].to_limbs(&r1[i * kw], kw); d.r2[i].to_limbs(&r2[i * kw], kw);
-    }
+    std::vector<uint32_t> n(kw);
+    ek.n.to_limbs(n.data(), kw);
+    RangeSlab s(1, EF, kw, RangeSlab::STATEMENT | RangeSlab::RESPONSES);
+    RangeWitness wt(1, EF, kw, true, true);
+    s.put_statement(0, range, BigInt());             // (no prover function reads the ciphertext)
+    wt.put_secret(0, secret_x, secret_r);
+    for (size_t i = 0; i < EF; i++) wt.put_nonces(i, d.w1[i], d.w2[i], d.r1[i], d.r2[i]);
     uint8_t eb[32], elen, status = 0;
     pack_challenge(ch, eb, elen);
-    zkp_range_ni_proofs p{};
-    p.n_bits = nb; p.error_factor = (uint32_t)EF; p.batch = 1; p.n = n.data(); p.range = rg.data();
-    p.resp_kind = kind.data(); p.resp_j = jj.data(); p.resp_w1 = rw1.data(); p.resp_r1 = rr1.data(); p.resp_w2 = rw2.data(); p.resp_r2 = rr2.data();
-    zkp_range_ni_witness w{x.data(), r.data(), w1.data(), w2.data(), r1.data(), r2.data()};
+    const zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
+    const zkp_range_ni_witness w = wt.abi();
     e.check(zkp_range_generate_proof_batch(e.ctx(), &p, &w, eb, &elen, &status, 0), "zkp_range_generate_proof_batch");
     if (status != 0) throw Panic("RangeProof::generate_proof: malformed (the reference would panic: bits_of_e[i])");
     Proof out;
-    for (size_t t = 0; t < EF; t++) {
-      Response rs;
-      if (kind[t] == ZKP_RESP_OPEN) {
-        rs.kind = Response::Open;
-        rs.w1 = BigInt::from_limbs(&rw1[t * kw], kw); rs.r1 = BigInt::from_limbs(&rr1[t * kw], kw);
-        rs.w2 = BigInt::from_limbs(&rw2[t * kw], kw); rs.r2 = BigInt::from_limbs(&rr2[t * kw], kw);
-      } else {
-        rs.kind = Response::Mask; rs.j = jj[t];
-        rs.masked_x = BigInt::from_limbs(&rw1[t * kw], kw); rs.masked_r = BigInt::from_limbs(&rr1[t * kw], kw);
-      }
-      out.responses.push_back(std::move(rs));
-    }
+    s.read_proof(0, out);
     return out;
   }
 
@@ -766,13 +624,7 @@ struct RangeProof {
     const size_t EF = error_factor;
     // values the fixed-width call cannot carry (negative, over-wide), short vectors, a challenge of more than 32 bytes: the reference's
     // row logic on signed host integers with the verifier's own challenge (RangeProofNi::verify_general), Enc still on the GPU
-    bool canonical = proof.responses.size() >= EF && ep.c1.size() >= EF && ep.c2.size() >= EF && ch.bytes.size() <= 32 && range.fits_limbs(kw) && cipher_x.fits_limbs(2 * kw);
-    for (size_t t = 0; canonical && t < EF; t++) {
-      const Response& rs = proof.responses[t];
-      canonical = ep.c1[t].fits_limbs(2 * kw) && ep.c2[t].fits_limbs(2 * kw) &&
-                  (rs.kind == Response::Open ? rs.w1.fits_limbs(kw) && rs.r1.fits_limbs(kw) && rs.w2.fits_limbs(kw) && rs.r2.fits_limbs(kw)
-                                             : rs.masked_x.fits_limbs(kw) && rs.masked_r.fits_limbs(kw));
-    }
+    const bool canonical = ch.bytes.size() <= 32 && range_layout_carries(kw, EF, range, cipher_x, ep, proof, false);
     if (!canonical) {
       RangeProofNi tmp;
       tmp.ek = ek; tmp.range = range; tmp.ciphertext = cipher_x; tmp.encrypted_pairs = ep; tmp.proof = proof; tmp.error_factor = EF;
@@ -781,24 +633,13 @@ struct RangeProof {
       (void)r.is_ok();                          // a panic of the reference is thrown here
       return r;
     }
-    std::vector<uint32_t> n(kw), rg(kw), ct(2 * kw), c1(EF * 2 * kw), c2(EF * 2 * kw), rw1(EF * kw), rr1(EF * kw), rw2(EF * kw), rr2(EF * kw);
-    std::vector<uint8_t> kind(EF), jj(EF);
-    ek.n.to_limbs(n.data(), kw); range.to_limbs(rg.data(), kw); cipher_x.to_limbs(ct.data(), 2 * kw);
-    for (size_t t = 0; t < EF; t++) {
-      ep.c1[t].to_limbs(&c1[t * 2 * kw], 2 * kw); ep.c2[t].to_limbs(&c2[t * 2 * kw], 2 * kw);
-      const Response& rs = proof.responses[t];
-      if (rs.kind == Response::Open) {
-        kind[t] = ZKP_RESP_OPEN;
-        rs.w1.to_limbs(&rw1[t * kw], kw); rs.r1.to_limbs(&rr1[t * kw], kw); rs.w2.to_limbs(&rw2[t * kw], kw); rs.r2.to_limbs(&rr2[t * kw], kw);
-      } else {
-        kind[t] = ZKP_RESP_MASK; jj[t] = rs.j;
-        rs.masked_x.to_limbs(&rw1[t * kw], kw); rs.masked_r.to_limbs(&rr1[t * kw], kw);
-      }
-    }
+    std::vector<uint32_t> n(kw);
+    ek.n.to_limbs(n.data(), kw);
+    RangeSlab s(1, EF, kw, RangeSlab::ALL);
+    s.put_statement(0, range, cipher_x); s.put_pairs(0, ep); s.put_proof(0, proof);
     uint8_t eb[32], elen, verdict = 0;
     pack_challenge(ch, eb, elen);
-    zkp_range_ni_proofs p{nb, (uint32_t)EF, 1, 0, n.data(), rg.data(), ct.data(), c1.data(), c2.data(), kind.data(), jj.data(),
-                          rw1.data(), rr1.data(), rw2.data(), rr2.data()};
+    const zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
     e.check(zkp_range_verifier_output_batch(e.ctx(), &p, eb, &elen, &verdict, 0), "zkp_range_verifier_output_batch");
     if (verdict == ZKP_VERDICT_MALFORMED) throw Panic("RangeProof::verifier_output: malformed proof (the reference would panic)");
     return Result(verdict == ZKP_VERDICT_ACCEPT);
@@ -995,35 +836,10 @@ class CompositeDLogProof {
   static constexpr uint32_t Y_BITS = 768;     // y = r + e*s < 2^513 for honest provers
   BigInt x, y;
   // wi_dlog_proof.rs:46-65
-  static CompositeDLogProof prove(const DLogStatement& st, const BigInt& secret) {
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.N), kw = nb / 32;
-    const BigInt r = BigInt::sample_below(BigInt::pow2(512));     // K + K' + SAMPLE_S = 512, :53-54
-    std::vector<uint32_t> N(kw), g(kw), ni(kw), s(8), rr(16), x(kw), y(Y_BITS / 32);
-    st.N.to_limbs(N.data(), kw); st.g.to_limbs(g.data(), kw); st.ni.to_limbs(ni.data(), kw); secret.to_limbs(s.data(), 8); r.to_limbs(rr.data(), 16);
-    e.check(zkp_dlog_prove_batch(e.ctx(), nb, Y_BITS, 1, N.data(), g.data(), ni.data(), s.data(), rr.data(), x.data(), y.data(), 0), "zkp_dlog_prove_batch");
-    return CompositeDLogProof{BigInt::from_limbs(x.data(), kw), BigInt::from_limbs(y.data(), Y_BITS / 32)};
-  }
+  static CompositeDLogProof prove(const DLogStatement& st, const BigInt& secret);
   // prove for a whole batch from what the reference's prove takes: the 512-bit nonces come from one OS seed, expanded on the GPU
-  static std::vector<CompositeDLogProof> prove_batch_seeded(const std::vector<DLogStatement>& st, const std::vector<BigInt>& secrets) {
-    if (st.size() != secrets.size()) throw std::invalid_argument("CompositeDLogProof::prove_batch_seeded: one secret per statement");
-    const size_t B = st.size();
-    if (B == 0) return {};
-    Engine& e = Engine::instance();
-    RangeProofNi::SeedGuard seed(true);
-    const detail::BatchKeys keys(st.begin(), st.end(), [](const DLogStatement& q) -> const BigInt& { return q.N; });
-    const uint32_t nb = keys.nb, kw = keys.kw, yw = Y_BITS / 32;
-    std::vector<uint32_t> N(B * kw), g(B * kw), ni(B * kw), x(B * kw), y(B * yw);
-    RawBuf<uint32_t> s(B * 8, true);
-    for (size_t b = 0; b < B; b++) {
-      st[b].N.to_limbs(&N[b * kw], kw); st[b].g.to_limbs(&g[b * kw], kw); st[b].ni.to_limbs(&ni[b * kw], kw); secrets[b].to_limbs(s.data() + b * 8, 8);
-    }
-    e.check(zkp_dlog_prove_seeded_batch(e.ctx(), nb, Y_BITS, B, N.data(), g.data(), ni.data(), s.data(), seed.bytes, 0, x.data(), y.data(), nullptr, 0),
-            "zkp_dlog_prove_seeded_batch");
-    std::vector<CompositeDLogProof> out;
-    for (size_t b = 0; b < B; b++) out.push_back(CompositeDLogProof{BigInt::from_limbs(&x[b * kw], kw), BigInt::from_limbs(&y[b * yw], yw)});
-    return out;
-  }
+  static std::vector<CompositeDLogProof> prove_batch_seeded(const std::vector<DLogStatement>& st, const std::vector<BigInt>& secrets);
+  static std::vector<CompositeDLogProof> prove_impl(const DLogStatement* st, const BigInt* secrets, size_t B, bool seeded);
   // base^exp mod N for a non-negative exponent of ANY length (a prover-chosen y is not bounded): exponents wider than the modulus
   // width go through the GPU in chunks, acc = acc^(2^c) * base^chunk, most significant chunk first
   static BigInt mod_pow_wide(const BigInt& base, const BigInt& exp, const BigInt& N) {
@@ -1057,10 +873,10 @@ class CompositeDLogProof {
       const BigInt ni_e = mod_pow(st.ni, ee, st.N), g_y = mod_pow_wide(st.g, y, st.N);                                    // :81-82
       return Result(x == (g_y * ni_e).modulus(st.N));                                                                     // :83-90
     }
-    std::vector<uint32_t> N(kw), g(kw), ni(kw), xx(kw), yy(Y_BITS / 32);
-    st.N.to_limbs(N.data(), kw); st.g.to_limbs(g.data(), kw); st.ni.to_limbs(ni.data(), kw); x.to_limbs(xx.data(), kw); y.to_limbs(yy.data(), Y_BITS / 32);
+    Columns in(1, {{kw, false}, {kw, false}, {kw, false}, {kw, false}, {Y_BITS / 32, false}});
+    in.put_row(0, {&st.N, &st.g, &st.ni, &x, &y});
     uint8_t v = 9;
-    e.check(zkp_dlog_verify_batch(e.ctx(), nb, Y_BITS, 1, N.data(), g.data(), ni.data(), xx.data(), yy.data(), &v, 0), "zkp_dlog_verify_batch");
+    e.check(zkp_dlog_verify_batch(e.ctx(), nb, Y_BITS, 1, in[0], in[1], in[2], in[3], in[4], &v, 0), "zkp_dlog_verify_batch");
     if (v == ZKP_VERDICT_MALFORMED) throw Panic("assertion failed in CompositeDLogProof::verify (N > 2^128, gcd(g,N) = gcd(ni,N) = 1)");   // :69,72,73
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
@@ -1078,44 +894,11 @@ struct ZeroStatement { EncryptionKey ek; BigInt c; };
 class ZeroProof {
  public:
   BigInt z, a;
-  static ZeroProof prove(const ZeroWitness& w, const ZeroStatement& st) {   // :44-64
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32;
-    const BigInt r_prime = BigInt::sample_below(st.ek.n);                     // :45
-    std::vector<uint32_t> n(kw), c(2 * kw), r(kw), rp(kw), z(2 * kw), a(2 * kw);
-    st.ek.n.to_limbs(n.data(), kw); st.c.to_limbs(c.data(), 2 * kw); (w.r % st.ek.nn).to_limbs(r.data(), kw); r_prime.to_limbs(rp.data(), kw);
-    e.check(zkp_zero_proof_prove_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), r.data(), rp.data(), z.data(), a.data(), 0), "zkp_zero_proof_prove_batch");
-    return ZeroProof{BigInt::from_limbs(z.data(), 2 * kw), BigInt::from_limbs(a.data(), 2 * kw)};
-  }
+  static ZeroProof prove(const ZeroWitness& w, const ZeroStatement& st);   // :44-64
   // prove for a whole batch from what the reference's prove takes: every r' comes from one OS seed, expanded on the GPU
-  static std::vector<ZeroProof> prove_batch_seeded(const std::vector<ZeroWitness>& w, const std::vector<ZeroStatement>& st) {
-    if (w.size() != st.size()) throw std::invalid_argument("ZeroProof::prove_batch_seeded: one witness per statement");
-    const size_t B = st.size();
-    if (B == 0) return {};
-    Engine& e = Engine::instance();
-    RangeProofNi::SeedGuard seed(true);
-    const detail::BatchKeys keys(st.begin(), st.end(), [](const ZeroStatement& q) -> const BigInt& { return q.ek.n; });
-    const uint32_t nb = keys.nb, kw = keys.kw;
-    std::vector<uint32_t> c(B * 2 * kw), z(B * 2 * kw), a(B * 2 * kw);
-    std::vector<uint8_t> status(B, 9);
-    RawBuf<uint32_t> r(B * kw, true);
-    for (size_t b = 0; b < B; b++) { st[b].c.to_limbs(&c[b * 2 * kw], 2 * kw); (w[b].r % st[b].ek.nn).to_limbs(r.data() + b * kw, kw); }
-    e.check(zkp_zero_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, c.data(), r.data(), seed.bytes, 0, z.data(), a.data(), status.data(), 0),
-            "zkp_zero_proof_prove_seeded_batch");
-    detail::seeded_status_ok(status, "BigInt::sample_below(0) (zero_enc_proof.rs:45)");
-    std::vector<ZeroProof> out;
-    for (size_t b = 0; b < B; b++) out.push_back(ZeroProof{BigInt::from_limbs(&z[b * 2 * kw], 2 * kw), BigInt::from_limbs(&a[b * 2 * kw], 2 * kw)});
-    return out;
-  }
-  Result verify(const ZeroStatement& st) const {                             // :66-94
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32;
-    std::vector<uint32_t> n(kw), c(2 * kw), zz(2 * kw), aa(2 * kw);
-    st.ek.n.to_limbs(n.data(), kw); st.c.to_limbs(c.data(), 2 * kw); z.to_limbs(zz.data(), 2 * kw); a.to_limbs(aa.data(), 2 * kw);
-    uint8_t v = 9;
-    e.check(zkp_zero_proof_verify_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), zz.data(), aa.data(), &v, 0), "zkp_zero_proof_verify_batch");
-    return Result(v == ZKP_VERDICT_ACCEPT);
-  }
+  static std::vector<ZeroProof> prove_batch_seeded(const std::vector<ZeroWitness>& w, const std::vector<ZeroStatement>& st);
+  static std::vector<ZeroProof> prove_impl(const ZeroWitness* w, const ZeroStatement* st, size_t B, bool seeded);
+  Result verify(const ZeroStatement& st) const;   // :66-94
   // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
   // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
   // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
@@ -1128,47 +911,11 @@ struct CiphertextStatement { EncryptionKey ek; BigInt c; };
 class CiphertextProof {
  public:
   BigInt z1, z2, c_prime;
-  static CiphertextProof prove(const CiphertextWitness& w, const CiphertextStatement& st) {   // :42-64
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32, z1w = kw + ZKP_Z1_EXTRA_LIMBS;
-    const BigInt x_prime = BigInt::sample_below(st.ek.n), r_prime = BigInt::sample_below(st.ek.n);   // :43-44
-    std::vector<uint32_t> n(kw), c(2 * kw), x(kw), r(kw), xp(kw), rp(kw), o1(z1w), o2(2 * kw), oc(2 * kw);
-    st.ek.n.to_limbs(n.data(), kw); st.c.to_limbs(c.data(), 2 * kw); w.x.to_limbs(x.data(), kw); w.r.to_limbs(r.data(), kw);
-    x_prime.to_limbs(xp.data(), kw); r_prime.to_limbs(rp.data(), kw);
-    e.check(zkp_ciphertext_proof_prove_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), x.data(), r.data(), xp.data(), rp.data(), o1.data(), o2.data(), oc.data(), 0),
-            "zkp_ciphertext_proof_prove_batch");
-    return CiphertextProof{BigInt::from_limbs(o1.data(), z1w), BigInt::from_limbs(o2.data(), 2 * kw), BigInt::from_limbs(oc.data(), 2 * kw)};
-  }
+  static CiphertextProof prove(const CiphertextWitness& w, const CiphertextStatement& st);   // :42-64
   // prove for a whole batch from what the reference's prove takes: every (x', r') comes from one OS seed, expanded on the GPU
-  static std::vector<CiphertextProof> prove_batch_seeded(const std::vector<CiphertextWitness>& w, const std::vector<CiphertextStatement>& st) {
-    if (w.size() != st.size()) throw std::invalid_argument("CiphertextProof::prove_batch_seeded: one witness per statement");
-    const size_t B = st.size();
-    if (B == 0) return {};
-    Engine& e = Engine::instance();
-    RangeProofNi::SeedGuard seed(true);
-    const detail::BatchKeys keys(st.begin(), st.end(), [](const CiphertextStatement& q) -> const BigInt& { return q.ek.n; });
-    const uint32_t nb = keys.nb, kw = keys.kw, z1w = kw + ZKP_Z1_EXTRA_LIMBS;
-    std::vector<uint32_t> c(B * 2 * kw), o1(B * z1w), o2(B * 2 * kw), oc(B * 2 * kw);
-    std::vector<uint8_t> status(B, 9);
-    RawBuf<uint32_t> x(B * kw, true), r(B * kw, true);
-    for (size_t b = 0; b < B; b++) { st[b].c.to_limbs(&c[b * 2 * kw], 2 * kw); w[b].x.to_limbs(x.data() + b * kw, kw); w[b].r.to_limbs(r.data() + b * kw, kw); }
-    e.check(zkp_ciphertext_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, c.data(), x.data(), r.data(), seed.bytes, 0, o1.data(), o2.data(),
-                                                    oc.data(), status.data(), 0), "zkp_ciphertext_proof_prove_seeded_batch");
-    detail::seeded_status_ok(status, "BigInt::sample_below(0) (correct_ciphertext.rs:43)");
-    std::vector<CiphertextProof> out;
-    for (size_t b = 0; b < B; b++)
-      out.push_back(CiphertextProof{BigInt::from_limbs(&o1[b * z1w], z1w), BigInt::from_limbs(&o2[b * 2 * kw], 2 * kw), BigInt::from_limbs(&oc[b * 2 * kw], 2 * kw)});
-    return out;
-  }
-  Result verify(const CiphertextStatement& st) const {                                        // :66-97
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32, z1w = kw + ZKP_Z1_EXTRA_LIMBS;
-    std::vector<uint32_t> n(kw), c(2 * kw), a1(z1w), a2(2 * kw), ac(2 * kw);
-    st.ek.n.to_limbs(n.data(), kw); st.c.to_limbs(c.data(), 2 * kw); z1.to_limbs(a1.data(), z1w); z2.to_limbs(a2.data(), 2 * kw); c_prime.to_limbs(ac.data(), 2 * kw);
-    uint8_t v = 9;
-    e.check(zkp_ciphertext_proof_verify_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), a1.data(), a2.data(), ac.data(), &v, 0), "zkp_ciphertext_proof_verify_batch");
-    return Result(v == ZKP_VERDICT_ACCEPT);
-  }
+  static std::vector<CiphertextProof> prove_batch_seeded(const std::vector<CiphertextWitness>& w, const std::vector<CiphertextStatement>& st);
+  static std::vector<CiphertextProof> prove_impl(const CiphertextWitness* w, const CiphertextStatement* st, size_t B, bool seeded);
+  Result verify(const CiphertextStatement& st) const;   // :66-97
   // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
   // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
   // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
@@ -1190,62 +937,12 @@ inline BigInt gen_phi(const EncryptionKey& ek, const BigInt& c, const BigInt& c_
 class VerlinProof {
  public:
   BigInt phi_a, z, z_prime, z_double_prime, r_z;
-  static VerlinProof prove(const VerlinWitness& w, const VerlinStatement& st) {   // :60-99
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32, zw = kw + ZKP_Z1_EXTRA_LIMBS;
-    const BigInt a = BigInt::sample_below(st.ek.n), ap = BigInt::sample_below(st.ek.n), app = BigInt::sample_below(st.ek.n);   // :61-63
-    BigInt r_a = BigInt::sample_below(st.ek.n);
-    while (BigInt::gcd(r_a, st.ek.n) != BigInt::one()) r_a = BigInt::sample_below(st.ek.n);                                   // :64-67
-    auto L1 = [&](const BigInt& v, size_t n) { std::vector<uint32_t> o(n); v.to_limbs(o.data(), n); return o; };
-    auto n = L1(st.ek.n, kw), c = L1(st.c, 2 * kw), cp = L1(st.c_prime, 2 * kw), phx = L1(st.phi_x, 2 * kw);
-    auto x = L1(w.x, kw), xp = L1(w.x_prime, kw), xpp = L1(w.x_double_prime, kw), rx = L1(w.r_x, kw);
-    auto va = L1(a, kw), vap = L1(ap, kw), vapp = L1(app, kw), vra = L1(r_a, kw);
-    std::vector<uint32_t> pa(2 * kw), z(zw), zp(zw), zpp(zw), rz(2 * kw);
-    e.check(zkp_verlin_proof_prove_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), cp.data(), phx.data(), x.data(), xp.data(), xpp.data(), rx.data(),
-                                         va.data(), vap.data(), vapp.data(), vra.data(), pa.data(), z.data(), zp.data(), zpp.data(), rz.data(), 0),
-            "zkp_verlin_proof_prove_batch");
-    return VerlinProof{BigInt::from_limbs(pa.data(), 2 * kw), BigInt::from_limbs(z.data(), zw), BigInt::from_limbs(zp.data(), zw),
-                       BigInt::from_limbs(zpp.data(), zw), BigInt::from_limbs(rz.data(), 2 * kw)};
-  }
+  static VerlinProof prove(const VerlinWitness& w, const VerlinStatement& st);   // :60-99
   // prove for a whole batch from what the reference's prove takes: every (a, a', a'', r_a) comes from one OS seed, expanded on the GPU — r_a
   // redrawn there until gcd(r_a, n) == 1 (:64-67; the rule is sample_coprime_below of include/zkp_hip.h)
-  static std::vector<VerlinProof> prove_batch_seeded(const std::vector<VerlinWitness>& w, const std::vector<VerlinStatement>& st) {
-    if (w.size() != st.size()) throw std::invalid_argument("VerlinProof::prove_batch_seeded: one witness per statement");
-    const size_t B = st.size();
-    if (B == 0) return {};
-    Engine& e = Engine::instance();
-    RangeProofNi::SeedGuard seed(true);
-    const detail::BatchKeys keys(st.begin(), st.end(), [](const VerlinStatement& q) -> const BigInt& { return q.ek.n; });
-    const uint32_t nb = keys.nb, kw = keys.kw, zw = kw + ZKP_Z1_EXTRA_LIMBS;
-    std::vector<uint32_t> c(B * 2 * kw), cp(B * 2 * kw), phx(B * 2 * kw), pa(B * 2 * kw), z(B * zw), zp(B * zw), zpp(B * zw), rz(B * 2 * kw);
-    std::vector<uint8_t> status(B, 9);
-    RawBuf<uint32_t> x(B * kw, true), xp(B * kw, true), xpp(B * kw, true), rx(B * kw, true);
-    for (size_t b = 0; b < B; b++) {
-      st[b].c.to_limbs(&c[b * 2 * kw], 2 * kw); st[b].c_prime.to_limbs(&cp[b * 2 * kw], 2 * kw); st[b].phi_x.to_limbs(&phx[b * 2 * kw], 2 * kw);
-      w[b].x.to_limbs(x.data() + b * kw, kw); w[b].x_prime.to_limbs(xp.data() + b * kw, kw); w[b].x_double_prime.to_limbs(xpp.data() + b * kw, kw);
-      w[b].r_x.to_limbs(rx.data() + b * kw, kw);
-    }
-    e.check(zkp_verlin_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, c.data(), cp.data(), phx.data(), x.data(), xp.data(), xpp.data(),
-                                                rx.data(), seed.bytes, 0, pa.data(), z.data(), zp.data(), zpp.data(), rz.data(), status.data(), 0),
-            "zkp_verlin_proof_prove_seeded_batch");
-    detail::seeded_status_ok(status, "BigInt::sample_below(0), or no r_a coprime to n (verlin_proof.rs:61-67)");
-    std::vector<VerlinProof> out;
-    for (size_t b = 0; b < B; b++)
-      out.push_back(VerlinProof{BigInt::from_limbs(&pa[b * 2 * kw], 2 * kw), BigInt::from_limbs(&z[b * zw], zw), BigInt::from_limbs(&zp[b * zw], zw),
-                                BigInt::from_limbs(&zpp[b * zw], zw), BigInt::from_limbs(&rz[b * 2 * kw], 2 * kw)});
-    return out;
-  }
-  Result verify(const VerlinStatement& st) const {                                // :101-135
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32, zw = kw + ZKP_Z1_EXTRA_LIMBS;
-    auto L1 = [&](const BigInt& v, size_t n) { std::vector<uint32_t> o(n); v.to_limbs(o.data(), n); return o; };
-    auto n = L1(st.ek.n, kw), c = L1(st.c, 2 * kw), cp = L1(st.c_prime, 2 * kw), phx = L1(st.phi_x, 2 * kw), pa = L1(phi_a, 2 * kw);
-    auto vz = L1(z, zw), vzp = L1(z_prime, zw), vzpp = L1(z_double_prime, zw), vrz = L1(r_z, 2 * kw);
-    uint8_t v = 9;
-    e.check(zkp_verlin_proof_verify_batch(e.ctx(), nb, 1, n.data(), 0, c.data(), cp.data(), phx.data(), pa.data(), vz.data(), vzp.data(), vzpp.data(),
-                                          vrz.data(), &v, 0), "zkp_verlin_proof_verify_batch");
-    return Result(v == ZKP_VERDICT_ACCEPT);
-  }
+  static std::vector<VerlinProof> prove_batch_seeded(const std::vector<VerlinWitness>& w, const std::vector<VerlinStatement>& st);
+  static std::vector<VerlinProof> prove_impl(const VerlinWitness* w, const VerlinStatement* st, size_t B, bool seeded);
+  Result verify(const VerlinStatement& st) const;   // :101-135
   // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
   // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
   // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
@@ -1283,61 +980,12 @@ inline BigInt sample_paillier_random(const BigInt& modulo) {    // :148-154
 class MulProof {
  public:
   BigInt f, z1, z2, e_d, e_db;
-  static MulProof prove(const MulWitness& w, const MulStatement& st) {   // :60-104
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32;
-    const BigInt d = BigInt::sample_below(st.ek.n), r_d = sample_paillier_random(st.ek.n);   // :61-62
-    auto L1 = [&](const BigInt& v, size_t n) { std::vector<uint32_t> o(n); v.to_limbs(o.data(), n); return o; };
-    auto n = L1(st.ek.n, kw), ea = L1(st.e_a, 2 * kw), eb = L1(st.e_b, 2 * kw), ec = L1(st.e_c, 2 * kw);
-    auto a = L1(w.a, kw), b = L1(w.b, kw), ra = L1(w.r_a, kw), rb = L1(w.r_b, kw), rc = L1(w.r_c, kw), vd = L1(d, kw), vrd = L1(r_d, kw);
-    std::vector<uint32_t> f(kw), z1(2 * kw), z2(2 * kw), ed(2 * kw), edb(2 * kw);
-    uint8_t status = 9;
-    e.check(zkp_mul_proof_prove_batch(e.ctx(), nb, 1, n.data(), 0, ea.data(), eb.data(), ec.data(), a.data(), b.data(), ra.data(), rb.data(), rc.data(),
-                                      vd.data(), vrd.data(), f.data(), z1.data(), z2.data(), ed.data(), edb.data(), &status, 0), "zkp_mul_proof_prove_batch");
-    if (status != 0) throw Panic("called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:95)");
-    return MulProof{BigInt::from_limbs(f.data(), kw), BigInt::from_limbs(z1.data(), 2 * kw), BigInt::from_limbs(z2.data(), 2 * kw),
-                    BigInt::from_limbs(ed.data(), 2 * kw), BigInt::from_limbs(edb.data(), 2 * kw)};
-  }
+  static MulProof prove(const MulWitness& w, const MulStatement& st);   // :60-104
   // prove for a whole batch from what the reference's prove takes: every (d, r_d) comes from one OS seed, expanded on the GPU — r_d
   // redrawn there until gcd(r_d, n) == 1 (sample_paillier_random, :148-154; the rule is sample_coprime_below of include/zkp_hip.h)
-  static std::vector<MulProof> prove_batch_seeded(const std::vector<MulWitness>& w, const std::vector<MulStatement>& st) {
-    if (w.size() != st.size()) throw std::invalid_argument("MulProof::prove_batch_seeded: one witness per statement");
-    const size_t B = st.size();
-    if (B == 0) return {};
-    Engine& e = Engine::instance();
-    RangeProofNi::SeedGuard seed(true);
-    const detail::BatchKeys keys(st.begin(), st.end(), [](const MulStatement& q) -> const BigInt& { return q.ek.n; });
-    const uint32_t nb = keys.nb, kw = keys.kw;
-    std::vector<uint32_t> ea(B * 2 * kw), eb(B * 2 * kw), ec(B * 2 * kw), f(B * kw), z1(B * 2 * kw), z2(B * 2 * kw), ed(B * 2 * kw), edb(B * 2 * kw);
-    std::vector<uint8_t> status(B, 9);
-    RawBuf<uint32_t> a(B * kw, true), bb(B * kw, true), ra(B * kw, true), rb(B * kw, true), rc(B * kw, true);
-    for (size_t b = 0; b < B; b++) {
-      st[b].e_a.to_limbs(&ea[b * 2 * kw], 2 * kw); st[b].e_b.to_limbs(&eb[b * 2 * kw], 2 * kw); st[b].e_c.to_limbs(&ec[b * 2 * kw], 2 * kw);
-      w[b].a.to_limbs(a.data() + b * kw, kw); w[b].b.to_limbs(bb.data() + b * kw, kw);
-      w[b].r_a.to_limbs(ra.data() + b * kw, kw); w[b].r_b.to_limbs(rb.data() + b * kw, kw); w[b].r_c.to_limbs(rc.data() + b * kw, kw);
-    }
-    e.check(zkp_mul_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, ea.data(), eb.data(), ec.data(), a.data(), bb.data(), ra.data(), rb.data(),
-                                             rc.data(), seed.bytes, 0, f.data(), z1.data(), z2.data(), ed.data(), edb.data(), status.data(), 0),
-            "zkp_mul_proof_prove_seeded_batch");
-    detail::seeded_status_ok(status, "called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:95), or no r_d coprime to n (:148-154)");
-    std::vector<MulProof> out;
-    for (size_t b = 0; b < B; b++)
-      out.push_back(MulProof{BigInt::from_limbs(&f[b * kw], kw), BigInt::from_limbs(&z1[b * 2 * kw], 2 * kw), BigInt::from_limbs(&z2[b * 2 * kw], 2 * kw),
-                             BigInt::from_limbs(&ed[b * 2 * kw], 2 * kw), BigInt::from_limbs(&edb[b * 2 * kw], 2 * kw)});
-    return out;
-  }
-  Result verify(const MulStatement& st) const {                         // :106-146
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(st.ek.n), kw = nb / 32;
-    auto L1 = [&](const BigInt& v, size_t n) { std::vector<uint32_t> o(n); v.to_limbs(o.data(), n); return o; };
-    auto n = L1(st.ek.n, kw), ea = L1(st.e_a, 2 * kw), eb = L1(st.e_b, 2 * kw), ec = L1(st.e_c, 2 * kw);
-    auto vf = L1(f, kw), vz1 = L1(z1, 2 * kw), vz2 = L1(z2, 2 * kw), ved = L1(e_d, 2 * kw), vedb = L1(e_db, 2 * kw);
-    uint8_t v = 9;
-    e.check(zkp_mul_proof_verify_batch(e.ctx(), nb, 1, n.data(), 0, ea.data(), eb.data(), ec.data(), vf.data(), vz1.data(), vz2.data(), ved.data(), vedb.data(),
-                                       &v, 0), "zkp_mul_proof_verify_batch");
-    if (v == ZKP_VERDICT_MALFORMED) throw Panic("called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:135)");
-    return Result(v == ZKP_VERDICT_ACCEPT);
-  }
+  static std::vector<MulProof> prove_batch_seeded(const std::vector<MulWitness>& w, const std::vector<MulStatement>& st);
+  static std::vector<MulProof> prove_impl(const MulWitness* w, const MulStatement* st, size_t B, bool seeded);
+  Result verify(const MulStatement& st) const;   // :106-146
   // serde_json::from_str of both documents + verify for whole batches, one Result per (statement, proof) pair: zkp_sigma_verify_json_batch reads,
   // checks and verifies on the GPU.  forms = ZKP_BIGINT_FORMS(key_form, bare_form).  A document that is no value of its type is the panic of
   // `from_str(..).unwrap()`; a pair the limb kernels are not specified for (ZKP_DOC_HOST_PATH) is Result::unsupported naming the reason.
@@ -1353,63 +1001,49 @@ class CorrectMessageProof {
   EncryptionKey ek;
   static constexpr size_t B = 256;   // :19
   static CorrectMessageProof prove(const EncryptionKey& ek, const std::vector<BigInt>& valid_messages, const BigInt& message_to_encrypt) {   // :35-123
-    Engine& e = Engine::instance();
-    const uint32_t nb = width_for(ek.n), kw = nb / 32;
-    const size_t K = valid_messages.size();
-    if (K == 0) throw Panic("attempt to subtract with overflow (num_of_message - 1, correct_message.rs:58)");
-    auto L1 = [&](const BigInt& v, size_t n) { std::vector<uint32_t> o(n); v.to_limbs(o.data(), n); return o; };
-    auto n = L1(ek.n, kw), msg = L1(message_to_encrypt, kw), r = L1(BigInt::sample_below(ek.n), kw), w = L1(BigInt::sample_below(ek.n), kw);   // :43, :65
-    std::vector<uint32_t> valid(K * kw), esim((K - 1) * 8 + 8), zsim((K - 1) * kw + kw);
-    for (size_t i = 0; i < K; i++) valid_messages[i].to_limbs(&valid[i * kw], kw);
-    for (size_t j = 0; j + 1 < K; j++) {
-      BigInt::sample(B).to_limbs(&esim[j * 8], 8);                       // :59-61
-      BigInt::sample_below(ek.n).to_limbs(&zsim[j * kw], kw);            // :62-64
-    }
-    std::vector<uint32_t> ct(2 * kw), ev(K * 8), zv(K * kw), av(K * 2 * kw);
-    uint8_t status = 9;
-    e.check(zkp_correct_message_prove_batch(e.ctx(), nb, 1, (uint32_t)K, n.data(), 0, valid.data(), msg.data(), r.data(), esim.data(), zsim.data(), w.data(),
-                                            ct.data(), ev.data(), zv.data(), av.data(), &status, 0), "zkp_correct_message_prove_batch");
-    if (status != 0) throw Panic("index out of bounds (correct_message.rs:72: no valid message equals the encrypted one)");
-    CorrectMessageProof p;
-    p.ciphertext = BigInt::from_limbs(ct.data(), 2 * kw); p.valid_messages = valid_messages; p.ek = ek;
-    for (size_t i = 0; i < K; i++) {
-      p.e_vec.push_back(BigInt::from_limbs(&ev[i * 8], 8)); p.z_vec.push_back(BigInt::from_limbs(&zv[i * kw], kw));
-      p.a_vec.push_back(BigInt::from_limbs(&av[i * 2 * kw], 2 * kw));
-    }
-    return p;
+    return prove_impl(ek, &valid_messages, &message_to_encrypt, 1, false)[0];
   }
   // prove for a whole batch under one key from what the reference's prove takes: r, w and the simulated (e_j, z_j) of every proof come from
   // one OS seed, expanded on the GPU.  Every proof of the batch has the same number of valid messages.
   static std::vector<CorrectMessageProof> prove_batch_seeded(const EncryptionKey& ek, const std::vector<std::vector<BigInt>>& valid_messages,
                                                              const std::vector<BigInt>& messages_to_encrypt) {
     if (valid_messages.size() != messages_to_encrypt.size()) throw std::invalid_argument("CorrectMessageProof::prove_batch_seeded: one message per list");
-    const size_t Bn = valid_messages.size();
-    if (Bn == 0) return {};
+    if (valid_messages.empty()) return {};
+    for (auto& v : valid_messages) if (v.size() != valid_messages[0].size()) throw std::invalid_argument("CorrectMessageProof::prove_batch_seeded: lists of one length per batch");
+    return prove_impl(ek, valid_messages.data(), messages_to_encrypt.data(), valid_messages.size(), true);
+  }
+  // Bn proofs of K valid messages each.  Columns: the key; per proof the message (secret) and the ciphertext; per (proof, message) the
+  // valid message and the proof's (e, z, a).
+  static std::vector<CorrectMessageProof> prove_impl(const EncryptionKey& ek, const std::vector<BigInt>* valid_messages, const BigInt* messages, size_t Bn, bool seeded) {
     const size_t K = valid_messages[0].size();
     if (K == 0) throw Panic("attempt to subtract with overflow (num_of_message - 1, correct_message.rs:58)");
-    for (auto& v : valid_messages) if (v.size() != K) throw std::invalid_argument("CorrectMessageProof::prove_batch_seeded: lists of one length per batch");
     Engine& e = Engine::instance();
-    RangeProofNi::SeedGuard seed(true);
+    RangeProofNi::SeedGuard seed(seeded);
     const uint32_t nb = width_for(ek.n), kw = nb / 32;
-    std::vector<uint32_t> n(kw), valid(Bn * K * kw), ct(Bn * 2 * kw), ev(Bn * K * 8), zv(Bn * K * kw), av(Bn * K * 2 * kw);
-    std::vector<uint8_t> status(Bn, 9);
-    RawBuf<uint32_t> msg(Bn * kw, true);
-    ek.n.to_limbs(n.data(), kw);
+    Columns key(1, {{kw, false}}), msg(Bn, {{kw, true}}), valid(Bn * K, {{kw, false}}), ct(Bn, {{2 * kw, false}}), rows(Bn * K, {{8, false}, {kw, false}, {2 * kw, false}});
+    key.put(0, 0, ek.n);
     for (size_t b = 0; b < Bn; b++) {
-      messages_to_encrypt[b].to_limbs(msg.data() + b * kw, kw);
-      for (size_t i = 0; i < K; i++) valid_messages[b][i].to_limbs(&valid[(b * K + i) * kw], kw);
+      msg.put(b, 0, messages[b]);
+      for (size_t i = 0; i < K; i++) valid.put(b * K + i, 0, valid_messages[b][i]);
     }
-    e.check(zkp_correct_message_prove_seeded_batch(e.ctx(), nb, Bn, (uint32_t)K, n.data(), 0, valid.data(), msg.data(), seed.bytes, 0, ct.data(), ev.data(), zv.data(),
-                                                   av.data(), status.data(), 0), "zkp_correct_message_prove_seeded_batch");
+    std::vector<uint8_t> status(Bn, 9);
+    if (seeded)
+      e.check(zkp_correct_message_prove_seeded_batch(e.ctx(), nb, Bn, (uint32_t)K, key[0], 0, valid[0], msg[0], seed.bytes, 0, ct[0], rows[0], rows[1], rows[2], status.data(), 0),
+              "zkp_correct_message_prove_seeded_batch");
+    else {
+      Columns nonce(Bn, {{kw, true}, {kw, true}}), sim(Bn * (K - 1) + 1, {{8, true}, {kw, true}});      // (one spare row: K = 1 simulates nothing)
+      for (size_t f = 0; f < 2; f++) for (size_t b = 0; b < Bn; b++) nonce.put(b, f, BigInt::sample_below(ek.n));   // r, w: :43, :65
+      for (size_t j = 0; j < Bn * (K - 1); j++) { sim.put(j, 0, BigInt::sample(B)); sim.put(j, 1, BigInt::sample_below(ek.n)); }      // the simulated (e_j, z_j), :59-64
+      sim.put(Bn * (K - 1), 0, BigInt()); sim.put(Bn * (K - 1), 1, BigInt());
+      e.check(zkp_correct_message_prove_batch(e.ctx(), nb, Bn, (uint32_t)K, key[0], 0, valid[0], msg[0], nonce[0], sim[0], sim[1], nonce[1], ct[0], rows[0], rows[1], rows[2],
+                                              status.data(), 0), "zkp_correct_message_prove_batch");
+    }
     detail::seeded_status_ok(status, "index out of bounds (correct_message.rs:72: no valid message equals the encrypted one)");
     std::vector<CorrectMessageProof> out(Bn);
     for (size_t b = 0; b < Bn; b++) {
       CorrectMessageProof& p = out[b];
-      p.ciphertext = BigInt::from_limbs(&ct[b * 2 * kw], 2 * kw); p.valid_messages = valid_messages[b]; p.ek = ek;
-      for (size_t i = 0; i < K; i++) {
-        p.e_vec.push_back(BigInt::from_limbs(&ev[(b * K + i) * 8], 8)); p.z_vec.push_back(BigInt::from_limbs(&zv[(b * K + i) * kw], kw));
-        p.a_vec.push_back(BigInt::from_limbs(&av[(b * K + i) * 2 * kw], 2 * kw));
-      }
+      p.ciphertext = ct.get(b, 0); p.valid_messages = valid_messages[b]; p.ek = ek;
+      for (size_t i = 0; i < K; i++) { p.e_vec.push_back(rows.get(b * K + i, 0)); p.z_vec.push_back(rows.get(b * K + i, 1)); p.a_vec.push_back(rows.get(b * K + i, 2)); }
     }
     return out;
   }
@@ -1418,19 +1052,261 @@ class CorrectMessageProof {
     const uint32_t nb = width_for(ek.n), kw = nb / 32;
     const size_t K = valid_messages.size();
     if (e_vec.size() < K || z_vec.size() < K || a_vec.size() < K) throw Panic("index out of bounds");
-    auto L1 = [&](const BigInt& v, size_t n) { std::vector<uint32_t> o(n); v.to_limbs(o.data(), n); return o; };
-    auto n = L1(ek.n, kw), ct = L1(ciphertext, 2 * kw);
-    std::vector<uint32_t> valid(K * kw), ev(K * 8), zv(K * kw), av(K * 2 * kw);
-    for (size_t i = 0; i < K; i++) {
-      valid_messages[i].to_limbs(&valid[i * kw], kw); e_vec[i].to_limbs(&ev[i * 8], 8); z_vec[i].to_limbs(&zv[i * kw], kw); a_vec[i].to_limbs(&av[i * 2 * kw], 2 * kw);
-    }
+    Columns head(1, {{kw, false}, {2 * kw, false}}), rows(K, {{kw, false}, {8, false}, {kw, false}, {2 * kw, false}});
+    head.put_row(0, {&ek.n, &ciphertext});
+    for (size_t i = 0; i < K; i++) rows.put_row(i, {&valid_messages[i], &e_vec[i], &z_vec[i], &a_vec[i]});
     uint8_t v = 9;
-    e.check(zkp_correct_message_verify_batch(e.ctx(), nb, 1, (uint32_t)K, n.data(), 0, valid.data(), ct.data(), ev.data(), zv.data(), av.data(), &v, 0),
-            "zkp_correct_message_verify_batch");
+    e.check(zkp_correct_message_verify_batch(e.ctx(), nb, 1, (uint32_t)K, head[0], 0, rows[0], head[1], rows[1], rows[2], rows[3], &v, 0), "zkp_correct_message_verify_batch");
     if (v == ZKP_VERDICT_MALFORMED) throw Panic("assertion failed: `(left == right)` chal / ei_sum (correct_message.rs:132)");
     return Result(v == ZKP_VERDICT_ACCEPT);
   }
 };
+
+// ------------------------------------------------------------------ the sigma proofs: one field table per type
+// ZeroProof, CiphertextProof, VerlinProof, MulProof, their statements and their witnesses (zero_enc_proof.rs:26-41, correct_ciphertext.rs:22-39,
+// verlin_proof.rs:34-57, multiplication_proof.rs:32-57), every field with its width in the batch layout, in declaration order.  The tables
+// flatten a batch into Columns for the C ABI and read one back (prove, prove_batch_seeded, verify below), and they are the serde defaults of
+// the derives for the documents (serde_json::to_string, sigma_from_str, to_string_batch, verify_json_batch): a statement's key is the
+// object "ek" with the field "n" in the key form; every other field is a bare BigInt.  A witness has no document form; its columns are secret.
+namespace detail {
+enum class SigmaWidth { N, NN, Z };          // kw | 2 kw | kw + ZKP_Z1_EXTRA_LIMBS words in the batch layout
+struct SigmaField { const char* name; BigInt* v; SigmaWidth w; bool key; };
+template <class T> struct SigmaDoc;
+#define ZKP_SIGMA_DOC(T, KIND, SECRET, ...)                                                                     \
+  template <> struct SigmaDoc<T> {                                                                              \
+    static constexpr uint32_t kind = KIND;                                                                      \
+    static constexpr bool secret = SECRET;                                                                      \
+    static constexpr const char* type = #T;                                                                     \
+    static std::vector<SigmaField> fields(T& d) { return __VA_ARGS__; }                                         \
+  };
+ZKP_SIGMA_DOC(ZeroStatement, ZKP_JSON_DOC_ZERO_STATEMENT, false, {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(ZeroProof, ZKP_JSON_DOC_ZERO_PROOF, false, {{"z", &d.z, SigmaWidth::NN, false}, {"a", &d.a, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(CiphertextStatement, ZKP_JSON_DOC_CIPHERTEXT_STATEMENT, false, {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(CiphertextProof, ZKP_JSON_DOC_CIPHERTEXT_PROOF, false,
+              {{"z1", &d.z1, SigmaWidth::Z, false}, {"z2", &d.z2, SigmaWidth::NN, false}, {"c_prime", &d.c_prime, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(VerlinStatement, ZKP_JSON_DOC_VERLIN_STATEMENT, false,
+              {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}, {"c_prime", &d.c_prime, SigmaWidth::NN, false}, {"phi_x", &d.phi_x, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(VerlinProof, ZKP_JSON_DOC_VERLIN_PROOF, false,
+              {{"phi_a", &d.phi_a, SigmaWidth::NN, false}, {"z", &d.z, SigmaWidth::Z, false}, {"z_prime", &d.z_prime, SigmaWidth::Z, false},
+               {"z_double_prime", &d.z_double_prime, SigmaWidth::Z, false}, {"r_z", &d.r_z, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(MulStatement, ZKP_JSON_DOC_MUL_STATEMENT, false,
+              {{"ek", &d.ek.n, SigmaWidth::N, true}, {"e_a", &d.e_a, SigmaWidth::NN, false}, {"e_b", &d.e_b, SigmaWidth::NN, false}, {"e_c", &d.e_c, SigmaWidth::NN, false}})
+ZKP_SIGMA_DOC(MulProof, ZKP_JSON_DOC_MUL_PROOF, false,
+              {{"f", &d.f, SigmaWidth::N, false}, {"z1", &d.z1, SigmaWidth::NN, false}, {"z2", &d.z2, SigmaWidth::NN, false}, {"e_d", &d.e_d, SigmaWidth::NN, false},
+               {"e_db", &d.e_db, SigmaWidth::NN, false}})
+// the witnesses as the prove entry points take them (MulWitness::c is not an input of the proof: multiplication_proof.rs:60-104 never reads it)
+ZKP_SIGMA_DOC(ZeroWitness, 0, true, {{"r", &d.r, SigmaWidth::N, false}})
+ZKP_SIGMA_DOC(CiphertextWitness, 0, true, {{"x", &d.x, SigmaWidth::N, false}, {"r", &d.r, SigmaWidth::N, false}})
+ZKP_SIGMA_DOC(VerlinWitness, 0, true,
+              {{"x", &d.x, SigmaWidth::N, false}, {"x_prime", &d.x_prime, SigmaWidth::N, false}, {"x_double_prime", &d.x_double_prime, SigmaWidth::N, false},
+               {"r_x", &d.r_x, SigmaWidth::N, false}})
+ZKP_SIGMA_DOC(MulWitness, 0, true,
+              {{"a", &d.a, SigmaWidth::N, false}, {"b", &d.b, SigmaWidth::N, false}, {"r_a", &d.r_a, SigmaWidth::N, false}, {"r_b", &d.r_b, SigmaWidth::N, false},
+               {"r_c", &d.r_c, SigmaWidth::N, false}})
+#undef ZKP_SIGMA_DOC
+inline size_t sigma_words(SigmaWidth w, uint32_t kw) { return w == SigmaWidth::N ? kw : w == SigmaWidth::NN ? 2 * kw : kw + ZKP_Z1_EXTRA_LIMBS; }
+
+// The columns of B values of T at kw limbs: one per field of the table — without the key unless with_key (the prove and verify entry
+// points take the keys as an array of their own, BatchKeys; a document writer takes it as field 0).
+template <class T> std::vector<Column> sigma_layout(uint32_t kw, bool with_key = false) {
+  T proto;
+  std::vector<Column> cols;
+  for (const SigmaField& f : SigmaDoc<T>::fields(proto)) if (with_key || !f.key) cols.push_back({sigma_words(f.w, kw), SigmaDoc<T>::secret});
+  return cols;
+}
+template <class T> Columns sigma_flatten(const T* v, size_t B, uint32_t kw, bool with_key = false) {
+  Columns c(B, sigma_layout<T>(kw, with_key));
+  for (size_t b = 0; b < B; b++) {
+    size_t k = 0;
+    for (const SigmaField& f : SigmaDoc<T>::fields(const_cast<T&>(v[b]))) if (with_key || !f.key) c.put(b, k++, *f.v);
+  }
+  return c;
+}
+template <class T> std::vector<T> sigma_read(const Columns& c) {
+  std::vector<T> out(c.B);
+  for (size_t b = 0; b < c.B; b++) {
+    size_t k = 0;
+    for (const SigmaField& f : SigmaDoc<T>::fields(out[b])) *f.v = c.get(b, k++);
+  }
+  return out;
+}
+// B nonces per column, each sample(b) — secret columns, wiped on release
+template <class F> void sample_column(Columns& c, size_t f, F sample) { for (size_t b = 0; b < c.B; b++) c.put(b, f, sample(b)); }
+struct KeyOfStatement { template <class S> const BigInt& operator()(const S& s) const { return s.ek.n; } };
+}  // namespace detail
+
+// prove, prove_batch_seeded and verify of every class are the same three steps: the columns from the tables, the ONE call, the result
+// columns back.  prove is the batch of one with nonces sampled here (into secret columns); prove_batch_seeded hands a seed over instead.
+
+// ---- ZeroProof (zero_enc_proof.rs:44-94)
+inline std::vector<ZeroProof> ZeroProof::prove_impl(const ZeroWitness* w, const ZeroStatement* st, size_t B, bool seeded) {
+  if (B == 0) return {};
+  Engine& e = Engine::instance();
+  RangeProofNi::SeedGuard seed(seeded);
+  const detail::BatchKeys keys(st, st + B, detail::KeyOfStatement());
+  const uint32_t nb = keys.nb, kw = keys.kw;
+  std::vector<ZeroWitness> reduced(B);
+  for (size_t b = 0; b < B; b++) reduced[b].r = w[b].r % st[b].ek.nn;
+  Columns S = detail::sigma_flatten(st, B, kw), W = detail::sigma_flatten(reduced.data(), B, kw), P(B, detail::sigma_layout<ZeroProof>(kw));
+  std::vector<uint8_t> status(B, seeded ? 9 : 0);
+  if (seeded)
+    e.check(zkp_zero_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], W[0], seed.bytes, 0, P[0], P[1], status.data(), 0), "zkp_zero_proof_prove_seeded_batch");
+  else {
+    Columns nonce(B, {{kw, true}});
+    detail::sample_column(nonce, 0, [&](size_t b) { return BigInt::sample_below(st[b].ek.n); });                // r', :45
+    e.check(zkp_zero_proof_prove_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], W[0], nonce[0], P[0], P[1], 0), "zkp_zero_proof_prove_batch");
+  }
+  detail::seeded_status_ok(status, "BigInt::sample_below(0) (zero_enc_proof.rs:45)");
+  return detail::sigma_read<ZeroProof>(P);
+}
+inline ZeroProof ZeroProof::prove(const ZeroWitness& w, const ZeroStatement& st) { return prove_impl(&w, &st, 1, false)[0]; }
+inline std::vector<ZeroProof> ZeroProof::prove_batch_seeded(const std::vector<ZeroWitness>& w, const std::vector<ZeroStatement>& st) {
+  if (w.size() != st.size()) throw std::invalid_argument("ZeroProof::prove_batch_seeded: one witness per statement");
+  return prove_impl(w.data(), st.data(), st.size(), true);
+}
+inline Result ZeroProof::verify(const ZeroStatement& st) const {
+  Engine& e = Engine::instance();
+  const detail::BatchKeys keys(&st, &st + 1, detail::KeyOfStatement());
+  Columns S = detail::sigma_flatten(&st, 1, keys.kw), P = detail::sigma_flatten(this, 1, keys.kw);
+  uint8_t v = 9;
+  e.check(zkp_zero_proof_verify_batch(e.ctx(), keys.nb, 1, keys.n.data(), 0, S[0], P[0], P[1], &v, 0), "zkp_zero_proof_verify_batch");
+  return Result(v == ZKP_VERDICT_ACCEPT);
+}
+
+// ---- CiphertextProof (correct_ciphertext.rs:42-97)
+inline std::vector<CiphertextProof> CiphertextProof::prove_impl(const CiphertextWitness* w, const CiphertextStatement* st, size_t B, bool seeded) {
+  if (B == 0) return {};
+  Engine& e = Engine::instance();
+  RangeProofNi::SeedGuard seed(seeded);
+  const detail::BatchKeys keys(st, st + B, detail::KeyOfStatement());
+  const uint32_t nb = keys.nb, kw = keys.kw;
+  Columns S = detail::sigma_flatten(st, B, kw), W = detail::sigma_flatten(w, B, kw), P(B, detail::sigma_layout<CiphertextProof>(kw));
+  std::vector<uint8_t> status(B, seeded ? 9 : 0);
+  if (seeded)
+    e.check(zkp_ciphertext_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], W[0], W[1], seed.bytes, 0, P[0], P[1], P[2], status.data(), 0),
+            "zkp_ciphertext_proof_prove_seeded_batch");
+  else {
+    Columns nonce(B, {{kw, true}, {kw, true}});
+    for (size_t f = 0; f < 2; f++) detail::sample_column(nonce, f, [&](size_t b) { return BigInt::sample_below(st[b].ek.n); });   // x', r', :43-44
+    e.check(zkp_ciphertext_proof_prove_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], W[0], W[1], nonce[0], nonce[1], P[0], P[1], P[2], 0),
+            "zkp_ciphertext_proof_prove_batch");
+  }
+  detail::seeded_status_ok(status, "BigInt::sample_below(0) (correct_ciphertext.rs:43)");
+  return detail::sigma_read<CiphertextProof>(P);
+}
+inline CiphertextProof CiphertextProof::prove(const CiphertextWitness& w, const CiphertextStatement& st) { return prove_impl(&w, &st, 1, false)[0]; }
+inline std::vector<CiphertextProof> CiphertextProof::prove_batch_seeded(const std::vector<CiphertextWitness>& w, const std::vector<CiphertextStatement>& st) {
+  if (w.size() != st.size()) throw std::invalid_argument("CiphertextProof::prove_batch_seeded: one witness per statement");
+  return prove_impl(w.data(), st.data(), st.size(), true);
+}
+inline Result CiphertextProof::verify(const CiphertextStatement& st) const {
+  Engine& e = Engine::instance();
+  const detail::BatchKeys keys(&st, &st + 1, detail::KeyOfStatement());
+  Columns S = detail::sigma_flatten(&st, 1, keys.kw), P = detail::sigma_flatten(this, 1, keys.kw);
+  uint8_t v = 9;
+  e.check(zkp_ciphertext_proof_verify_batch(e.ctx(), keys.nb, 1, keys.n.data(), 0, S[0], P[0], P[1], P[2], &v, 0), "zkp_ciphertext_proof_verify_batch");
+  return Result(v == ZKP_VERDICT_ACCEPT);
+}
+
+// ---- VerlinProof (verlin_proof.rs:60-135)
+inline std::vector<VerlinProof> VerlinProof::prove_impl(const VerlinWitness* w, const VerlinStatement* st, size_t B, bool seeded) {
+  if (B == 0) return {};
+  Engine& e = Engine::instance();
+  RangeProofNi::SeedGuard seed(seeded);
+  const detail::BatchKeys keys(st, st + B, detail::KeyOfStatement());
+  const uint32_t nb = keys.nb, kw = keys.kw;
+  Columns S = detail::sigma_flatten(st, B, kw), W = detail::sigma_flatten(w, B, kw), P(B, detail::sigma_layout<VerlinProof>(kw));
+  std::vector<uint8_t> status(B, seeded ? 9 : 0);
+  if (seeded)
+    e.check(zkp_verlin_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], S[1], S[2], W[0], W[1], W[2], W[3], seed.bytes, 0, P[0], P[1], P[2], P[3], P[4],
+                                                status.data(), 0), "zkp_verlin_proof_prove_seeded_batch");
+  else {
+    Columns nonce(B, {{kw, true}, {kw, true}, {kw, true}, {kw, true}});
+    for (size_t f = 0; f < 3; f++) detail::sample_column(nonce, f, [&](size_t b) { return BigInt::sample_below(st[b].ek.n); });   // a, a', a'', :61-63
+    detail::sample_column(nonce, 3, [&](size_t b) { return sample_paillier_random(st[b].ek.n); });                                // r_a coprime to n, :64-67
+    e.check(zkp_verlin_proof_prove_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], S[1], S[2], W[0], W[1], W[2], W[3], nonce[0], nonce[1], nonce[2], nonce[3],
+                                         P[0], P[1], P[2], P[3], P[4], 0), "zkp_verlin_proof_prove_batch");
+  }
+  detail::seeded_status_ok(status, "BigInt::sample_below(0), or no r_a coprime to n (verlin_proof.rs:61-67)");
+  return detail::sigma_read<VerlinProof>(P);
+}
+inline VerlinProof VerlinProof::prove(const VerlinWitness& w, const VerlinStatement& st) { return prove_impl(&w, &st, 1, false)[0]; }
+inline std::vector<VerlinProof> VerlinProof::prove_batch_seeded(const std::vector<VerlinWitness>& w, const std::vector<VerlinStatement>& st) {
+  if (w.size() != st.size()) throw std::invalid_argument("VerlinProof::prove_batch_seeded: one witness per statement");
+  return prove_impl(w.data(), st.data(), st.size(), true);
+}
+inline Result VerlinProof::verify(const VerlinStatement& st) const {
+  Engine& e = Engine::instance();
+  const detail::BatchKeys keys(&st, &st + 1, detail::KeyOfStatement());
+  Columns S = detail::sigma_flatten(&st, 1, keys.kw), P = detail::sigma_flatten(this, 1, keys.kw);
+  uint8_t v = 9;
+  e.check(zkp_verlin_proof_verify_batch(e.ctx(), keys.nb, 1, keys.n.data(), 0, S[0], S[1], S[2], P[0], P[1], P[2], P[3], P[4], &v, 0), "zkp_verlin_proof_verify_batch");
+  return Result(v == ZKP_VERDICT_ACCEPT);
+}
+
+// ---- MulProof (multiplication_proof.rs:60-146)
+inline std::vector<MulProof> MulProof::prove_impl(const MulWitness* w, const MulStatement* st, size_t B, bool seeded) {
+  if (B == 0) return {};
+  Engine& e = Engine::instance();
+  RangeProofNi::SeedGuard seed(seeded);
+  const detail::BatchKeys keys(st, st + B, detail::KeyOfStatement());
+  const uint32_t nb = keys.nb, kw = keys.kw;
+  Columns S = detail::sigma_flatten(st, B, kw), W = detail::sigma_flatten(w, B, kw), P(B, detail::sigma_layout<MulProof>(kw));
+  std::vector<uint8_t> status(B, 9);
+  if (seeded)
+    e.check(zkp_mul_proof_prove_seeded_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], S[1], S[2], W[0], W[1], W[2], W[3], W[4], seed.bytes, 0, P[0], P[1], P[2], P[3], P[4],
+                                             status.data(), 0), "zkp_mul_proof_prove_seeded_batch");
+  else {
+    Columns nonce(B, {{kw, true}, {kw, true}});
+    detail::sample_column(nonce, 0, [&](size_t b) { return BigInt::sample_below(st[b].ek.n); });          // d, :61
+    detail::sample_column(nonce, 1, [&](size_t b) { return sample_paillier_random(st[b].ek.n); });        // r_d, :62
+    e.check(zkp_mul_proof_prove_batch(e.ctx(), nb, B, keys.n.data(), keys.stride, S[0], S[1], S[2], W[0], W[1], W[2], W[3], W[4], nonce[0], nonce[1], P[0], P[1], P[2], P[3], P[4],
+                                      status.data(), 0), "zkp_mul_proof_prove_batch");
+  }
+  detail::seeded_status_ok(status, seeded ? "called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:95), or no r_d coprime to n (:148-154)"
+                                          : "called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:95)");
+  return detail::sigma_read<MulProof>(P);
+}
+inline MulProof MulProof::prove(const MulWitness& w, const MulStatement& st) { return prove_impl(&w, &st, 1, false)[0]; }
+inline std::vector<MulProof> MulProof::prove_batch_seeded(const std::vector<MulWitness>& w, const std::vector<MulStatement>& st) {
+  if (w.size() != st.size()) throw std::invalid_argument("MulProof::prove_batch_seeded: one witness per statement");
+  return prove_impl(w.data(), st.data(), st.size(), true);
+}
+inline Result MulProof::verify(const MulStatement& st) const {
+  Engine& e = Engine::instance();
+  const detail::BatchKeys keys(&st, &st + 1, detail::KeyOfStatement());
+  Columns S = detail::sigma_flatten(&st, 1, keys.kw), P = detail::sigma_flatten(this, 1, keys.kw);
+  uint8_t v = 9;
+  e.check(zkp_mul_proof_verify_batch(e.ctx(), keys.nb, 1, keys.n.data(), 0, S[0], S[1], S[2], P[0], P[1], P[2], P[3], P[4], &v, 0), "zkp_mul_proof_verify_batch");
+  if (v == ZKP_VERDICT_MALFORMED) throw Panic("called `Option::unwrap()` on a `None` value (mod_inv, multiplication_proof.rs:135)");
+  return Result(v == ZKP_VERDICT_ACCEPT);
+}
+
+// ---- CompositeDLogProof (wi_dlog_proof.rs:46-65): explicit widths — N, g, ni, x at kw limbs, the secret at 8, the nonce at 16, y at Y_BITS / 32
+inline std::vector<CompositeDLogProof> CompositeDLogProof::prove_impl(const DLogStatement* st, const BigInt* secrets, size_t B, bool seeded) {
+  if (B == 0) return {};
+  Engine& e = Engine::instance();
+  RangeProofNi::SeedGuard seed(seeded);
+  const detail::BatchKeys keys(st, st + B, [](const DLogStatement& q) -> const BigInt& { return q.N; });
+  const uint32_t nb = keys.nb, kw = keys.kw;
+  Columns in(B, {{kw, false}, {kw, false}, {kw, false}, {8, true}}), out(B, {{kw, false}, {Y_BITS / 32, false}});
+  for (size_t b = 0; b < B; b++) in.put_row(b, {&st[b].N, &st[b].g, &st[b].ni, &secrets[b]});
+  if (seeded)
+    e.check(zkp_dlog_prove_seeded_batch(e.ctx(), nb, Y_BITS, B, in[0], in[1], in[2], in[3], seed.bytes, 0, out[0], out[1], nullptr, 0), "zkp_dlog_prove_seeded_batch");
+  else {
+    Columns nonce(B, {{16, true}});
+    detail::sample_column(nonce, 0, [](size_t) { return BigInt::sample_below(BigInt::pow2(512)); });     // K + K' + SAMPLE_S = 512, :53-54
+    e.check(zkp_dlog_prove_batch(e.ctx(), nb, Y_BITS, B, in[0], in[1], in[2], in[3], nonce[0], out[0], out[1], 0), "zkp_dlog_prove_batch");
+  }
+  std::vector<CompositeDLogProof> proofs;
+  for (size_t b = 0; b < B; b++) proofs.push_back(CompositeDLogProof{out.get(b, 0), out.get(b, 1)});
+  return proofs;
+}
+inline CompositeDLogProof CompositeDLogProof::prove(const DLogStatement& st, const BigInt& secret) { return prove_impl(&st, &secret, 1, false)[0]; }
+inline std::vector<CompositeDLogProof> CompositeDLogProof::prove_batch_seeded(const std::vector<DLogStatement>& st, const std::vector<BigInt>& secrets) {
+  if (st.size() != secrets.size()) throw std::invalid_argument("CompositeDLogProof::prove_batch_seeded: one secret per statement");
+  return prove_impl(st.data(), secrets.data(), st.size(), true);
+}
 
 // ------------------------------------------------------------------ wire format (src/serialize.rs + the serde derives)
 // Writers produce what serde_json::to_string produces for the reference's types; readers go through the batched
@@ -1488,13 +1364,11 @@ inline std::vector<std::pair<EncryptedPairs, Proof>> range_from_str(const Encryp
                                                                     const std::vector<std::string>& proof_docs) {
   Engine& e = Engine::instance();
   const uint32_t nb = width_for(ek.n), kw = nb / 32;
-  const size_t B = pairs_docs.size(), EF = error_factor, rows = B * EF;
+  const size_t B = pairs_docs.size(), EF = error_factor;
   if (proof_docs.size() != B) throw std::invalid_argument("range_from_str: one EncryptedPairs and one Proof document per proof");
-  std::vector<uint32_t> c1(rows * 2 * kw), c2(rows * 2 * kw), w1(rows * kw), r1(rows * kw), w2(rows * kw), r2(rows * kw);
-  std::vector<uint8_t> kind(rows), jj(rows), st1(B), st2(B);
-  zkp_range_ni_proofs p{};
-  p.n_bits = nb; p.error_factor = (uint32_t)EF; p.batch = B; p.c1 = c1.data(); p.c2 = c2.data(); p.resp_kind = kind.data(); p.resp_j = jj.data();
-  p.resp_w1 = w1.data(); p.resp_r1 = r1.data(); p.resp_w2 = w2.data(); p.resp_r2 = r2.data();
+  RangeSlab s(B, EF, kw, RangeSlab::PAIRS | RangeSlab::RESPONSES);
+  std::vector<uint8_t> st1(B), st2(B);
+  const zkp_range_ni_proofs p = s.abi(nb, nullptr, 0);
   auto run = [&](const std::vector<std::string>& docs, bool proofs, std::vector<uint8_t>& st) {
     std::string text; std::vector<uint64_t> off, len;
     for (auto& d : docs) { off.push_back(text.size()); len.push_back(d.size()); text += d; }
@@ -1505,19 +1379,7 @@ inline std::vector<std::pair<EncryptedPairs, Proof>> range_from_str(const Encryp
   std::vector<std::pair<EncryptedPairs, Proof>> out(B);
   for (size_t b = 0; b < B; b++) {
     if (st1[b] || st2[b]) throw std::runtime_error("serde_json: document " + std::to_string(b) + " is not a valid EncryptedPairs / Proof of this width");
-    for (size_t i = 0; i < EF; i++) {
-      const size_t t = b * EF + i;
-      out[b].first.c1.push_back(BigInt::from_limbs(&c1[t * 2 * kw], 2 * kw)); out[b].first.c2.push_back(BigInt::from_limbs(&c2[t * 2 * kw], 2 * kw));
-      Response rs;
-      if (kind[t] == ZKP_RESP_OPEN) {
-        rs.kind = Response::Open;
-        rs.w1 = BigInt::from_limbs(&w1[t * kw], kw); rs.r1 = BigInt::from_limbs(&r1[t * kw], kw); rs.w2 = BigInt::from_limbs(&w2[t * kw], kw); rs.r2 = BigInt::from_limbs(&r2[t * kw], kw);
-      } else {
-        rs.kind = Response::Mask; rs.j = jj[t];
-        rs.masked_x = BigInt::from_limbs(&w1[t * kw], kw); rs.masked_r = BigInt::from_limbs(&r1[t * kw], kw);
-      }
-      out[b].second.responses.push_back(std::move(rs));
-    }
+    s.read_pairs(b, out[b].first); s.read_proof(b, out[b].second);
   }
   return out;
 }
@@ -1548,67 +1410,40 @@ enum class BigintText { Dec = ZKP_BIGINT_DEC, Hex = ZKP_BIGINT_HEX, Bytes = ZKP_
 // device-resident batch —, so these overloads stage the limbs in again; a caller that holds the SoA batch on the device uses the C ABI
 // entry points with ZKP_F_DEVICE_PTRS and moves no limb at all.)
 namespace detail_json {
-struct WriteBatch {
-  uint32_t nb = 0, kw = 0; size_t B = 0, EF = 0;
-  std::vector<uint32_t> n, range, ct, c1, c2, w1, r1, w2, r2;
-  std::vector<uint8_t> kind, jj;
-  zkp_range_ni_proofs p{};
-  WriteBatch(const BigInt& key, size_t B_, size_t EF_) : nb(width_for(key)), kw(nb / 32), B(B_), EF(EF_) {
-    p.n_bits = nb; p.error_factor = (uint32_t)EF; p.batch = B;
-  }
-  void pairs(size_t b, const EncryptedPairs& e) {
-    if (e.c1.size() != EF || e.c2.size() != EF) throw std::invalid_argument("to_string_batch: every document of a batch has the same number of rows");
-    if (c1.empty()) { c1.resize(B * EF * 2 * kw); c2.resize(B * EF * 2 * kw); p.c1 = c1.data(); p.c2 = c2.data(); }
-    for (size_t i = 0; i < EF; i++) { e.c1[i].to_limbs(&c1[(b * EF + i) * 2 * kw], 2 * kw); e.c2[i].to_limbs(&c2[(b * EF + i) * 2 * kw], 2 * kw); }
-  }
-  void proof(size_t b, const Proof& pr) {
-    if (pr.responses.size() != EF) throw std::invalid_argument("to_string_batch: every document of a batch has the same number of rows");
-    if (w1.empty()) {
-      for (auto* v : {&w1, &r1, &w2, &r2}) v->resize(B * EF * kw);
-      kind.resize(B * EF); jj.resize(B * EF);
-      p.resp_w1 = w1.data(); p.resp_r1 = r1.data(); p.resp_w2 = w2.data(); p.resp_r2 = r2.data(); p.resp_kind = kind.data(); p.resp_j = jj.data();
-    }
-    for (size_t i = 0; i < EF; i++) {
-      const Response& r = pr.responses[i];
-      const size_t t = b * EF + i;
-      if (r.kind == Response::Open) {
-        kind[t] = ZKP_RESP_OPEN;
-        r.w1.to_limbs(&w1[t * kw], kw); r.r1.to_limbs(&r1[t * kw], kw); r.w2.to_limbs(&w2[t * kw], kw); r.r2.to_limbs(&r2[t * kw], kw);
-      } else {
-        kind[t] = ZKP_RESP_MASK; jj[t] = r.j;
-        r.masked_x.to_limbs(&w1[t * kw], kw); r.masked_r.to_limbs(&r1[t * kw], kw);
-      }
-    }
-  }
-  // call(text or null, capacity, offsets) -> status: the sizing call, one allocation, the writing call
-  template <class F> std::vector<std::string> run(F call, const char* what) {
-    Engine& e = Engine::instance();
-    std::vector<uint64_t> off(B + 1, 0);
-    e.check(call((char*)nullptr, (uint64_t)0, off.data()), what);
-    std::string text((size_t)off[B], '\0');
-    if (!text.empty()) e.check(call(&text[0], (uint64_t)text.size(), off.data()), what);
-    std::vector<std::string> out(B);
-    for (size_t b = 0; b < B; b++) out[b] = text.substr((size_t)off[b], (size_t)(off[b + 1] - off[b]));
-    return out;
-  }
-};
+// the ONE sizing protocol of the writers: call(text or null, capacity, offsets[B + 1]) -> status — the sizing call, one allocation, the
+// writing call, the text cut at the offsets
+template <class F> std::vector<std::string> write_documents(size_t B, F call, const char* what) {
+  Engine& e = Engine::instance();
+  std::vector<uint64_t> off(B + 1, 0);
+  e.check(call((char*)nullptr, (uint64_t)0, off.data()), what);
+  std::string text((size_t)off[B], '\0');
+  if (!text.empty()) e.check(call(&text[0], (uint64_t)text.size(), off.data()), what);
+  std::vector<std::string> out(B);
+  for (size_t b = 0; b < B; b++) out[b] = text.substr((size_t)off[b], (size_t)(off[b + 1] - off[b]));
+  return out;
+}
+inline void same_rows(size_t have, size_t EF) { if (have != EF) throw std::invalid_argument("to_string_batch: every document of a batch has the same number of rows"); }
 }  // namespace detail_json
 
 inline std::vector<std::string> to_string_batch(const std::vector<EncryptedPairs>& v, const EncryptionKey& ek) {
   if (v.empty()) return {};
-  detail_json::WriteBatch w(ek.n, v.size(), v[0].c1.size());
-  for (size_t b = 0; b < v.size(); b++) w.pairs(b, v[b]);
   Engine& e = Engine::instance();
-  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_encrypted_pairs_batch(e.ctx(), &w.p, t, cap, off, nullptr, 0); },
-               "zkp_json_write_encrypted_pairs_batch");
+  const uint32_t nb = width_for(ek.n);
+  RangeSlab s(v.size(), v[0].c1.size(), nb / 32, RangeSlab::PAIRS);
+  for (size_t b = 0; b < v.size(); b++) { detail_json::same_rows(v[b].c1.size(), s.EF); detail_json::same_rows(v[b].c2.size(), s.EF); s.put_pairs(b, v[b]); }
+  const zkp_range_ni_proofs p = s.abi(nb, nullptr, 0);
+  return detail_json::write_documents(v.size(), [&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_encrypted_pairs_batch(e.ctx(), &p, t, cap, off, nullptr, 0); },
+                                      "zkp_json_write_encrypted_pairs_batch");
 }
 inline std::vector<std::string> to_string_batch(const std::vector<Proof>& v, const EncryptionKey& ek) {
   if (v.empty()) return {};
-  detail_json::WriteBatch w(ek.n, v.size(), v[0].responses.size());
-  for (size_t b = 0; b < v.size(); b++) w.proof(b, v[b]);
   Engine& e = Engine::instance();
-  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_range_proof_batch(e.ctx(), &w.p, t, cap, off, nullptr, 0); },
-               "zkp_json_write_range_proof_batch");
+  const uint32_t nb = width_for(ek.n);
+  RangeSlab s(v.size(), v[0].responses.size(), nb / 32, RangeSlab::RESPONSES);
+  for (size_t b = 0; b < v.size(); b++) { detail_json::same_rows(v[b].responses.size(), s.EF); s.put_proof(b, v[b]); }
+  const zkp_range_ni_proofs p = s.abi(nb, nullptr, 0);
+  return detail_json::write_documents(v.size(), [&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_range_proof_batch(e.ctx(), &p, t, cap, off, nullptr, 0); },
+                                      "zkp_json_write_range_proof_batch");
 }
 inline std::vector<std::string> to_string_batch(const std::vector<NiCorrectKeyProof>& v, const EncryptionKey& ek) {
   if (v.empty()) return {};
@@ -1619,25 +1454,25 @@ inline std::vector<std::string> to_string_batch(const std::vector<NiCorrectKeyPr
     if (v[b].sigma_vec.size() != ZKP_CORRECT_KEY_M2) throw std::invalid_argument("to_string_batch: a NiCorrectKeyProof has 11 values");
     for (size_t i = 0; i < ZKP_CORRECT_KEY_M2; i++) v[b].sigma_vec[i].to_limbs(&sigma[(b * ZKP_CORRECT_KEY_M2 + i) * kw], kw);
   }
-  detail_json::WriteBatch w(ek.n, v.size(), 0);
-  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_correct_key_proof_batch(e.ctx(), nb, v.size(), sigma.data(), t, cap, off, nullptr, 0); },
-               "zkp_json_write_correct_key_proof_batch");
+  return detail_json::write_documents(v.size(), [&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_correct_key_proof_batch(e.ctx(), nb, v.size(), sigma.data(), t, cap, off, nullptr, 0); },
+                                      "zkp_json_write_correct_key_proof_batch");
 }
 inline std::vector<std::string> to_string_batch(const std::vector<RangeProofNi>& v, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
   if (v.empty()) return {};
-  detail_json::WriteBatch w(v[0].ek.n, v.size(), v[0].error_factor);
-  const uint32_t kw = w.kw;
-  w.n.resize(v.size() * kw); w.range.resize(v.size() * kw); w.ct.resize(v.size() * 2 * kw);
-  for (size_t b = 0; b < v.size(); b++) {
-    if (width_for(v[b].ek.n) != w.nb || v[b].error_factor != w.EF) throw std::invalid_argument("to_string_batch: one key width and one error_factor per batch");
-    v[b].ek.n.to_limbs(&w.n[b * kw], kw); v[b].range.to_limbs(&w.range[b * kw], kw); v[b].ciphertext.to_limbs(&w.ct[b * 2 * kw], 2 * kw);
-    w.pairs(b, v[b].encrypted_pairs); w.proof(b, v[b].proof);
-  }
-  w.p.n = w.n.data(); w.p.n_stride = kw; w.p.range = w.range.data(); w.p.ciphertext = w.ct.data();
-  const uint32_t forms = ZKP_BIGINT_FORMS((uint32_t)key_form, (uint32_t)bigint_form);
   Engine& e = Engine::instance();
-  return w.run([&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_range_proof_ni_batch(e.ctx(), &w.p, forms, t, cap, off, nullptr, 0); },
-               "zkp_json_write_range_proof_ni_batch");
+  const uint32_t nb = width_for(v[0].ek.n), kw = nb / 32;
+  RangeSlab s(v.size(), v[0].error_factor, kw, RangeSlab::ALL);
+  std::vector<uint32_t> n(v.size() * kw);
+  for (size_t b = 0; b < v.size(); b++) {
+    if (width_for(v[b].ek.n) != nb || v[b].error_factor != s.EF) throw std::invalid_argument("to_string_batch: one key width and one error_factor per batch");
+    detail_json::same_rows(v[b].encrypted_pairs.c1.size(), s.EF); detail_json::same_rows(v[b].encrypted_pairs.c2.size(), s.EF); detail_json::same_rows(v[b].proof.responses.size(), s.EF);
+    v[b].ek.n.to_limbs(&n[b * kw], kw);
+    s.put_statement(b, v[b].range, v[b].ciphertext); s.put_pairs(b, v[b].encrypted_pairs); s.put_proof(b, v[b].proof);
+  }
+  const zkp_range_ni_proofs p = s.abi(nb, n.data(), kw);
+  const uint32_t forms = ZKP_BIGINT_FORMS((uint32_t)key_form, (uint32_t)bigint_form);
+  return detail_json::write_documents(v.size(), [&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_range_proof_ni_batch(e.ctx(), &p, forms, t, cap, off, nullptr, 0); },
+                                      "zkp_json_write_range_proof_ni_batch");
 }
 // the whole document (range_proof_ni.rs:36-44), the inverse of range_proof_ni_from_str
 inline std::string to_string(const RangeProofNi& p, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
@@ -1790,45 +1625,17 @@ inline DLogStatement dlog_statement_from_str(const std::string& doc, BigintText 
   return s;
 }
 
-// ZeroProof, CiphertextProof, VerlinProof, MulProof and their statements (zero_enc_proof.rs:26-41, correct_ciphertext.rs:22-39, verlin_proof.rs:34-57,
-// multiplication_proof.rs:32-57): the serde defaults of the derives.  A statement's key is the object "ek" with the field "n" in the key form;
-// every other field is a bare BigInt.  One table per type, in declaration order, serves to_string, from_str, to_string_batch and verify_json_batch.
+// the documents of the sigma proofs and their statements: driven by the tables of zkproofs::detail (SigmaDoc, above)
 namespace detail_json {
-enum class SigmaWidth { N, NN, Z };          // kw | 2 kw | kw + ZKP_Z1_EXTRA_LIMBS words in the batch layout
-struct SigmaField { const char* name; BigInt* v; SigmaWidth w; bool key; };
-template <class T> struct SigmaDoc;
-#define ZKP_SIGMA_DOC(T, KIND, ...)                                                                             \
-  template <> struct SigmaDoc<T> {                                                                              \
-    static constexpr uint32_t kind = KIND;                                                                      \
-    static constexpr const char* type = #T;                                                                     \
-    static std::vector<SigmaField> fields(T& d) { return __VA_ARGS__; }                                         \
-  };
-ZKP_SIGMA_DOC(ZeroStatement, ZKP_JSON_DOC_ZERO_STATEMENT, {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(ZeroProof, ZKP_JSON_DOC_ZERO_PROOF, {{"z", &d.z, SigmaWidth::NN, false}, {"a", &d.a, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(CiphertextStatement, ZKP_JSON_DOC_CIPHERTEXT_STATEMENT, {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(CiphertextProof, ZKP_JSON_DOC_CIPHERTEXT_PROOF,
-              {{"z1", &d.z1, SigmaWidth::Z, false}, {"z2", &d.z2, SigmaWidth::NN, false}, {"c_prime", &d.c_prime, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(VerlinStatement, ZKP_JSON_DOC_VERLIN_STATEMENT,
-              {{"ek", &d.ek.n, SigmaWidth::N, true}, {"c", &d.c, SigmaWidth::NN, false}, {"c_prime", &d.c_prime, SigmaWidth::NN, false}, {"phi_x", &d.phi_x, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(VerlinProof, ZKP_JSON_DOC_VERLIN_PROOF,
-              {{"phi_a", &d.phi_a, SigmaWidth::NN, false}, {"z", &d.z, SigmaWidth::Z, false}, {"z_prime", &d.z_prime, SigmaWidth::Z, false},
-               {"z_double_prime", &d.z_double_prime, SigmaWidth::Z, false}, {"r_z", &d.r_z, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(MulStatement, ZKP_JSON_DOC_MUL_STATEMENT,
-              {{"ek", &d.ek.n, SigmaWidth::N, true}, {"e_a", &d.e_a, SigmaWidth::NN, false}, {"e_b", &d.e_b, SigmaWidth::NN, false}, {"e_c", &d.e_c, SigmaWidth::NN, false}})
-ZKP_SIGMA_DOC(MulProof, ZKP_JSON_DOC_MUL_PROOF,
-              {{"f", &d.f, SigmaWidth::N, false}, {"z1", &d.z1, SigmaWidth::NN, false}, {"z2", &d.z2, SigmaWidth::NN, false}, {"e_d", &d.e_d, SigmaWidth::NN, false},
-               {"e_db", &d.e_db, SigmaWidth::NN, false}})
-#undef ZKP_SIGMA_DOC
 // MinimalEncryptionKey -> EncryptionKey { n, nn = n * n } for the types that carry a key [upstream kzen-paillier]
 template <class T> auto set_nn(T& d, int) -> decltype(d.ek.nn, void()) { d.ek.nn = d.ek.n * d.ek.n; }
 template <class T> void set_nn(T&, long) {}
-inline size_t sigma_words(SigmaWidth w, uint32_t kw) { return w == SigmaWidth::N ? kw : w == SigmaWidth::NN ? 2 * kw : kw + ZKP_Z1_EXTRA_LIMBS; }
 }  // namespace detail_json
 
-template <class T, class D = detail_json::SigmaDoc<T>> std::string to_string(const T& doc, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
+template <class T, class D = detail::SigmaDoc<T>> std::string to_string(const T& doc, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
   std::string s = "{";
   bool after_key = false;
-  for (const detail_json::SigmaField& f : D::fields(const_cast<T&>(doc))) {
+  for (const detail::SigmaField& f : D::fields(const_cast<T&>(doc))) {
     if (s.size() > 1) s += after_key ? "}," : ",";
     s += std::string("\"") + f.name + "\":" + (f.key ? "{\"n\":" : "") + bigint_text(*f.v, f.key ? key_form : bare_form);
     after_key = f.key;
@@ -1836,9 +1643,9 @@ template <class T, class D = detail_json::SigmaDoc<T>> std::string to_string(con
   return s + (after_key ? "}}" : "}");
 }
 // serde_json::from_str::<T>: throws (std::runtime_error) where serde reports an error
-template <class T, class D = detail_json::SigmaDoc<T>> T sigma_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
+template <class T, class D = detail::SigmaDoc<T>> T sigma_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
   T out;
-  const std::vector<detail_json::SigmaField> fields = D::fields(out);
+  const std::vector<detail::SigmaField> fields = D::fields(out);
   detail_json::Cur j{doc};
   unsigned seen = 0;
   j.object([&](const std::string& nm) {
@@ -1861,38 +1668,24 @@ template <class T, class D = detail_json::SigmaDoc<T>> T sigma_from_str(const st
   return out;
 }
 // whole batches through zkp_json_write_sigma_batch: one key width per batch — the smallest in which every value fits its array
-template <class T, class D = detail_json::SigmaDoc<T>>
+template <class T, class D = detail::SigmaDoc<T>>
 std::vector<std::string> to_string_batch(const std::vector<T>& v, BigintText key_form = BigintText::Dec, BigintText bare_form = BigintText::Dec) {
+  static_assert(!D::secret, "a witness has no document form");
   const size_t B = v.size();
   if (B == 0) return {};
-  std::vector<std::vector<detail_json::SigmaField>> rows;
-  for (const T& d : v) rows.push_back(D::fields(const_cast<T&>(d)));
   uint32_t nb = 0;
   for (uint32_t cand : {1024u, 2048u, 4096u}) {
     bool fits = true;
-    for (auto& r : rows) for (auto& f : r) fits = fits && !f.v->is_negative() && f.v->bit_length() <= 32 * detail_json::sigma_words(f.w, cand / 32);
+    for (const T& d : v) for (const detail::SigmaField& f : D::fields(const_cast<T&>(d))) fits = fits && f.v->fits_limbs(detail::sigma_words(f.w, cand / 32));
     if (fits) { nb = cand; break; }
   }
   if (!nb) throw std::invalid_argument(std::string("to_string_batch: a ") + D::type + " with a negative value or one wider than the 4096-bit layout");
-  const size_t nf = rows[0].size();
-  std::vector<std::vector<uint32_t>> arr(nf);
-  uint32_t* ptrs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (size_t f = 0; f < nf; f++) {
-    const size_t w = detail_json::sigma_words(rows[0][f].w, nb / 32);
-    arr[f].resize(B * w);
-    for (size_t b = 0; b < B; b++) rows[b][f].v->to_limbs(&arr[f][b * w], w);
-    ptrs[f] = arr[f].data();
-  }
-  const zkp_sigma_fields in{ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4]};
+  Columns c = detail::sigma_flatten(v.data(), B, nb / 32, true);
+  const zkp_sigma_fields in{c[0], c[1], c[2], c[3], c[4]};
   const uint32_t forms = ZKP_BIGINT_FORMS((uint32_t)key_form, (uint32_t)bare_form);
   Engine& e = Engine::instance();
-  std::vector<uint64_t> off(B + 1);
-  e.check(zkp_json_write_sigma_batch(e.ctx(), D::kind, nb, B, &in, forms, nullptr, 0, off.data(), nullptr, 0), "zkp_json_write_sigma_batch");
-  std::string text(off[B], '\0');
-  e.check(zkp_json_write_sigma_batch(e.ctx(), D::kind, nb, B, &in, forms, &text[0], text.size(), off.data(), nullptr, 0), "zkp_json_write_sigma_batch");
-  std::vector<std::string> out(B);
-  for (size_t b = 0; b < B; b++) out[b] = text.substr(off[b], off[b + 1] - off[b]);
-  return out;
+  return detail_json::write_documents(B, [&](char* t, uint64_t cap, uint64_t* off) { return zkp_json_write_sigma_batch(e.ctx(), D::kind, nb, B, &in, forms, t, cap, off, nullptr, 0); },
+                                      "zkp_json_write_sigma_batch");
 }
 
 inline RangeProofNi range_proof_ni_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
@@ -2082,9 +1875,9 @@ inline std::vector<Result> NiCorrectKeyProof::verify_json_batch(const std::vecto
 namespace detail_json_sigma {
 template <class Proof, class Statement>
 std::vector<Result> verify_json_batch(const std::vector<std::string>& statements, const std::vector<std::string>& proofs, uint32_t forms) {
-  using PD = serde_json::detail_json::SigmaDoc<Proof>;
-  using SD = serde_json::detail_json::SigmaDoc<Statement>;
-  using serde_json::detail_json::SigmaWidth;
+  using PD = detail::SigmaDoc<Proof>;
+  using SD = detail::SigmaDoc<Statement>;
+  using detail::SigmaWidth;
   const std::string name = std::string(PD::type) + "::verify_json_batch";
   const size_t B = statements.size();
   if (proofs.size() != B) throw std::invalid_argument(name + ": one proof per statement");
@@ -2122,11 +1915,11 @@ std::vector<Result> verify_json_batch(const std::vector<std::string>& statements
     else {
       const BigInt nn = s.ek.n * s.ek.n;
       const uint32_t kw = width_for(s.ek.n) / 32;
-      auto look = [&](const std::vector<serde_json::detail_json::SigmaField>& fields) {
+      auto look = [&](const std::vector<detail::SigmaField>& fields) {
         for (const auto& f : fields) {
           if (f.key || !why.empty()) continue;
           if (f.v->is_negative()) why = std::string(f.name) + " is negative";
-          else if (f.w == SigmaWidth::Z && f.v->bit_length() > 32 * serde_json::detail_json::sigma_words(f.w, kw)) why = std::string(f.name) + " is wider than n by more than 512 bits";
+          else if (f.w == SigmaWidth::Z && f.v->bit_length() > 32 * detail::sigma_words(f.w, kw)) why = std::string(f.name) + " is wider than n by more than 512 bits";
           else if (f.w == SigmaWidth::NN && !(*f.v < nn)) why = std::string(f.name) + " is not below n^2";
           else if (f.w == SigmaWidth::N && !(*f.v < s.ek.n)) why = std::string(f.name) + " is not below n";
         }
