@@ -3,11 +3,18 @@
 // cut or not, and on the engine that runs each part the base-n plan, the pair ladder and the second stream.  tests/test_cpp_route_plan.py
 // builds it under the sanitizers and compares what it prints with tests/routing_model.py and with the pinned table tests/golden/route_plan.json.
 //
+//   test_route_plan            error factor 128, every config, 1 ... 400 proofs (the table of tests/golden/route_plan.json)
+//   test_route_plan <EF>       another error factor (1 ... 256), the three chips only, every batch from 1 to the first one whose items
+//                              (2 EF per proof) exceed 48 per SIMD — beyond that no rule looks at the size any more.  "prove" is then the
+//                              Enc launch of zkp_range_generate_encrypted_pairs_batch: zkp_range_ni_prove_batch always writes 128 rows, and
+//                              only a call of 128 rows per proof asks range_split (csrc/zkp_api_proofs.inc)
+//
 //   config <name>                                  the knobs of the ctx (throughput build, 36 limbs per lane)
 //   prove|verify <B> <decision>                    one line per call
 //   takes <w> <B> <asked> <placed>                 B < cus: "takes the hashes" as range_verify_impl asks it | hash blocks of the launch's own plan
 //   pass 2                                         everything once more, computed in the opposite order
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -15,7 +22,9 @@
 
 using namespace zkp;
 
-static const int N_BITS = 2048, EF = 128, MAX_B = 400;
+static const int N_BITS = 2048, DEFAULT_EF = 128;
+static int EF = DEFAULT_EF, MAX_B = 400;      // MAX_B == 0: up to the first batch beyond 48 items per SIMD (max_batch)
+static bool CHIPS_ONLY = false;
 static const int OCCUPANCY = 2;      // resident workgroups per compute unit of the base-n kernels: an input of the plan (the library asks the runtime)
 
 struct Config { std::string name; RouteKnobs k; };
@@ -42,6 +51,7 @@ static std::vector<Config> configs() {
   std::vector<Config> v;
   for (int cus : {256, 64, 304}) v.push_back({"cus" + std::to_string(cus), base_knobs(cus)});
   auto variant = [&](const char* name, auto set) { RouteKnobs k = base_knobs(256); set(k); v.push_back({name, k}); };
+  if (CHIPS_ONLY) return v;
   variant("grid_expected0", [](RouteKnobs& k) { k.grid_expected = 0; });
   variant("split0", [](RouteKnobs& k) { k.split_calls = 0; });
   variant("fuse_hash0", [](RouteKnobs& k) { k.fuse_hash_on = 0; });
@@ -91,9 +101,15 @@ static std::string part(const RouteKnobs& k, bool verify, uint64_t batch) {
 }
 static const char* engine_name(int e) { return e < 0 ? "own" : e == 0 ? "lat" : "mid"; }
 
+static int max_batch(const RouteKnobs& k) {
+  if (MAX_B) return MAX_B;
+  return (int)(48 * simds(k) / (2 * (uint64_t)EF)) + 1;
+}
+
 static std::string decide(const RouteKnobs& k, bool verify, uint64_t batch) {
-  const uint64_t rows = 2 * EF;
-  const RangeSplit sp = range_split(k, batch, rows, N_BITS, 0, verify);
+  const uint64_t rows = 2 * (uint64_t)EF;
+  // (a prove of another row count is the interactive generate_encrypted_pairs: routed by its items, never cut)
+  const RangeSplit sp = (verify || EF == DEFAULT_EF) ? range_split(k, batch, rows, N_BITS, 0, verify) : RangeSplit();
   auto on = [&](int e) { return e < 0 ? k : engine_knobs(k, k.eng_w[e]); };
   if (sp.head)
     return "cut head=" + std::to_string(sp.head) + "@" + engine_name(sp.head_engine) + " [" + part(on(sp.head_engine), verify, sp.head) + "] tail=" +
@@ -110,8 +126,9 @@ static std::vector<std::string> run(bool backwards) {
   for (size_t ci = 0; ci < cfg.size(); ci++) {
     const Config& c = cfg[backwards ? cfg.size() - 1 - ci : ci];
     std::vector<Job> jobs;
-    for (int kind = 0; kind < 2; kind++) for (int B = 1; B <= MAX_B; B++) jobs.push_back({kind, 36, B});
-    for (int w : {36, 18, 9}) for (int B = 1; B < c.k.cus && B <= MAX_B; B++) jobs.push_back({2, w, B});
+    const int last = max_batch(c.k);
+    for (int kind = 0; kind < 2; kind++) for (int B = 1; B <= last; B++) jobs.push_back({kind, 36, B});
+    for (int w : {36, 18, 9}) for (int B = 1; B < c.k.cus && B <= last; B++) jobs.push_back({2, w, B});
     std::vector<std::string>& lines = blocks[backwards ? cfg.size() - 1 - ci : ci];
     lines.assign(jobs.size() + 1, "");
     lines[0] = "config " + c.name;
@@ -131,7 +148,13 @@ static std::vector<std::string> run(bool backwards) {
   return out;
 }
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1) {
+    EF = std::atoi(argv[1]);
+    if (EF < 1 || EF > 256) { std::fprintf(stderr, "usage: test_route_plan [error factor 1 ... 256]\n"); return 2; }
+    MAX_B = 0;
+    CHIPS_ONLY = true;
+  }
   for (const std::string& l : run(false)) std::puts(l.c_str());
   std::puts("pass 2");
   for (const std::string& l : run(true)) std::puts(l.c_str());

@@ -5,11 +5,17 @@ verify call of 1 ... 400 proofs under one 2048-bit key, for 256, 64 and 304 comp
   against the model    family and tail equal tests/routing_model.py at every size (the device test compares the model at 16 sizes)
   against the parent   the decisions equal tests/golden/route_plan.json, recorded from the expressions the header replaced
   one rule, two callers   "takes the hashes" as range_verify_impl asks it ahead of the launch = the hash placement of the launch's own plan
-  no hidden state      computed twice, the second time in the opposite order: the same lines"""
+  no hidden state      computed twice, the second time in the opposite order: the same lines
+  other row counts     the same program at 1, 7, 40, 120 and 256 rows per proof, every batch up to 48 items per SIMD on the three chips, against
+                       the model — with what no size may break: a head inside the batch and inside its engine's one round, a grid for every
+                       launch the plan takes, the hashes aboard within the bound their branch states"""
+import functools
 import json
 import os
 import re
 import subprocess
+
+import pytest
 
 import helpers as H
 import routing_model as R
@@ -20,12 +26,17 @@ NUMBER = re.compile(r"\d+")
 MAX_B = 400
 
 
-def run_program():
+@functools.lru_cache(maxsize=None)
+def built_program():
     src = os.path.join(ROOT, "tests", "cpp", "test_route_plan.cpp")
     exe = os.path.join(ROOT, "build", "test_route_plan")
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    return exe
+
+
+def run_program(*args):
+    out = subprocess.run([built_program()] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     return out.stdout
 
@@ -123,3 +134,91 @@ def test_route_plan_under_sanitizers():
         assert c["takes"], name
         assert all(asked == (placed != 0) for _, _, asked, placed in c["takes"]), (name, [t for t in c["takes"] if t[2] != (t[3] != 0)][:10])
     assert any(placed == 16 for _, _, _, placed in got["cus256"]["takes"]) and any(placed == 64 for _, _, _, placed in got["cus256"]["takes"])
+
+
+PART = re.compile(r"\[w=(\d+) pair=(\d) form=(\d) r2l=(\d) lanes=(\d+) blocks=(\d+) wgs=(\d+) hash=(\d+) two=(\d) side=(\d)\]")
+HEAD_ENGINE = {"mid": 18, "lat": 9, "own": 36}
+
+
+def parts_of(decision, batch):
+    """[(proofs of the part, its printed plan as a dict)] of a decision: one part, or the head and the tail of a cut call"""
+    plans = [dict(zip(("w", "pair", "form", "r2l", "lanes", "blocks", "wgs", "hash", "two", "side"), (int(x) for x in m))) for m in PART.findall(decision)]
+    if decision.startswith("cut "):
+        head, tail = int(re.search(r"head=(\d+)@", decision).group(1)), int(re.search(r"tail=(\d+)", decision).group(1))
+        assert len(plans) == 2, decision
+        return [(head, plans[0]), (tail, plans[1])]
+    assert len(plans) == 1, decision
+    return [(batch, plans[0])]
+
+
+def check_decisions(got, ef, last_of):
+    """every decision of the three chips at `ef` rows per proof against the model, and the invariants no size may break"""
+    rows = 2 * ef
+    wrong = []
+    for name in ("cus256", "cus64", "cus304"):
+        cus = int(name[3:])
+        simds = 4 * cus
+        last = last_of(cus)
+        for kind in ("prove", "verify"):
+            listed = kind == "verify"
+            never = kind == "prove" and ef != 128                 # (generate_encrypted_pairs: routed by its items, never cut)
+            assert sorted(got[name][kind]) == list(range(1, last + 1)), (name, kind, ef)
+            for b in range(1, last + 1):
+                d = got[name][kind][b]
+                at = (ef, name, kind, b, d)
+                fam, tail = family_and_tail(d)
+                want = R.expected_family(cus, 9, 18, rows * b, listed=listed, rows_per_proof=rows, never_split=never)
+                cut = None if never else R.expected_split(cus, b, rows, listed)
+                if fam != want or (fam == "split") != (cut is not None):
+                    wrong.append((at, fam, want))
+                    continue
+                parts = parts_of(d, b)
+                if cut:
+                    head, engine, per_simd = cut
+                    got_head, got_engine = re.search(r"head=(\d+)@(\w+)", d).groups()
+                    assert 0 < int(got_head) < b and int(got_head) + tail == b, at
+                    assert int(got_head) * rows <= per_simd * simds, at          # the head fits the one round it was cut for
+                    assert (int(got_head), got_engine) == (head, engine) and tail == R.expected_tail(cus, b, rows, listed), (at, cut)
+                    assert parts[0][1]["w"] == HEAD_ENGINE[engine] and parts[1][1]["w"] == 9, at
+                else:
+                    assert not d.startswith("cut "), at
+                for proofs, p in parts:
+                    assert proofs > 0, at
+                    if p["form"]:
+                        assert p["blocks"] > 0, at                               # a launch the plan takes has a grid
+                        if p["r2l"]:
+                            assert p["wgs"] > 0 and p["lanes"] in (36, 12, 8), at
+                    if p["hash"]:                                                # the transcript hashes aboard: one workgroup each, in front of the Enc workgroups
+                        assert p["form"] and p["r2l"] and p["hash"] in (16, 64), at
+                        bound = cus if p["lanes"] == 36 else simds if p["hash"] == 64 else 2 * simds
+                        assert proofs + p["wgs"] <= bound, (at, bound)
+    assert not wrong, wrong[:20]
+
+
+@pytest.mark.parametrize("ef", [1, 7, 40, 120, 256])
+def test_route_plan_at_other_row_counts(ef):
+    """the same program at another error factor: every batch from 1 to the first one beyond 48 items per SIMD, on the three chips — the
+    model is the reference (tests/test_gpu_range_error_factors.py holds the model against the device)"""
+    text = run_program(ef).splitlines()
+    cut = text.index("pass 2")
+    assert text[:cut] == text[cut + 1:]
+    got = parse(text[:cut])
+    assert sorted(got) == ["cus256", "cus304", "cus64"]
+    check_decisions(got, ef, lambda cus: 48 * 4 * cus // (2 * ef) + 1)
+    for name, c in got.items():
+        assert c["takes"], name
+        assert all(asked == (placed != 0) for _, _, asked, placed in c["takes"]), (ef, name, [t for t in c["takes"] if t[2] != (t[3] != 0)][:10])
+    # the sweep reaches what it is about: at 40 rows a verify is cut in both of its windows — 4 ... 5 and 16 ... 24 items per SIMD; the third,
+    # 8 ... 9 per SIMD (103 ... 115 proofs), is a window of proves only: a verify of that size fits the latency engine's one round by its
+    # expected items, as 33 ... 36 proofs of 128 rows do — and a prove never is
+    if ef == 40:
+        cuts = {b: re.search(r"head=(\d+)@(\w+)", d).groups() for b, d in got["cus256"]["verify"].items() if d.startswith("cut ")}
+        assert sorted(cuts) == list(range(52, 65)) + list(range(263, 308))
+        assert {cuts[b] for b in range(52, 65)} == {("51", "lat")} and {cuts[b] for b in range(263, 308)} == {("204", "mid")}
+        assert not any(d.startswith("cut ") for d in got["cus256"]["prove"].values())
+
+
+def test_route_plan_invariants_at_128_rows():
+    text = run_program().splitlines()
+    got = parse(text[:text.index("pass 2")])
+    check_decisions(got, 128, lambda cus: MAX_B)
