@@ -1,6 +1,8 @@
 """mod_inv, MulProof (multiplication_proof.rs) and CorrectMessageProof (correct_message.rs) — SURVEY §8(f) rank 4.
 CPU: the C oracle against the pure-Python model (and the reference's own accept / reject behaviours,
 multiplication_proof.rs:172-290, correct_message.rs:169-200).  GPU: the HIP engine against the oracle, byte-exact."""
+import math
+
 import numpy as np
 import pytest
 
@@ -18,6 +20,8 @@ def inv_cases(mod, kw, seed, count):
     # a == M modulo 2^32 / 2^64 / 2^96: the first difference has whole zero low words (the unfused path of k_modinv)
     vals += [mod - (3 << 32), mod - (5 << 64), mod - (7 << 96), mod - (d.below(1 << 200) << 64)]
     vals += [d.below(mod) for _ in range(count - len(vals))]
+    # a = M - r for small even r: the values whose cofactor can end below -M (tests/modinv_class_cases.py has vectors that do); on top of `count`
+    vals += [mod - r for r in (14, 30, 42, 46, 62) if math.gcd(mod - r, mod) == 1]
     return vals
 
 

@@ -55,6 +55,25 @@ def test_cofactor_slightly_above_the_modulus_in_magnitude():
     assert hits > 0                                      # the case is exercised, not just survived
 
 
+def test_the_record_of_a_call_names_its_class():
+    """stats["call"]: where the cofactor stood before the finalisation and what the rounds did (tests/modinv_class_cases.py builds on it)"""
+    M = 4400505965657808285
+    st = {"maxcof": 0}
+    W.wbgcd(M - 14, M, 8, True, st)
+    c = st["call"]
+    assert (c["v_class"], c["final_passes"], c["start_le64"], c["cross_le64"]) == ("below_neg_m", 2, True, False) and c["rounds"] == st["iters"]
+    W.wbgcd(3, 7, 8, True, st)                            # the record is per call, the maxima are not
+    assert st["call"]["v_class"] in ("in_range", "neg") and st["call"]["final_passes"] <= 1 and st["final_passes"] == 2
+    assert W.v_class(-8, 7, 2) == "below_neg_m" and W.v_class(-7, 7, 2) == "neg" and W.v_class(6, 7, 2) == "in_range"
+    assert W.v_class(7, 7, 2) == "ge_m" and W.v_class(1 << 64, 7, 2) == "ge_m_signword"
+    W.wbgcd(6, 9, 8, True, st)                            # no inverse: no class
+    assert st["call"]["v_class"] is None and st["call"]["final_passes"] is None
+    rnd = random.Random(3)
+    M = rnd.getrandbits(2048) | 1 | (1 << 2047)
+    W.wbgcd(M - (3 << 31), M, 64, True, st)               # close to a full-width M: a comes out negative, the sign word carries magnitude
+    assert st["call"]["neg_a_rounds"] > 0 and st["call"]["signword_magnitude"] and st["call"]["cross_le64"] and not st["call"]["start_le64"]
+
+
 def test_gcd_of_values_above_the_modulus_and_zero_low_words():
     """the DLog coprimality tests hand over any kw-word value, also ones above N and ones with zero low words"""
     rnd = random.Random(7)

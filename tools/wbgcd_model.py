@@ -36,17 +36,34 @@ def negate(W):
     for x in W:
         t = (x ^ 0xFFFFFFFF) + c; out.append(t & 0xFFFFFFFF); c = t >> 32
     return out
+V_CLASSES = ("in_range", "neg", "below_neg_m", "ge_m", "ge_m_signword")
+def v_class(vv, m, kw):
+    """where the cofactor v stands before k_modinv's finalisation: the loop adds m while v < 0 and subtracts it while v >= m"""
+    if vv < -m: return "below_neg_m"
+    if vv < 0: return "neg"
+    if vv < m: return "in_range"
+    return "ge_m" if vv < 1 << (32 * kw) else "ge_m_signword"
+def sign_word_has_magnitude(w, kw):   # w[kw] is not the sign extension of the word below it
+    return w[kw] != (0xFFFFFFFF if w[kw - 1] >> 31 else 0)
 def wbgcd(y, m, kw, cof=True, stats=None):
+    """stats (a dict) keeps its running maxima over calls ("maxcof", "iters", "final_passes") and gets stats["call"], the record of THIS
+    call: rounds, neg_a_rounds / neg_b_rounds (rounds whose accA / accB came out negative), signword_magnitude (u[kw] or v[kw] held
+    magnitude after some round), start_le64 / cross_le64 (the first round took the n <= 64 branch / a later one did after a start above
+    64 bits), and for gcd == 1: v_class (one of V_CLASSES) and final_passes."""
     a, b = words(y, kw), words(m, kw)
     u, v = words(1, kw + 1), words(0, kw + 1)
     mw = words(m, kw) + [0]
     minv = (-pow(m, -1, 1 << K)) % (1 << K)
     na = nb = kw; iters = 0
+    call = dict(rounds=0, neg_a_rounds=0, neg_b_rounds=0, signword_magnitude=False, start_le64=False, cross_le64=False, v_class=None, final_passes=None)
+    if stats is not None: stats["call"] = call
     while True:
         na, la = bitlen_words(a, na); nb, lb = bitlen_words(b, nb)
         if la == 0: break
         n = max(la, lb)
         if n <= 64:
+            if iters == 0: call["start_le64"] = True
+            elif not call["start_le64"]: call["cross_le64"] = True
             xa, xb = unwords(a[:2]), unwords(b[:2])
         else:
             xa = (extract(a, n - 34, 34, kw) << 30) | (a[0] & MK)
@@ -64,6 +81,7 @@ def wbgcd(y, m, kw, cof=True, stats=None):
         assert Ta[0] & MK == 0 and Tb[0] & MK == 0
         if nega: A2 = negate(A2); f0, g0 = -f0, -g0
         if negb: B2 = negate(B2); f1, g1 = -f1, -g1
+        call["neg_a_rounds"] += nega; call["neg_b_rounds"] += negb
         a[:nw] = A2; b[:nw] = B2
         na = nb = nw                      # either result may be as long as the longer input
         if cof:
@@ -83,15 +101,18 @@ def wbgcd(y, m, kw, cof=True, stats=None):
                 return [((T[w] >> K) | (T[w + 1] << (32 - K))) & 0xFFFFFFFF for w in range(kw + 1)]
             u2, v2 = upd(f0, g0), upd(f1, g1)
             u, v = u2, v2
+            if sign_word_has_magnitude(u, kw) or sign_word_has_magnitude(v, kw): call["signword_magnitude"] = True
             if stats is not None: stats["maxcof"] = max(stats["maxcof"], abs(sunwords(u)) // m, abs(sunwords(v)) // m)
         iters += 1
         assert iters < 2 * 32 * kw // K + 40
     g = unwords(b)
+    call["rounds"] = iters
     if stats is not None: stats["iters"] = max(stats.get("iters", 0), iters)
     if not cof: return g, None
     if g != 1: return g, None
     vv = sunwords(v)
     assert (vv * y - 1) % m == 0
+    call["v_class"] = v_class(vv, m, kw)
     # the kernel's finalisation (kernels_inv.hpp: k_modinv): add m while negative, subtract m while >= m, on kw words + sign word
     passes = 0
     while True:
@@ -104,6 +125,7 @@ def wbgcd(y, m, kw, cof=True, stats=None):
         v = words(t & ((1 << (32 * kw)) - 1), kw) + [(v[kw] + carry) & 0xFFFFFFFF]
         passes += 1
         assert passes < 256
+    call["final_passes"] = passes
     if stats is not None: stats["final_passes"] = max(stats.get("final_passes", 0), passes)
     assert v[kw] == 0 and unwords(v[:kw]) == vv % m
     return g, unwords(v[:kw])
