@@ -151,6 +151,8 @@ extern "C" {
     pub fn zkp_range_challenge_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, out_e: *mut u8, out_e_len: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_generate_proof_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, w: *const zkp_range_ni_witness, e: *const u8, e_len: *const u8, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_verifier_output_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, e: *const u8, e_len: *const u8, out_verdict: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_generate_encrypted_pairs_seeded_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, seed: *const u8, first_index: u64, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_generate_proof_seeded_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, x: *const u32, r: *const u32, seed: *const u8, first_index: u64, e: *const u8, e_len: *const u8, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_correct_key_ni_verify_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, sigma: *const u32, salt: *const u8, salt_len: u32, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_dlog_prove_batch(ctx: *mut zkp_ctx, n_bits: u32, y_bits: u32, batch: u64, N: *const u32, g: *const u32, ni: *const u32, secret: *const u32, r: *const u32, out_x: *mut u32, out_y: *mut u32, flags: u32) -> i32;
     pub fn zkp_dlog_verify_batch(ctx: *mut zkp_ctx, n_bits: u32, y_bits: u32, batch: u64, N: *const u32, g: *const u32, ni: *const u32, x: *const u32, y: *const u32, out_verdict: *mut u8, flags: u32) -> i32;
@@ -180,6 +182,7 @@ extern "C" {
     pub fn zkp_json_range_proof_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, p: *const zkp_range_ni_proofs, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_range_proof_ni_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, bigint_forms: u32, p: *const zkp_range_ni_proofs, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_ni_verify_json_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, batch: u64, n_bits: u32, error_factor: u32, bigint_forms: u32, verifier_n: *const u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_verifier_output_json_batch(ctx: *mut zkp_ctx, text: *const c_char, pairs_off: *const u64, pairs_len: *const u64, proof_off: *const u64, proof_len: *const u64, batch: u64, n_bits: u32, error_factor: u32, n: *const u32, n_stride: u64, range: *const u32, ciphertext: *const u32, e: *const u8, e_len: *const u8, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_correct_key_proof_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, n_bits: u32, batch: u64, out_sigma: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_correct_key_ni_verify_json_batch(ctx: *mut zkp_ctx, text: *const c_char, doc_off: *const u64, doc_len: *const u64, batch: u64, n_bits: u32, n: *const u32, salt: *const u8, salt_len: u32, out_status: *mut u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_json_doc_bound(doc_kind: u32, n_bits: u32, error_factor: u32, bigint_forms: u32) -> u64;

@@ -234,6 +234,23 @@ int32_t zkp_range_generate_proof_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* 
                                        const uint8_t* e, const uint8_t* e_len, uint8_t* out_status, uint32_t flags);
 int32_t zkp_range_verifier_output_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, const uint8_t* e, const uint8_t* e_len,
                                         uint8_t* out_verdict, uint32_t flags);
+/* The two prover steps from a seed: zkp_range_generate_encrypted_pairs_batch and zkp_range_generate_proof_batch with the witness of
+ * zkp_range_sample_witness_batch at p->error_factor rows (1 .. 256; the stream above is unchanged, a row does not depend on the row count).
+ * Step 1 reads p->n, p->range and writes p->c1, p->c2 only; step 2 reads p->n, p->range, x, r, e, e_len and writes p->resp_* only.  Step 2
+ * regenerates exactly the witness step 1 committed to from the same (seed, first_index): the prover keeps 32 bytes between the two
+ * messages, not 4 * EF * kw limbs per session.  The witness never leaves the device and is zeroed there — as are the staged seed and the
+ * staged copies of x and r of a host-pointer call — before the call's blocks are given back, on error returns too.
+ * out_status [B] (nullable): step 1, the sampler's ZKP_VERDICT_MALFORMED cases (range < 3, n == 0, 128 rejected attempts: that session's
+ * witness is all zero, and its c1 / c2 rows are what the unseeded call writes for a zero witness); step 2, those OR-ed with the status of
+ * zkp_range_generate_proof_batch (a challenge shorter than ceil(EF / 8) bytes is ZKP_VERDICT_MALFORMED).  `seed` is always a HOST pointer.
+ * SECURITY CONTRACT, extended.  Besides "never one (seed, index) for two statements": a (seed, index) answers ONE challenge only.  Two
+ * different challenges over the same commitments open some row both as Open (w1, w2) and as Mask (x + w), which reveals x.  The same holds
+ * for a prover who keeps the witness itself; it is stated here because a seed makes answering again easy. */
+int32_t zkp_range_generate_encrypted_pairs_seeded_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, const uint8_t* seed,
+                                                        uint64_t first_index, uint8_t* out_status, uint32_t flags);
+int32_t zkp_range_generate_proof_seeded_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r,
+                                              const uint8_t* seed, uint64_t first_index, const uint8_t* e, const uint8_t* e_len,
+                                              uint8_t* out_status, uint32_t flags);
 
 /* ------------------------------------------------------------------ NiCorrectKeyProof
  * NiCorrectKeyProof::verify (src/zkproofs/correct_key_ni.rs:73-100) for B (key, proof)
@@ -536,6 +553,22 @@ int32_t zkp_range_ni_verify_json_batch(zkp_ctx* ctx, const char* text, const uin
                                        const uint32_t* verifier_n /* [kw], NULL = verify_self: each document's own key */,
                                        uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */,
                                        uint32_t flags);
+/* RangeProof::verifier_output (range_proof.rs:254-355) on the two received documents of an interactive session: EncryptedPairs b and Proof b
+ * are two spans of the same `text` (host memory, uploaded once, like the four offset arrays); one status byte and one verdict byte per
+ * session come out.  = zkp_json_encrypted_pairs_batch and zkp_json_range_proof_batch (device route) into arrays the call owns, then
+ * zkp_range_verifier_output_batch on them; no limb travels to the host.  The statement (n, n_stride, range, ciphertext: n_stride 0 or
+ * n_bits/32) and the verifier's own challenge (e [B][32] left aligned, e_len [B]) are limbs and bytes; ZKP_F_DEVICE_PTRS applies to them and
+ * to out_status and out_verdict.  out_status[b]: the worse of the two documents' reader statuses (ZKP_DOC_INVALID beats ZKP_DOC_HOST_PATH
+ * beats ZKP_DOC_OK; a document with another number of rows than error_factor is ZKP_DOC_HOST_PATH).  out_verdict[b]: what
+ * zkp_range_verifier_output_batch gives where the status is ZKP_DOC_OK (ZKP_VERDICT_MALFORMED for a challenge shorter than
+ * ceil(error_factor / 8) bytes included), ZKP_VERDICT_REJECT everywhere else.  The whole batch is launched and the verdicts of unread
+ * sessions are masked afterwards: such a session costs its share of the launch, changes no other verdict and never fails the call.
+ * n_bits in {1024, 2048, 4096}, error_factor 1 .. 256, batch 0 .. 2^24. */
+int32_t zkp_range_verifier_output_json_batch(zkp_ctx* ctx, const char* text, const uint64_t* pairs_off, const uint64_t* pairs_len,
+                                             const uint64_t* proof_off, const uint64_t* proof_len, uint64_t batch, uint32_t n_bits,
+                                             uint32_t error_factor, const uint32_t* n, uint64_t n_stride, const uint32_t* range,
+                                             const uint32_t* ciphertext, const uint8_t* e, const uint8_t* e_len,
+                                             uint8_t* out_status /* [B] ZKP_DOC_* */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */, uint32_t flags);
 /* {"sigma_vec":["..", x11]} -> sigma [B][11][n_bits/32].  A sigma_vec of another length is ZKP_DOC_INVALID; an over-wide or negative
  * entry is ZKP_DOC_HOST_PATH (that entry is zero, the others are converted). */
 int32_t zkp_json_correct_key_proof_batch(zkp_ctx* ctx, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint32_t n_bits,

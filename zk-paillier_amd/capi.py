@@ -99,6 +99,11 @@ EXPORTS = {
     "zkp_range_generate_proof_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.POINTER(RangeNiWitness), C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_uint32]),
     "zkp_range_verifier_output_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_generate_encrypted_pairs_seeded_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "zkp_range_generate_proof_seeded_batch": (C.c_int32, [C.c_void_p, C.POINTER(RangeNiProofs), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_verifier_output_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_modinv_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_mul_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_mul_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
@@ -636,6 +641,41 @@ class Context:
     def range_verifier_output(self, proofs, e, e_len, out_verdict, device: bool):
         self.check(self.lib.zkp_range_verifier_output_batch(self.h, C.byref(proofs), ptr(e), ptr(e_len), ptr(out_verdict),
                                                             ZKP_F_DEVICE_PTRS if device else 0))
+
+    # ---- the two prover steps from a 32-byte seed (always host bytes): the witness is expanded on the GPU in both and never leaves it
+    def range_generate_encrypted_pairs_seeded(self, proofs, seed: bytes, first_index: int = 0, out_status=None, device: bool = False):
+        """zkp_range_generate_encrypted_pairs_seeded_batch: c1, c2 of `proofs` (proofs.error_factor rows) from (n, range) and the seed"""
+        self.check(self.lib.zkp_range_generate_encrypted_pairs_seeded_batch(self.h, C.byref(proofs), _seed(seed), first_index, ptr(out_status),
+                                                                            ZKP_F_DEVICE_PTRS if device else 0))
+
+    def range_generate_proof_seeded(self, proofs, x, r, seed: bytes, first_index: int, e, e_len, out_status=None, device: bool = False):
+        """zkp_range_generate_proof_seeded_batch: resp_* of `proofs` from (n, range, x, r), the verifier's challenge and the SAME
+        (seed, first_index) that made the encrypted pairs.  One (seed, index) answers one challenge only."""
+        self.check(self.lib.zkp_range_generate_proof_seeded_batch(self.h, C.byref(proofs), ptr(x), ptr(r), _seed(seed), first_index, ptr(e), ptr(e_len),
+                                                                  ptr(out_status), ZKP_F_DEVICE_PTRS if device else 0))
+
+    def range_verifier_output_json(self, pairs_docs, proof_docs, n_bits: int, ef: int, n, range, ciphertext, e, e_len, device: bool = False,
+                                   out_status=None, out_verdict=None):
+        """zkp_range_verifier_output_json_batch: EncryptedPairs document b and Proof document b (two lists) -> (status, verdict) bytes, one pair
+        per session.  n: [n_bits / 32] or [1][n_bits / 32] (one key for the batch) or [B][n_bits / 32]; range [B][kw], ciphertext [B][2 kw],
+        e [B][32], e_len [B].  device: those five and the two outputs are torch cuda tensors (the outputs are made here when not given)."""
+        assert len(pairs_docs) == len(proof_docs)
+        B = len(pairs_docs)
+        buf, off, ln = self._json_docs(list(pairs_docs) + list(proof_docs))
+        if out_status is None or out_verdict is None:
+            if device:
+                import torch
+                out_status = torch.zeros(B, dtype=torch.uint8, device="cuda"); out_verdict = torch.zeros(B, dtype=torch.uint8, device="cuda")
+            else:
+                out_status = np.zeros(B, np.uint8); out_verdict = np.zeros(B, np.uint8)
+        kw = n_bits // 32
+        words = 0 if n is None else (n.numel() if hasattr(n, "numel") else n.size)
+        n_stride = 0 if words <= kw else kw
+        a_off, a_len, b_off, b_len = (np.ascontiguousarray(a) for a in (off[:B], ln[:B], off[B:], ln[B:]))
+        self.check(self.lib.zkp_range_verifier_output_json_batch(self.h, C.cast(buf, C.c_void_p), ptr(a_off), ptr(a_len), ptr(b_off), ptr(b_len), B, n_bits, ef,
+                                                                 ptr(n), n_stride, ptr(range), ptr(ciphertext), ptr(e), ptr(e_len), ptr(out_status),
+                                                                 ptr(out_verdict), ZKP_F_DEVICE_PTRS if device else 0))
+        return out_status, out_verdict
 
     # ---- mod_inv, MulProof (SURVEY 8(f) rank 4)
     def modinv(self, mod_bits, count, a, mod, mod_stride, out, out_status):

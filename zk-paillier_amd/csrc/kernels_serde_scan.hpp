@@ -409,6 +409,14 @@ __global__ void __launch_bounds__(256) k_scan_mask_verdicts(const uint8_t* __res
   if (b < B && status[b] != ZKP_DOC_OK) verdict[b] = ZKP_VERDICT_REJECT;
 }
 
+// a session of two documents: its status is the worse of theirs (INVALID beats HOST_PATH beats OK)
+__global__ void __launch_bounds__(256) k_scan_worse_status(uint8_t* __restrict__ status, const uint8_t* __restrict__ other, uint64_t B) {
+  const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const uint8_t s1 = status[b], s2 = other[b];
+  status[b] = (s1 == ZKP_DOC_INVALID || s2 == ZKP_DOC_INVALID) ? (uint8_t)ZKP_DOC_INVALID : (s1 != ZKP_DOC_OK || s2 != ZKP_DOC_OK) ? (uint8_t)ZKP_DOC_HOST_PATH : (uint8_t)ZKP_DOC_OK;
+}
+
 // ---- CompositeDLogProof::verify on documents: is pair b inside the domain of the limb kernels?
 // wave-uniform: v < n, both kw words, most significant word first: the highest word in which they differ decides (found by ballot)
 __device__ __forceinline__ bool sc_less(const uint32_t* __restrict__ v, const uint32_t* __restrict__ n, uint32_t kw, int lane) {

@@ -428,6 +428,63 @@ extern "C" int32_t zkp_range_generate_proof_batch(zkp_ctx* c, const zkp_range_ni
   return range_prove_entry(c, "zkp_range_generate_proof_batch", p, w, p ? p->error_factor : 0, 2, e, e_len, nullptr, nullptr, out_status, flags);
 } ZKP_CATCH(c)
 
+// The two prover steps of the interactive protocol from a seed: built as zkp_range_ni_prove_seeded_batch is.  Everything is made device-resident
+// in a Stage, the sampler expands rows [0, p->error_factor) of the published stream, and the unseeded step runs as the device-pointer call it
+// already knows (its routing, split plans, key cache and kernels).  step 1 writes c1 / c2 only; step 2 regenerates the SAME witness from the
+// same (seed, first_index) and writes resp_* only.  `s` wipes the witness, the staged seed and the staged x and r on every path out.
+static int32_t range_interactive_seeded(zkp_ctx* c, const char* name, int step, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r,
+                                        const uint8_t* seed, uint64_t first_index, const uint8_t* e, const uint8_t* e_len, uint8_t* out_status, uint32_t flags) {
+  if (!c) return ZKP_EINVAL;
+  if (!range_args_ok(p, RA_RANGE | (step == 1 ? RA_PAIRS : RA_RESP)) || p->error_factor == 0 || !seed || (step == 2 && (!e || !e_len || (p->batch && (!x || !r))))) {
+    c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL;
+  }
+  if (p->batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = p->n_bits / 32, B = p->batch, EF = p->error_factor, rows = B * EF;
+  Stage s(c, flags);
+  zkp_range_ni_proofs d = *p;
+  d.n = s.in(p->n, p->n_stride ? B * kw : kw);
+  d.range = s.in(p->range, B * kw);
+  d.ciphertext = nullptr;                                // (no prover function reads it)
+  d.c1 = d.c2 = nullptr; d.resp_kind = d.resp_j = nullptr; d.resp_w1 = d.resp_r1 = d.resp_w2 = d.resp_r2 = nullptr;
+  if (step == 1) { d.c1 = s.out(p->c1, rows * 2 * kw); d.c2 = s.out(p->c2, rows * 2 * kw); }
+  else {
+    d.resp_kind = s.out(p->resp_kind, rows); d.resp_j = s.out(p->resp_j, rows);
+    d.resp_w1 = s.out(p->resp_w1, rows * kw); d.resp_r1 = s.out(p->resp_r1, rows * kw);
+    d.resp_w2 = s.out(p->resp_w2, rows * kw); d.resp_r2 = s.out(p->resp_r2, rows * kw);
+  }
+  const uint32_t* key = (const uint32_t*)s.host_in(seed, 32);
+  s.secret(key, 32);
+  zkp_range_ni_witness dw{};
+  uint32_t* wit[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (auto& q : wit) { q = s.st ? nullptr : (uint32_t*)s.take(rows * kw * 4); s.secret(q, rows * kw * 4); }
+  dw.w1 = wit[0]; dw.w2 = wit[1]; dw.r1 = wit[2]; dw.r2 = wit[3];
+  const uint8_t *de = nullptr, *dl = nullptr;
+  if (step == 2) {
+    dw.x = s.in(x, B * kw); dw.r = s.in(r, B * kw);
+    if (!s.dev) { s.secret(dw.x, B * kw * 4); s.secret(dw.r, B * kw * 4); }
+    de = s.in(e, B * 32); dl = s.in(e_len, B);
+  }
+  uint8_t* ds = s.out(out_status, B);
+  int32_t st = s.st;
+  if (!st) st = ensure(c, c->scratch[S_SAMPLE_STATUS], B);
+  uint8_t* sampler_status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p;
+  if (!st) st = range_sample_launch(c, d, (uint32_t)EF, key, first_index, wit[0], wit[1], wit[2], wit[3], sampler_status);
+  if (!st) st = step == 1 ? zkp_range_generate_encrypted_pairs_batch(c, &d, &dw, ZKP_F_DEVICE_PTRS)
+                          : zkp_range_generate_proof_batch(c, &d, &dw, de, dl, ds, ZKP_F_DEVICE_PTRS);
+  if (!st) st = seeded_status(c, ds, sampler_status, B, step == 2);      // (step 1 has no status of its own: the sampler's alone)
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+}
+extern "C" int32_t zkp_range_generate_encrypted_pairs_seeded_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint8_t* seed, uint64_t first_index,
+                                                                   uint8_t* out_status, uint32_t flags) try {
+  return range_interactive_seeded(c, "zkp_range_generate_encrypted_pairs_seeded_batch", 1, p, nullptr, nullptr, seed, first_index, nullptr, nullptr, out_status, flags);
+} ZKP_CATCH(c)
+extern "C" int32_t zkp_range_generate_proof_seeded_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r, const uint8_t* seed,
+                                                         uint64_t first_index, const uint8_t* e, const uint8_t* e_len, uint8_t* out_status, uint32_t flags) try {
+  return range_interactive_seeded(c, "zkp_range_generate_proof_seeded_batch", 2, p, x, r, seed, first_index, e, e_len, out_status, flags);
+} ZKP_CATCH(c)
+
 // utils::compute_digest + the Fiat-Shamir glue as an entry point of its own (SURVEY 8(a) row a3)
 extern "C" int32_t zkp_range_challenge_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, uint8_t* out_e, uint8_t* out_e_len, uint32_t flags) try {
   ZKP_ROUTE(c, p ? p->batch * 2 * p->error_factor : 0, p ? 2 * p->n_bits : 0, zkp_range_challenge_batch, p, out_e, out_e_len, flags)

@@ -485,6 +485,53 @@ extern "C" int32_t zkp_range_ni_verify_json_batch(zkp_ctx* c, const char* text, 
   return verify_end(c, s, st, dstat, dv, B);
 } ZKP_CATCH(c)
 
+// RangeProof::verifier_output (range_proof.rs:254-355) on the two received documents of a session: EncryptedPairs b and Proof b are two spans of
+// one text, uploaded once and read by the device route of the two readers into arrays the call owns; the statement and the verifier's own
+// challenge come in as limbs and bytes.  The status of a session is the worse of its two documents'; zkp_range_verifier_output_batch runs on the
+// whole batch — an unread document is zero rows under the caller's key, answered with a verdict of that session alone — and the verdicts of
+// unread sessions are masked afterwards.  The events of zkp_diag_last_json_scan_ms are: upload | pairs read | proofs read | verify.
+extern "C" int32_t zkp_range_verifier_output_json_batch(zkp_ctx* c, const char* text, const uint64_t* pairs_off, const uint64_t* pairs_len, const uint64_t* proof_off,
+                                                        const uint64_t* proof_len, uint64_t B, uint32_t n_bits, uint32_t error_factor, const uint32_t* n, uint64_t n_stride,
+                                                        const uint32_t* range, const uint32_t* ciphertext, const uint8_t* e, const uint8_t* e_len, uint8_t* out_status,
+                                                        uint8_t* out_verdict, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (B == 0) return ZKP_OK;
+  if ((flags & ~(uint32_t)ZKP_F_DEVICE_PTRS) || !text || !pairs_off || !pairs_len || !proof_off || !proof_len || !n || !range || !ciphertext || !e || !e_len || !out_status ||
+      !out_verdict || !key_bits_ok(n_bits) || error_factor == 0 || error_factor > 256 || B > (1ull << 24) || (n_stride != 0 && n_stride != n_bits / 32)) {
+    c->err = "zkp_range_verifier_output_json_batch: invalid argument"; return ZKP_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const char* name = "zkp_range_verifier_output_json_batch";
+  const uint64_t kw = n_bits / 32, rows = B * error_factor;
+  Stage s(c, flags);
+  uint8_t* dstat = s.out(out_status, B);
+  uint8_t* dv = s.out(out_verdict, B);
+  zkp_range_ni_proofs d{};
+  d.n_bits = n_bits; d.error_factor = error_factor; d.batch = B; d.n_stride = n_stride;
+  d.n = s.in(n, n_stride ? B * kw : kw); d.range = s.in(range, B * kw); d.ciphertext = s.in(ciphertext, B * 2 * kw);
+  const uint8_t* de = s.in(e, B * 32);
+  const uint8_t* dl = s.in(e_len, B);
+  d.c1 = (uint32_t*)s.take(rows * 2 * kw * 4); d.c2 = (uint32_t*)s.take(rows * 2 * kw * 4);
+  d.resp_kind = (uint8_t*)s.take(rows); d.resp_j = (uint8_t*)s.take(rows);
+  d.resp_w1 = (uint32_t*)s.take(rows * kw * 4); d.resp_r1 = (uint32_t*)s.take(rows * kw * 4);
+  d.resp_w2 = (uint32_t*)s.take(rows * kw * 4); d.resp_r2 = (uint32_t*)s.take(rows * kw * 4);
+  uint8_t* dstat2 = (uint8_t*)s.take(B);
+  ScanText up{};
+  int32_t st = s.st;
+  if (!st) st = scan_begin(c, s, text, pairs_off, pairs_len, proof_off, proof_len, B, &up);
+  if (!st) st = scan_event(c, 1);
+  if (!st) st = json_scan(c, s, name, W_DOC_PAIRS, up, text, pairs_off, pairs_len, 0, d, nullptr, dstat, 0, false);
+  if (!st) st = scan_event(c, 2);
+  if (!st) st = json_scan(c, s, name, W_DOC_PROOF, up, text, proof_off, proof_len, 0, d, nullptr, dstat2, 0, false);
+  if (!st) st = scan_event(c, 3);
+  if (!st) {
+    hipLaunchKernelGGL(k_scan_worse_status, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, dstat, (const uint8_t*)dstat2, B);
+    if (hipGetLastError() != hipSuccess) { st = ZKP_EDEVICE; c->err = "k_scan_worse_status launch"; }
+  }
+  if (!st) st = zkp_range_verifier_output_batch(c, &d, de, dl, dv, ZKP_F_DEVICE_PTRS);
+  return verify_end(c, s, st, dstat, dv, B);
+} ZKP_CATCH(c)
+
 // NiCorrectKeyProof::verify on documents: the same three steps with sigma in a block the call owns.  An unread document leaves zero (or, where
 // one number overflowed, partly converted) sigma rows: k_ck_check answers them with a verdict of that proof alone, masked afterwards.
 extern "C" int32_t zkp_correct_key_ni_verify_json_batch(zkp_ctx* c, const char* text, const uint64_t* doc_off, const uint64_t* doc_len, uint64_t B, uint32_t n_bits,

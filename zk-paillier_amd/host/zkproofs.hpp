@@ -644,6 +644,77 @@ struct RangeProof {
     if (verdict == ZKP_VERDICT_MALFORMED) throw Panic("RangeProof::verifier_output: malformed proof (the reference would panic)");
     return Result(verdict == ZKP_VERDICT_ACCEPT);
   }
+
+  // ---- whole batches of sessions under one key, one GPU call per step.  The prover keeps a ProverSeed between message 1 and message 3 instead
+  // of DataRandomnessPairs: both steps expand the witness of session b from (seed, first_index + b) ON THE GPU (the stream is defined in
+  // include/zkp_hip.h), where it is wiped before the call returns.  A (seed, index) commits to ONE statement and answers ONE challenge: a second
+  // challenge over the same commitments opens some row both ways and gives x away.
+  struct ProverSeed {
+    uint8_t bytes[32];
+    ProverSeed() { std::memset(bytes, 0, sizeof bytes); }
+    static ProverSeed fresh() { ProverSeed s; detail::ChaChaRng::os_random(s.bytes, sizeof s.bytes); return s; }     // (the source of prove_batch_seeded)
+    ~ProverSeed() { detail::ChaChaRng::wipe(bytes, sizeof bytes); }
+  };
+  // :128-193 for B sessions: EncryptedPairs only — there is no DataRandomnessPairs to hand back
+  static std::vector<EncryptedPairs> generate_encrypted_pairs_batch_seeded(const EncryptionKey& ek, const std::vector<BigInt>& ranges, size_t error_factor,
+                                                                           const ProverSeed& seed, uint64_t first_index = 0) {
+    Engine& e = Engine::instance();
+    const uint32_t nb = width_for(ek.n), kw = nb / 32;
+    const size_t B = ranges.size(), EF = error_factor;
+    std::vector<EncryptedPairs> out(B);
+    if (B == 0) return out;
+    std::vector<uint32_t> n(kw);
+    ek.n.to_limbs(n.data(), kw);
+    RangeSlab s(B, EF, kw, RangeSlab::STATEMENT | RangeSlab::PAIRS);
+    parallel_for(B, [&](size_t b) { s.put_statement(b, ranges[b], BigInt()); });      // (no prover function reads the ciphertext)
+    std::vector<uint8_t> status(B, 0);
+    const zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
+    e.check(zkp_range_generate_encrypted_pairs_seeded_batch(e.ctx(), &p, seed.bytes, first_index, status.data(), 0), "zkp_range_generate_encrypted_pairs_seeded_batch");
+    statuses_ok(status, "RangeProof::generate_encrypted_pairs: malformed (an empty interval to sample from: the reference would panic)");
+    parallel_for(B, [&](size_t b) { s.read_pairs(b, out[b]); });
+    return out;
+  }
+  // :210-252 for B sessions, with the seed and first_index of their generate_encrypted_pairs_batch_seeded
+  static std::vector<Proof> generate_proof_batch_seeded(const EncryptionKey& ek, const std::vector<BigInt>& xs, const std::vector<BigInt>& rs,
+                                                        const std::vector<ChallengeBits>& challenges, const std::vector<BigInt>& ranges, size_t error_factor,
+                                                        const ProverSeed& seed, uint64_t first_index = 0) {
+    Engine& e = Engine::instance();
+    const uint32_t nb = width_for(ek.n), kw = nb / 32;
+    const size_t B = ranges.size(), EF = error_factor;
+    if (xs.size() != B || rs.size() != B || challenges.size() != B) throw std::invalid_argument("RangeProof::generate_proof_batch_seeded: one secret and one challenge per session");
+    std::vector<Proof> out(B);
+    if (B == 0) return out;
+    std::vector<uint32_t> n(kw);
+    ek.n.to_limbs(n.data(), kw);
+    RangeSlab s(B, EF, kw, RangeSlab::STATEMENT | RangeSlab::RESPONSES);
+    RangeWitness wt(B, EF, kw, true, false);
+    std::vector<uint8_t> eb(B * 32), elen(B), status(B, 0);
+    for (size_t b = 0; b < B; b++) {
+      s.put_statement(b, ranges[b], BigInt());
+      wt.put_secret(b, xs[b], rs[b]);
+      uint8_t one[32];
+      pack_challenge(challenges[b], one, elen[b]);
+      std::memcpy(&eb[b * 32], one, 32);
+    }
+    const zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
+    const int32_t st = zkp_range_generate_proof_seeded_batch(e.ctx(), &p, wt.x(), wt.r(), seed.bytes, first_index, eb.data(), elen.data(), status.data(), 0);
+    wt.wipe_secrets();                                  // x and r: gone before this call returns, whatever it returns
+    e.check(st, "zkp_range_generate_proof_seeded_batch");
+    statuses_ok(status, "RangeProof::generate_proof: malformed (the reference would panic: bits_of_e[i])");
+    parallel_for(B, [&](size_t b) { s.read_proof(b, out[b]); });
+    return out;
+  }
+  // :254-355 for B sessions on the two received documents of each: zkp_range_verifier_output_json_batch tokenises, converts and verifies on the
+  // GPU.  A session it hands back (ZKP_DOC_HOST_PATH: valid documents the fixed layout cannot carry), one whose statement the layout cannot
+  // carry and one whose challenge has more than 32 bytes are parsed here and go through verifier_output, which handles signed and over-wide
+  // values; a document that is no EncryptedPairs / Proof is the panic `from_str(..).unwrap()` is in the reference.  A panic of the reference
+  // is a Result that throws when looked at.  Defined behind serde_json, at the end of this header.
+  static std::vector<Result> verifier_output_json_batch(const EncryptionKey& ek, const std::vector<ChallengeBits>& challenges, const std::vector<std::string>& pairs_docs,
+                                                        const std::vector<std::string>& proof_docs, const std::vector<BigInt>& ranges, const std::vector<BigInt>& cipher_xs,
+                                                        size_t error_factor);
+
+ private:
+  static void statuses_ok(const std::vector<uint8_t>& status, const char* what) { for (uint8_t s : status) if (s != 0) throw Panic(what); }
 };
 
 // ------------------------------------------------------------------ NiCorrectKeyProof
@@ -1688,12 +1759,82 @@ std::vector<std::string> to_string_batch(const std::vector<T>& v, BigintText key
                                       "zkp_json_write_sigma_batch");
 }
 
+namespace detail_json {
+// EncryptedPairs {"c1":[..],"c2":[..]} and Proof [{"Open":{..}} | {"Mask":{..}}, ..] (range_proof.rs:32-81) at the cursor: signed integers of any
+// size, any number of rows
+inline void read_encrypted_pairs(Cur& j, EncryptedPairs& ep) {
+  auto vec = [&](std::vector<BigInt>& v) { j.expect('['); if (!j.eat(']')) { do v.push_back(j.dec()); while (j.eat(',')); j.expect(']'); } };
+  unsigned s2 = 0;
+  j.object([&](const std::string& f) {
+    if (f == "c1") { if (s2 & 1) j.fail("duplicate field"); s2 |= 1; vec(ep.c1); return true; }
+    if (f == "c2") { if (s2 & 2) j.fail("duplicate field"); s2 |= 2; vec(ep.c2); return true; }
+    return false;
+  });
+  if (s2 != 3) j.fail("missing field of EncryptedPairs");
+}
+inline void read_proof(Cur& j, Proof& proof) {
+  j.expect('[');
+  if (j.eat(']')) return;
+  do {
+    Response rs;
+    int variants = 0;
+    j.object([&](const std::string& var) {
+      if (++variants > 1) j.fail("expected a single-variant enum map");
+      unsigned s3 = 0;
+      if (var == "Open") {
+        rs.kind = Response::Open;
+        j.object([&](const std::string& f) {
+          BigInt* dst = f == "w1" ? &rs.w1 : f == "r1" ? &rs.r1 : f == "w2" ? &rs.w2 : f == "r2" ? &rs.r2 : nullptr;
+          if (!dst) return false;
+          const unsigned bit = f == "w1" ? 1 : f == "r1" ? 2 : f == "w2" ? 4 : 8;
+          if (s3 & bit) j.fail("duplicate field");
+          s3 |= bit;
+          *dst = j.dec();
+          return true;
+        });
+        if (s3 != 15) j.fail("missing field of Response::Open");
+      } else if (var == "Mask") {
+        rs.kind = Response::Mask;
+        j.object([&](const std::string& f) {
+          if (f == "j") { if (s3 & 1) j.fail("duplicate field"); s3 |= 1; const uint64_t v = j.uint(); if (v > 255) j.fail("j is a u8"); rs.j = (uint8_t)v; return true; }
+          if (f == "masked_x") { if (s3 & 2) j.fail("duplicate field"); s3 |= 2; rs.masked_x = j.dec(); return true; }
+          if (f == "masked_r") { if (s3 & 4) j.fail("duplicate field"); s3 |= 4; rs.masked_r = j.dec(); return true; }
+          return false;
+        });
+        if (s3 != 7) j.fail("missing field of Response::Mask");
+      } else j.fail("unknown variant of Response");
+      return true;
+    });
+    if (variants != 1) j.fail("expected a single-variant enum map");
+    proof.responses.push_back(std::move(rs));
+  } while (j.eat(','));
+  j.expect(']');
+}
+}  // namespace detail_json
+
+// serde_json::from_str::<EncryptedPairs> / ::<Proof> on the HOST, for the documents of an interactive session the GPU readers hand back
+inline EncryptedPairs encrypted_pairs_from_str_host(const std::string& doc) {
+  detail_json::Cur j{doc};
+  EncryptedPairs out;
+  detail_json::read_encrypted_pairs(j, out);
+  j.ws();
+  if (j.p != doc.size()) j.fail("trailing characters");
+  return out;
+}
+inline Proof proof_from_str_host(const std::string& doc) {
+  detail_json::Cur j{doc};
+  Proof out;
+  detail_json::read_proof(j, out);
+  j.ws();
+  if (j.p != doc.size()) j.fail("trailing characters");
+  return out;
+}
+
 inline RangeProofNi range_proof_ni_from_str(const std::string& doc, BigintText key_form = BigintText::Dec, BigintText bigint_form = BigintText::Dec) {
   detail_json::Cur j{doc};
   RangeProofNi out;
   unsigned seen = 0;
   auto once = [&](unsigned bit) { if (seen & bit) j.fail("duplicate field"); seen |= bit; };
-  auto vec = [&](std::vector<BigInt>& v) { j.expect('['); if (!j.eat(']')) { do v.push_back(j.dec()); while (j.eat(',')); j.expect(']'); } };
   j.object([&](const std::string& nm) {
     if (nm == "ek") {
       once(1);
@@ -1703,55 +1844,9 @@ inline RangeProofNi range_proof_ni_from_str(const std::string& doc, BigintText k
       out.ek.nn = out.ek.n * out.ek.n;       // MinimalEncryptionKey -> EncryptionKey { n, nn = n * n } [upstream kzen-paillier]
     } else if (nm == "range") { once(2); out.range = j.bigint(bigint_form); }
     else if (nm == "ciphertext") { once(4); out.ciphertext = j.bigint(bigint_form); }
-    else if (nm == "encrypted_pairs") {
-      once(8);
-      unsigned s2 = 0;
-      j.object([&](const std::string& f) {
-        if (f == "c1") { if (s2 & 1) j.fail("duplicate field"); s2 |= 1; vec(out.encrypted_pairs.c1); return true; }
-        if (f == "c2") { if (s2 & 2) j.fail("duplicate field"); s2 |= 2; vec(out.encrypted_pairs.c2); return true; }
-        return false;
-      });
-      if (s2 != 3) j.fail("missing field of EncryptedPairs");
-    } else if (nm == "proof") {
-      once(16);
-      j.expect('[');
-      if (!j.eat(']')) {
-        do {
-          Response rs;
-          int variants = 0;
-          j.object([&](const std::string& var) {
-            if (++variants > 1) j.fail("expected a single-variant enum map");
-            unsigned s3 = 0;
-            if (var == "Open") {
-              rs.kind = Response::Open;
-              j.object([&](const std::string& f) {
-                BigInt* dst = f == "w1" ? &rs.w1 : f == "r1" ? &rs.r1 : f == "w2" ? &rs.w2 : f == "r2" ? &rs.r2 : nullptr;
-                if (!dst) return false;
-                const unsigned bit = f == "w1" ? 1 : f == "r1" ? 2 : f == "w2" ? 4 : 8;
-                if (s3 & bit) j.fail("duplicate field");
-                s3 |= bit;
-                *dst = j.dec();
-                return true;
-              });
-              if (s3 != 15) j.fail("missing field of Response::Open");
-            } else if (var == "Mask") {
-              rs.kind = Response::Mask;
-              j.object([&](const std::string& f) {
-                if (f == "j") { if (s3 & 1) j.fail("duplicate field"); s3 |= 1; const uint64_t v = j.uint(); if (v > 255) j.fail("j is a u8"); rs.j = (uint8_t)v; return true; }
-                if (f == "masked_x") { if (s3 & 2) j.fail("duplicate field"); s3 |= 2; rs.masked_x = j.dec(); return true; }
-                if (f == "masked_r") { if (s3 & 4) j.fail("duplicate field"); s3 |= 4; rs.masked_r = j.dec(); return true; }
-                return false;
-              });
-              if (s3 != 7) j.fail("missing field of Response::Mask");
-            } else j.fail("unknown variant of Response");
-            return true;
-          });
-          if (variants != 1) j.fail("expected a single-variant enum map");
-          out.proof.responses.push_back(std::move(rs));
-        } while (j.eat(','));
-        j.expect(']');
-      }
-    } else if (nm == "error_factor") { once(32); out.error_factor = (size_t)j.uint(); }
+    else if (nm == "encrypted_pairs") { once(8); detail_json::read_encrypted_pairs(j, out.encrypted_pairs); }
+    else if (nm == "proof") { once(16); detail_json::read_proof(j, out.proof); }
+    else if (nm == "error_factor") { once(32); out.error_factor = (size_t)j.uint(); }
     else return false;
     return true;
   });
@@ -1795,6 +1890,60 @@ inline std::vector<Result> RangeProofNi::verify_json_batch(const std::vector<std
     if (!err.empty()) { out[b] = Result::panicked("called `Result::unwrap()` on an `Err` value: " + err); continue; }
     if (ek && !(q.ek == *ek)) { out[b] = Result::panicked("assertion failed: `(left == right)` ek"); continue; }
     out[b] = verify_batch(q.ek, {&q})[0];       // ZKP_DOC_HOST_PATH (or a key of another width): the host path for integers of any size and sign
+  }
+  return out;
+}
+
+inline std::vector<Result> RangeProof::verifier_output_json_batch(const EncryptionKey& ek, const std::vector<ChallengeBits>& challenges, const std::vector<std::string>& pairs_docs,
+                                                                  const std::vector<std::string>& proof_docs, const std::vector<BigInt>& ranges,
+                                                                  const std::vector<BigInt>& cipher_xs, size_t error_factor) {
+  const size_t B = pairs_docs.size(), EF = error_factor;
+  if (proof_docs.size() != B || challenges.size() != B || ranges.size() != B || cipher_xs.size() != B)
+    throw std::invalid_argument("RangeProof::verifier_output_json_batch: one challenge, two documents and one statement per session");
+  if (B == 0) return {};
+  const bool key_carried = !ek.n.is_negative() && ek.n.is_odd() && ek.n.bit_length() <= 4096 && ek.n.bit_length() >= 2;
+  if (!key_carried) return std::vector<Result>(B, Result::unsupported("RangeProof::verifier_output: the key is not a positive odd integer of at most 4096 bits"));
+  const uint32_t nb = width_for(ek.n), kw = nb / 32;
+  // the sessions the one call takes: a challenge the ABI carries and a statement within the widths; at least one row, at most 256
+  std::vector<size_t> idx;
+  if (EF >= 1 && EF <= 256)
+    for (size_t b = 0; b < B; b++)
+      if (challenges[b].bytes.size() <= 32 && ranges[b].fits_limbs(kw) && cipher_xs[b].fits_limbs(2 * kw)) idx.push_back(b);
+  std::vector<uint8_t> status(B, ZKP_DOC_HOST_PATH), verdict(B, ZKP_VERDICT_REJECT);
+  if (!idx.empty()) {
+    const size_t G = idx.size();
+    std::string text;
+    std::vector<uint64_t> ao(G), al(G), po(G), pl(G);
+    for (size_t q = 0; q < G; q++) { ao[q] = text.size(); al[q] = pairs_docs[idx[q]].size(); text += pairs_docs[idx[q]]; }
+    for (size_t q = 0; q < G; q++) { po[q] = text.size(); pl[q] = proof_docs[idx[q]].size(); text += proof_docs[idx[q]]; }
+    std::vector<uint32_t> n(kw);
+    ek.n.to_limbs(n.data(), kw);
+    RangeSlab s(G, EF, kw, RangeSlab::STATEMENT);
+    std::vector<uint8_t> eb(G * 32), elen(G), st(G, ZKP_DOC_HOST_PATH), v(G, ZKP_VERDICT_REJECT);
+    for (size_t q = 0; q < G; q++) {
+      s.put_statement(q, ranges[idx[q]], cipher_xs[idx[q]]);
+      uint8_t one[32];
+      pack_challenge(challenges[idx[q]], one, elen[q]);
+      std::memcpy(&eb[q * 32], one, 32);
+    }
+    const zkp_range_ni_proofs p = s.abi(nb, n.data(), 0);
+    Engine& e = Engine::instance();
+    e.check(zkp_range_verifier_output_json_batch(e.ctx(), text.data(), ao.data(), al.data(), po.data(), pl.data(), G, nb, (uint32_t)EF, p.n, 0, p.range, p.ciphertext, eb.data(),
+                                                 elen.data(), st.data(), v.data(), 0), "zkp_range_verifier_output_json_batch");
+    for (size_t q = 0; q < G; q++) { status[idx[q]] = st[q]; verdict[idx[q]] = v[q]; }
+  }
+  std::vector<Result> out(B, Result(false));
+  for (size_t b = 0; b < B; b++) {
+    if (status[b] == ZKP_DOC_OK) {
+      out[b] = verdict[b] == ZKP_VERDICT_MALFORMED ? Result::panicked("RangeProof::verifier_output: malformed proof (the reference would panic)") : Result(verdict[b] == ZKP_VERDICT_ACCEPT);
+      continue;
+    }
+    EncryptedPairs ep; Proof pr;
+    try { ep = serde_json::encrypted_pairs_from_str_host(pairs_docs[b]); pr = serde_json::proof_from_str_host(proof_docs[b]); }
+    catch (const std::exception& err) { out[b] = Result::panicked(std::string("called `Result::unwrap()` on an `Err` value: ") + err.what()); continue; }
+    // ZKP_DOC_HOST_PATH, or a session kept from the call: the single-session path for integers of any size and sign
+    try { out[b] = verifier_output(ek, challenges[b], ep, pr, ranges[b], cipher_xs[b], EF); }
+    catch (const Panic& panic) { out[b] = Result::panicked(panic.what()); }
   }
   return out;
 }
