@@ -22,6 +22,7 @@ pub const ZKP_RESP_OPEN: u8 = 0;
 pub const ZKP_RESP_MASK: u8 = 1;
 pub const ZKP_SECURITY_PARAMETER: usize = 128;
 pub const ZKP_CORRECT_KEY_M2: usize = 11;
+pub const ZKP_SEEDED_KIND_RANGE_COMMIT: u32 = 7;
 pub const ZKP_Z1_EXTRA_LIMBS: usize = 16;
 pub const ZKP_INV_OK: u8 = 0;
 pub const ZKP_INV_NONE: u8 = 1;
@@ -153,6 +154,9 @@ extern "C" {
     pub fn zkp_range_verifier_output_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, e: *const u8, e_len: *const u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_generate_encrypted_pairs_seeded_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, seed: *const u8, first_index: u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_range_generate_proof_seeded_batch(ctx: *mut zkp_ctx, p: *const zkp_range_ni_proofs, x: *const u32, r: *const u32, seed: *const u8, first_index: u64, e: *const u8, e_len: *const u8, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_verifier_commit_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, n_stride: u64, e_len: u32, seed: *const u8, first_index: u64, out_com: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_verifier_reveal_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, n_stride: u64, e_len: u32, seed: *const u8, first_index: u64, out_r: *mut u32, out_e: *mut u8, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_range_verify_commit_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, n_stride: u64, com: *const u32, r: *const u32, e: *const u8, e_len: *const u8, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_correct_key_ni_verify_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, sigma: *const u32, salt: *const u8, salt_len: u32, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_dlog_prove_batch(ctx: *mut zkp_ctx, n_bits: u32, y_bits: u32, batch: u64, N: *const u32, g: *const u32, ni: *const u32, secret: *const u32, r: *const u32, out_x: *mut u32, out_y: *mut u32, flags: u32) -> i32;
     pub fn zkp_dlog_verify_batch(ctx: *mut zkp_ctx, n_bits: u32, y_bits: u32, batch: u64, N: *const u32, g: *const u32, ni: *const u32, x: *const u32, y: *const u32, out_verdict: *mut u8, flags: u32) -> i32;

@@ -251,6 +251,48 @@ int32_t zkp_range_generate_encrypted_pairs_seeded_batch(zkp_ctx* ctx, const zkp_
 int32_t zkp_range_generate_proof_seeded_batch(zkp_ctx* ctx, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r,
                                               const uint8_t* seed, uint64_t first_index, const uint8_t* e, const uint8_t* e_len,
                                               uint8_t* out_status, uint32_t flags);
+/* The verifier's commitment to its challenge, for whole batches of sessions: RangeProof::verifier_commit (range_proof.rs:118-126) draws the
+ * challenge bits e and a randomness r and sends com = Enc(ek_v, m, r) with m = from_bytes(SHA256(e)); RangeProof::verify_commit
+ * (range_proof.rs:195-208) is the prover's check of the revealed (r, e) against com before it trusts the challenge it answered.
+ *   m: the 32 digest bytes read big-endian (result_bigint()).  It does not pass through to_bytes: a digest with leading zero bytes is simply
+ *   a smaller integer.
+ * The stream of (r, e), by the construction of zkp_nonce_sample_batch below (state word 15 = 0x80000000 | kind << 20 | slot << 4 | field) with
+ * a kind of its own, ZKP_SEEDED_KIND_RANGE_COMMIT, slot 0 (tests/seeded_commit_model.py restates it):
+ *   field 0 = r = sample_below(n), the rule above word for word, at most 128 attempts;
+ *   field 1 = e = the first e_len bytes of keystream block 0: byte k is bits 8 (k % 4) .. 8 (k % 4) + 7 of word k / 4.  No rejection.
+ *   e_len is 1 .. 32 in the seeded calls (5 = the reference's STATISTICAL_ERROR_FACTOR / 8); anything else is ZKP_EINVAL, no byte touched.
+ * zkp_range_verifier_commit_seeded_batch expands (seed, first_index + b) on the device, hashes e into m and writes out_com[b] = Enc(m, r)
+ * under n (n_stride 0: one key for the batch, or n_bits/32: one per session).  It writes out_com (and out_status) only; r, e and m never
+ * leave the device.  zkp_range_verifier_reveal_seeded_batch regenerates exactly the (r, e) that call committed to, from the same
+ * (n, e_len, seed, first_index), for the decommit message and for the verifier's own zkp_range_verifier_output_batch /
+ * zkp_range_verifier_output_json_batch: out_r [B][kw], out_e [B][32] left aligned — all 32 bytes of a row are written, zero past e_len.
+ * The verifier keeps 32 bytes between its messages.  In both calls the staged seed and every device copy of r, e and m (the staged copies
+ * of out_r / out_e of a host-pointer call included) are zeroed on the device before the call's blocks are given back, on error returns too.
+ * zkp_range_verify_commit_batch: out_verdict[b] = ZKP_VERDICT_ACCEPT iff com[b] == Enc(from_bytes(SHA256(e[b][0 .. e_len[b]))), r[b]) under
+ * n, ZKP_VERDICT_REJECT otherwise.  The stored com is compared as it is, so a com >= n^2 never matches (the `expected` shape of
+ * zkp_paillier_enc_check_batch, whose launch this is); e_len[b] is 0 .. 32, and zero bytes hash the empty string, as the reference would.
+ * KEY DOMAIN.  That of zkp_paillier_enc_batch — n odd — and, OUR rule, bit_length(n) > 256: m < 2^256 must be a canonical plaintext, and a
+ * Paillier key below 257 bits is no key.  A key outside the domain does not fail the call: the three calls return what the Enc call under
+ * that key returns (ZKP_OK; zkp_paillier_enc_batch writes zeros under an even n), and the session is ZKP_VERDICT_MALFORMED — in out_status
+ * of the seeded calls, with r, e and com all zero, and in out_verdict of zkp_range_verify_commit_batch, as is a session whose e_len[b] is
+ * above 32.  The sampler's failures (n == 0, 128 rejected attempts) are ZKP_VERDICT_MALFORMED for that session too: its r and e are zero in
+ * both seeded calls, its com is what a zero (r, e) gives, zero; the other sessions are unaffected.
+ * `seed` is always a HOST pointer; ZKP_F_DEVICE_PTRS applies to the limb, byte and verdict arrays (a device out_r is 16-byte aligned).
+ * n_bits in {1024, 2048, 4096}, batch 0 .. 2^24, out_status [B] nullable.
+ * SECURITY CONTRACT.  A (seed, index) pair belongs to ONE session: the same pair under another key or in another session repeats (r, e).
+ * The commitment hides e only while r is secret, and the seed is worth both.  Reveal AFTER the prover's encrypted pairs have arrived,
+ * never before: a prover who knows e before it commits can answer without knowing x.  Draw the seed from the operating system, wipe it
+ * after the reveal. */
+#define ZKP_SEEDED_KIND_RANGE_COMMIT 7u
+int32_t zkp_range_verifier_commit_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                               uint32_t e_len, const uint8_t* seed, uint64_t first_index,
+                                               uint32_t* out_com /* [B][2kw] */, uint8_t* out_status /* [B], nullable */, uint32_t flags);
+int32_t zkp_range_verifier_reveal_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                               uint32_t e_len, const uint8_t* seed, uint64_t first_index, uint32_t* out_r /* [B][kw] */,
+                                               uint8_t* out_e /* [B][32] */, uint8_t* out_status /* [B], nullable */, uint32_t flags);
+int32_t zkp_range_verify_commit_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                      const uint32_t* com /* [B][2kw] */, const uint32_t* r /* [B][kw] */, const uint8_t* e /* [B][32] */,
+                                      const uint8_t* e_len /* [B] */, uint8_t* out_verdict /* [B] ZKP_VERDICT_* */, uint32_t flags);
 
 /* ------------------------------------------------------------------ NiCorrectKeyProof
  * NiCorrectKeyProof::verify (src/zkproofs/correct_key_ni.rs:73-100) for B (key, proof)

@@ -8,6 +8,6 @@ from .capi import (Context, MultiContext, RangeNiProofs, RangeNiWitness, ZkpErro
                    JSON_DOC_ENCRYPTED_PAIRS, JSON_DOC_RANGE_PROOF, JSON_DOC_RANGE_PROOF_NI, JSON_DOC_CORRECT_KEY_PROOF, json_doc_bound,
                    JSON_DOC_DLOG_PROOF, JSON_DOC_DLOG_STATEMENT, JSON_DOC_ZERO_STATEMENT, JSON_DOC_ZERO_PROOF, JSON_DOC_CIPHERTEXT_STATEMENT, JSON_DOC_CIPHERTEXT_PROOF,
                    JSON_DOC_VERLIN_STATEMENT, JSON_DOC_VERLIN_PROOF, JSON_DOC_MUL_STATEMENT, JSON_DOC_MUL_PROOF, SIGMA_FIELDS, SigmaFields,
-                   SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KIND_DLOG, SEEDED_KIND_VERLIN, SEEDED_KIND_MUL,
+                   SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KIND_DLOG, SEEDED_KIND_VERLIN, SEEDED_KIND_MUL, SEEDED_KIND_RANGE_COMMIT,
                    SECURITY_PARAMETER, CORRECT_KEY_M2, ZKP_F_DEVICE_PTRS, EXPORTS, DIAG_EXPORTS)
 from .batch import RangeBatch, make_range_witness  # noqa: F401

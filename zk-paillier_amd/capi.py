@@ -104,6 +104,12 @@ EXPORTS = {
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_range_verifier_output_json_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                                          C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_verifier_commit_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64,
+                                                           C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_verifier_reveal_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_range_verify_commit_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_uint32]),
     "zkp_modinv_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_mul_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_mul_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
@@ -196,6 +202,7 @@ EXPORTS = {
 Z1_EXTRA_LIMBS = 16
 SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KIND_DLOG = 1, 2, 3, 4
 SEEDED_KIND_VERLIN, SEEDED_KIND_MUL = 5, 6
+SEEDED_KIND_RANGE_COMMIT = 7
 _lib = None
 
 
@@ -676,6 +683,24 @@ class Context:
                                                                  ptr(n), n_stride, ptr(range), ptr(ciphertext), ptr(e), ptr(e_len), ptr(out_status),
                                                                  ptr(out_verdict), ZKP_F_DEVICE_PTRS if device else 0))
         return out_status, out_verdict
+
+    # ---- the verifier's commitment to its challenge (RangeProof::verifier_commit / verify_commit) for whole batches of sessions
+    def range_verifier_commit_seeded(self, n_bits, batch, n, n_stride, e_len: int, seed: bytes, first_index: int, out_com, out_status=None):
+        """zkp_range_verifier_commit_seeded_batch: out_com[b] = Enc(SHA256(e), r) with (r, e) expanded from (seed, first_index + b) on the GPU;
+        neither leaves it.  One (seed, index) belongs to one session."""
+        self.check(self.lib.zkp_range_verifier_commit_seeded_batch(self.h, n_bits, batch, ptr(n), n_stride, e_len, _seed(seed), first_index, ptr(out_com),
+                                                                   ptr(out_status), self._flags(n, out_com, out_status)))
+
+    def range_verifier_reveal_seeded(self, n_bits, batch, n, n_stride, e_len: int, seed: bytes, first_index: int, out_r, out_e, out_status=None):
+        """zkp_range_verifier_reveal_seeded_batch: the (r, e) the commit call committed to, from the SAME (n, e_len, seed, first_index):
+        out_r [B][kw], out_e [B][32] left aligned.  Only after the prover's encrypted pairs have arrived."""
+        self.check(self.lib.zkp_range_verifier_reveal_seeded_batch(self.h, n_bits, batch, ptr(n), n_stride, e_len, _seed(seed), first_index, ptr(out_r),
+                                                                   ptr(out_e), ptr(out_status), self._flags(n, out_r, out_e, out_status)))
+
+    def range_verify_commit(self, n_bits, batch, n, n_stride, com, r, e, e_len, out_verdict):
+        """zkp_range_verify_commit_batch: out_verdict[b] = ACCEPT iff com[b] == Enc(SHA256(e[b][:e_len[b]]), r[b])"""
+        self.check(self.lib.zkp_range_verify_commit_batch(self.h, n_bits, batch, ptr(n), n_stride, ptr(com), ptr(r), ptr(e), ptr(e_len), ptr(out_verdict),
+                                                          self._flags(n, com, r, e, e_len, out_verdict)))
 
     # ---- mod_inv, MulProof (SURVEY 8(f) rank 4)
     def modinv(self, mod_bits, count, a, mod, mod_stride, out, out_status):

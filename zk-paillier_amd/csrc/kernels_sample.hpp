@@ -1,6 +1,7 @@
 // kernels_sample.hpp — the witness of RangeProofNi::prove expanded on the device from a 32-byte seed (include/zkp_hip.h:
 // zkp_range_sample_witness_batch; the stream is defined in DESIGN.md section 4 and restated by tests/seeded_model.py), and below it the
-// nonces of the sigma proofs and of CompositeDLogProof (zkp_nonce_sample_batch, tests/seeded_nonce_model.py).
+// nonces of the sigma proofs and of CompositeDLogProof (zkp_nonce_sample_batch, tests/seeded_nonce_model.py), and the two operands of the verifier's
+// commitment of the interactive RangeProof (zkp_range_verifier_commit_seeded_batch, tests/seeded_commit_model.py).
 //
 // Per row the reference draws w1, w2, a coin, r1 and r2 (range_proof.rs:133-159).  Here every (proof, row, field) has a ChaCha20
 // stream of its own — key = the seed, nonce = (index lo, index hi, row << 2 | field) — and sample_below(u) reads WHOLE blocks per
@@ -13,6 +14,7 @@
 // Tasks are numbered field-major, so the lanes of a wavefront nearly always work on one field.
 #pragma once
 #include "chacha_dev.hpp"
+#include "sha256_dev.hpp"
 
 namespace zkp {
 
@@ -275,6 +277,149 @@ __global__ void __launch_bounds__(256) k_nonce_fixup(NonceSampleArgs a) {
     const uint64_t quads = k < 3 ? (uint64_t)a.below_per[k] * a.kw / 4 : (uint64_t)a.raw_per * a.raw_words / 4;      // per proof
     if (present && quads && gid < a.batch * quads && a.status[gid / quads]) ((uint4*)out)[gid] = z;
   }
+}
+
+// ---- the verifier's commitment of the interactive RangeProof (include/zkp_hip.h: zkp_range_verifier_commit_seeded_batch and its two
+// neighbours; tests/seeded_commit_model.py) ----
+// RangeProof::verifier_commit (range_proof.rs:118-126) sends com = Enc(ek_v, from(SHA256(e)), r); verify_commit (:195-208) recomputes it.
+// This kernel makes the two operands of that ONE Enc per session; the Enc itself is the existing launch.  G lanes per session:
+//   seeded (key != null): r = sample_below(n) on stream (kind 7, slot 0, field 0) — the attempt loop is k_nonce_sample's —, e = the first
+//     e_len bytes of block 0 of field 1; e_in / e_len_in are not read;
+//   given  (key == null): e = the caller's e_in[b][0 .. e_len_in[b]); r is the caller's and is not touched.
+//   m (nullable) = the 32 digest bytes of SHA256(e) read big-endian, as kw little-endian limbs: one block, since e_len <= 32.
+// A session whose key is outside the domain (even — zero included —, or of at most 256 bits: m < 2^256 must be a canonical plaintext), whose
+// e_len_in is above 32 or whose 128 attempts were all rejected is MALFORMED: r and e are zero; m is zero too, except after 128 rejections
+// (the key is good there: m is the hash of the zero bytes).
+struct RangeCommitArgs {
+  const uint32_t* key;        // the seed as 8 little-endian words (device memory), or null: e is given
+  const uint32_t* n; uint64_t n_stride;
+  const uint8_t* e_in;        // [B][32] left aligned   (given)
+  const uint8_t* e_len_in;    // [B]                    (given)
+  uint32_t* r;                // [B][kw], 16-byte aligned   (seeded)
+  uint32_t* m;                // [B][kw], 16-byte aligned; nullable
+  uint8_t* e_out;             // [B][32]: e left aligned, zero behind it; nullable   (seeded)
+  uint8_t* status;            // [B] 0 | ZKP_VERDICT_MALFORMED
+  uint64_t first_index, batch;
+  uint32_t kw, e_len, kind, max_attempts;
+};
+
+template <int G>
+__global__ void __launch_bounds__(256) k_range_commit(RangeCommitArgs a) {
+  static_assert(G == 2 || G == 4 || G == 8, "kw = 32, 64 or 128 words");
+  constexpr uint64_t GM = (1ull << G) - 1;
+  const uint64_t gid = blockIdx.x * 256ull + threadIdx.x, b = gid / G;
+  const uint32_t l = (uint32_t)(gid % G);
+  if (b >= a.batch) return;                                      // (whole groups leave together: 256 and 64 are multiples of G)
+  const bool seeded = a.key != nullptr;
+  const uint32_t* u = a.n + b * a.n_stride;
+  uint32_t bits = 0;                                             // every lane of the group reads the same words
+  for (int i = (int)a.kw - 1; i >= 0 && !bits; i--) {
+    const uint32_t nv = u[i];
+    if (nv) bits = 32u * (uint32_t)i + 32u - (uint32_t)__clz((int)nv);
+  }
+  const bool key_ok = bits > 256u && (u[0] & 1u) != 0;
+  const uint32_t elen = seeded ? a.e_len : a.e_len_in[b];
+  const uint32_t g0 = (threadIdx.x & 63u) - l;                   // the group's first bit in a ballot
+  const uint64_t index = a.first_index + b;
+  const uint32_t n0 = (uint32_t)index, n1 = (uint32_t)(index >> 32);
+  uint32_t key[8], v[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) v[i] = 0u;
+  bool ok = key_ok && elen <= 32u;
+  if (seeded) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) key[i] = a.key[i];
+    bool active = ok;
+    ok = false;
+    if (active) {                                                // (a group is in or out as a whole)
+      const uint32_t nw = (bits + 31) / 32, nb = (nw + 15) / 16;
+      const uint32_t topmask = (bits & 31u) ? (1u << (bits & 31u)) - 1u : 0xffffffffu;
+      const uint32_t n2 = nonce_word15(a.kind, 0u, 0u);
+      uint32_t uw[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) { const uint32_t wi = 16 * l + i; uw[i] = wi < nw ? u[wi] : 0u; }
+      for (uint32_t t = 0; t < a.max_attempts; t++) {
+        int c = 0;
+        if (active) {
+          if (l < nb) {
+            chacha20_block(key, t * nb + l, n0, n1, n2, v);
+#pragma unroll
+            for (int i = 0; i < 16; i++) { const uint32_t wi = 16 * l + i; if (wi >= nw) v[i] = 0u; else if (wi == nw - 1) v[i] &= topmask; }
+          }
+#pragma unroll
+          for (int i = 15; i >= 0; i--) if (c == 0 && v[i] != uw[i]) c = v[i] < uw[i] ? -1 : 1;
+        }
+        const uint64_t ne = __ballot(active && c != 0), lt = __ballot(active && c < 0);
+        if (active) {
+          const uint32_t mm = (uint32_t)((ne >> g0) & GM);
+          if (mm) ok = ((lt >> (g0 + (31u - (uint32_t)__clz((int)mm)))) & 1ull) != 0;     // the most significant lane that differs decides
+          if (ok) active = false;
+        }
+        if (__ballot(active) == 0) break;
+      }
+    }
+    uint4* o = (uint4*)(a.r + b * a.kw + 16 * l);
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[i] = ok ? make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  uint4* om = a.m ? (uint4*)(a.m + b * a.kw + 16 * l) : nullptr;
+  if (l != 0) {                                                  // m < 2^256: the words of lane 0
+    if (om) for (int i = 0; i < 4; i++) om[i] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  a.status[b] = ok ? 0 : 2;
+  // e as 8 little-endian words (byte k = bits 8 (k % 4) .. of word k / 4), zero from byte elen on
+  uint32_t e[9];
+#pragma unroll
+  for (int j = 0; j < 9; j++) e[j] = 0u;
+  if (ok && seeded) {
+    uint32_t ks[16];
+    chacha20_block(key, 0u, n0, n1, nonce_word15(a.kind, 0u, 1u), ks);
+#pragma unroll
+    for (int j = 0; j < 8; j++) e[j] = ks[j];
+  } else if (ok) {
+    const uint8_t* src = a.e_in + b * 32;
+#pragma unroll
+    for (int j = 0; j < 8; j++) e[j] = (uint32_t)src[4 * j] | ((uint32_t)src[4 * j + 1] << 8) | ((uint32_t)src[4 * j + 2] << 16) | ((uint32_t)src[4 * j + 3] << 24);
+  }
+  const uint32_t len = elen <= 32u ? elen : 0u;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const uint32_t have = len > 4u * j ? len - 4u * j : 0u;      // bytes of word j that belong to e
+    if (have < 4u) e[j] &= (1u << (8u * have)) - 1u;
+  }
+  if (a.e_out) {
+    uint8_t* dst = a.e_out + b * 32;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { dst[4 * j] = (uint8_t)e[j]; dst[4 * j + 1] = (uint8_t)(e[j] >> 8); dst[4 * j + 2] = (uint8_t)(e[j] >> 16); dst[4 * j + 3] = (uint8_t)(e[j] >> 24); }
+  }
+  if (!om) return;
+  uint32_t h[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) h[i] = 0u;
+  if (key_ok && elen <= 32u) {                                   // one padded block: e, 80, zeros, the bit count
+#pragma unroll
+    for (int j = 0; j < 9; j++) if (len / 4u == (uint32_t)j) e[j] |= 0x80u << (8u * (len & 3u));
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = j < 9 ? __builtin_bswap32(e[j]) : 0u;
+    w[15] = 8u * len;
+    Sha256 sh;
+    sh.init(nullptr, 0);
+    sh.compress_words(w);
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] = sh.h[i];
+  }
+  om[0] = make_uint4(h[7], h[6], h[5], h[4]);
+  om[1] = make_uint4(h[3], h[2], h[1], h[0]);
+  om[2] = make_uint4(0u, 0u, 0u, 0u);
+  om[3] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// verdict[b] = MALFORMED where the session was (zkp_range_verify_commit_batch: the Enc launch wrote 0 / 1 for every session)
+__global__ void __launch_bounds__(256) k_range_commit_verdict(uint8_t* verdict, const uint8_t* status, uint64_t count) {
+  const uint64_t b = blockIdx.x * 256ull + threadIdx.x;
+  if (b < count && status[b]) verdict[b] = 2;
 }
 
 // non-zero words of a device region (zkp_diag_witness_residue)

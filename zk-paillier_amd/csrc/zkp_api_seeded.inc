@@ -296,3 +296,98 @@ extern "C" int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits,
   const int32_t fin = s.finish();
   return st ? st : fin;
 } ZKP_CATCH(c)
+
+// ---- the verifier's commitment of the interactive RangeProof: RangeProof::verifier_commit from a seed, the (r, e) it committed to for the
+// decommit message, and RangeProof::verify_commit (range_proof.rs:118-126, 195-208).  k_range_commit makes the two operands of the one Enc
+// of every session, and the Enc runs as the device-pointer call it already is: zkp_paillier_enc_batch (store) or
+// zkp_paillier_enc_check_batch (compare with `expected`), with their routing, key cache and kernels.
+static int32_t range_commit_launch(zkp_ctx* c, uint32_t n_bits, const RangeCommitArgs& a) {
+  const dim3 grid((unsigned)((a.batch * (n_bits / 512) + 255) / 256));
+  switch (n_bits / 512) {
+    case 2: hipLaunchKernelGGL(k_range_commit<2>, grid, dim3(256), 0, c->stream, a); break;
+    case 4: hipLaunchKernelGGL(k_range_commit<4>, grid, dim3(256), 0, c->stream, a); break;
+    default: hipLaunchKernelGGL(k_range_commit<8>, grid, dim3(256), 0, c->stream, a); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+
+// commit (out_com) or reveal (out_r, out_e): the same stream, so the same (r, e).  `s` wipes the seed and every copy of r, e and m on every
+// path out; in the commit call none of them is ever outside the blocks it wipes.
+static int32_t range_commit_seeded(zkp_ctx* c, const char* name, bool reveal, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride,
+                                   uint32_t e_len, const uint8_t* seed, uint64_t first_index, uint32_t* out_com, uint32_t* out_r, uint8_t* out_e,
+                                   uint8_t* out_status, uint32_t flags) {
+  if (!c) return ZKP_EINVAL;
+  if (!sigma_args_ok(n_bits, batch, n_stride) || !n || !seed || e_len < 1 || e_len > 32 || (batch && (reveal ? !out_r || !out_e : !out_com))) {
+    c->err = std::string(name) + ": invalid argument"; return ZKP_EINVAL;
+  }
+  if (reveal && (flags & ZKP_F_DEVICE_PTRS) && ((uintptr_t)out_r & 15u)) { c->err = std::string(name) + ": device output arrays must be 16-byte aligned"; return ZKP_EINVAL; }
+  if (batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = n_bits / 32;
+  Stage s(c, flags);
+  RangeCommitArgs a{};
+  a.n = s.in(n, n_stride ? batch * kw : kw); a.n_stride = n_stride;
+  a.key = (const uint32_t*)s.host_in(seed, 32);
+  s.secret(a.key, 32);
+  uint32_t* dcom = nullptr;
+  if (reveal) {
+    a.r = s.out(out_r, batch * kw); a.e_out = s.out(out_e, batch * 32);
+    if (!s.dev) { s.secret(a.r, batch * kw * 4); s.secret(a.e_out, batch * 32); }      // (host arrays: the staged copies are wiped behind the D2H)
+  } else {
+    dcom = s.out(out_com, batch * 2 * kw);
+    a.r = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4); s.secret(a.r, batch * kw * 4);
+    a.m = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4); s.secret(a.m, batch * kw * 4);
+  }
+  a.status = s.out(out_status, batch);
+  a.first_index = first_index; a.batch = batch; a.kw = (uint32_t)kw; a.e_len = e_len; a.kind = ZKP_SEEDED_KIND_RANGE_COMMIT; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
+  int32_t st = s.st;
+  if (!st && !a.status) { st = ensure(c, c->scratch[S_SAMPLE_STATUS], batch); a.status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p; }
+  if (!st) st = range_commit_launch(c, n_bits, a);
+  if (!st && !reveal) st = zkp_paillier_enc_batch(c, n_bits, batch, a.n, n_stride, a.m, a.r, dcom, ZKP_F_DEVICE_PTRS);
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+}
+
+extern "C" int32_t zkp_range_verifier_commit_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, uint32_t e_len,
+                                                          const uint8_t* seed, uint64_t first_index, uint32_t* out_com, uint8_t* out_status,
+                                                          uint32_t flags) try {
+  return range_commit_seeded(c, "zkp_range_verifier_commit_seeded_batch", false, n_bits, batch, n, n_stride, e_len, seed, first_index, out_com, nullptr, nullptr,
+                             out_status, flags);
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_range_verifier_reveal_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, uint32_t e_len,
+                                                          const uint8_t* seed, uint64_t first_index, uint32_t* out_r, uint8_t* out_e, uint8_t* out_status,
+                                                          uint32_t flags) try {
+  return range_commit_seeded(c, "zkp_range_verifier_reveal_seeded_batch", true, n_bits, batch, n, n_stride, e_len, seed, first_index, nullptr, out_r, out_e,
+                             out_status, flags);
+} ZKP_CATCH(c)
+
+extern "C" int32_t zkp_range_verify_commit_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* com,
+                                                 const uint32_t* r, const uint8_t* e, const uint8_t* e_len, uint8_t* out_verdict, uint32_t flags) try {
+  if (!c) return ZKP_EINVAL;
+  if (!sigma_args_ok(n_bits, batch, n_stride) || !n || (batch && (!com || !r || !e || !e_len || !out_verdict))) { c->err = "zkp_range_verify_commit_batch: invalid argument"; return ZKP_EINVAL; }
+  if (batch == 0) return ZKP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t kw = n_bits / 32;
+  Stage s(c, flags);
+  RangeCommitArgs a{};
+  a.n = s.in(n, n_stride ? batch * kw : kw); a.n_stride = n_stride;
+  const uint32_t* dcom = s.in(com, batch * 2 * kw);
+  const uint32_t* dr = s.in(r, batch * kw);
+  a.e_in = s.in(e, batch * 32); a.e_len_in = s.in(e_len, batch);
+  uint8_t* dv = s.out(out_verdict, batch);
+  a.m = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4);      // (r and e are public by now: nothing to wipe)
+  a.batch = batch; a.kw = (uint32_t)kw;
+  int32_t st = s.st;
+  if (!st) st = ensure(c, c->scratch[S_SAMPLE_STATUS], batch);
+  a.status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p;
+  if (!st) st = range_commit_launch(c, n_bits, a);
+  if (!st) st = zkp_paillier_enc_check_batch(c, n_bits, batch, a.n, n_stride, a.m, dr, nullptr, nullptr, dcom, dv, ZKP_F_DEVICE_PTRS);
+  if (!st) {
+    hipLaunchKernelGGL(k_range_commit_verdict, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, dv, (const uint8_t*)a.status, batch);
+    if (hipGetLastError() != hipSuccess) { c->err = "k_range_commit_verdict launch"; st = ZKP_EDEVICE; }
+  }
+  const int32_t fin = s.finish();
+  return st ? st : fin;
+} ZKP_CATCH(c)

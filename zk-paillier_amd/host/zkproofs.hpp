@@ -704,6 +704,105 @@ struct RangeProof {
     parallel_for(B, [&](size_t b) { s.read_proof(b, out[b]); });
     return out;
   }
+  // ---- the verifier's commitment to its challenge for whole batches of sessions, one GPU call per step.  The verifier keeps a VerifierSeed
+  // between its messages instead of (r, e) per session: the commit call expands (seed, first_index + b) ON THE GPU into r and e, hashes e and
+  // encrypts, and nothing but com leaves the device; the reveal call regenerates the same (r, e) for the decommit message and for
+  // verifier_output.  A (seed, index) belongs to ONE session; reveal only after the prover's encrypted pairs have arrived.
+  // keys: one key for all `sessions` sessions, or one key per session (sessions = 0: keys.size()), all of one kernel width.  A key of this
+  // step is an odd integer of 257 .. 4096 bits (the digest must be a canonical plaintext): anything else is std::invalid_argument.
+  struct VerifierSeed {
+    uint8_t bytes[32];
+    VerifierSeed() { std::memset(bytes, 0, sizeof bytes); }
+    static VerifierSeed fresh() { VerifierSeed s; detail::ChaChaRng::os_random(s.bytes, sizeof s.bytes); return s; }
+    ~VerifierSeed() { detail::ChaChaRng::wipe(bytes, sizeof bytes); }
+  };
+  // :118-126 for B sessions: the commitments only
+  static std::vector<Commitment> verifier_commit_batch_seeded(const std::vector<EncryptionKey>& keys, const VerifierSeed& seed, uint64_t first_index = 0,
+                                                              size_t sessions = 0, size_t e_len = STATISTICAL_ERROR_FACTOR / 8) {
+    Engine& e = Engine::instance();
+    const CommitKeys k = commit_keys(keys, sessions, "RangeProof::verifier_commit_batch_seeded");
+    std::vector<Commitment> out(k.B);
+    if (k.B == 0) return out;
+    std::vector<uint32_t> com(k.B * 2 * k.kw);
+    std::vector<uint8_t> status(k.B, 0);
+    e.check(zkp_range_verifier_commit_seeded_batch(e.ctx(), k.nb, k.B, k.n.data(), k.stride, (uint32_t)e_len, seed.bytes, first_index, com.data(), status.data(), 0),
+            "zkp_range_verifier_commit_seeded_batch");
+    statuses_ok(status, "RangeProof::verifier_commit: no r below n in 128 attempts");
+    for (size_t b = 0; b < k.B; b++) out[b].com = BigInt::from_limbs(&com[b * 2 * k.kw], 2 * k.kw);
+    return out;
+  }
+  // the (r, e) of those commitments, from the same (keys, seed, first_index, sessions, e_len)
+  static std::vector<std::pair<ChallengeRandomness, ChallengeBits>> verifier_reveal_batch_seeded(const std::vector<EncryptionKey>& keys, const VerifierSeed& seed,
+                                                                                                 uint64_t first_index = 0, size_t sessions = 0,
+                                                                                                 size_t e_len = STATISTICAL_ERROR_FACTOR / 8) {
+    Engine& e = Engine::instance();
+    const CommitKeys k = commit_keys(keys, sessions, "RangeProof::verifier_reveal_batch_seeded");
+    std::vector<std::pair<ChallengeRandomness, ChallengeBits>> out(k.B);
+    if (k.B == 0) return out;
+    std::vector<uint32_t> r(k.B * k.kw);
+    std::vector<uint8_t> eb(k.B * 32), status(k.B, 0);
+    const int32_t st = zkp_range_verifier_reveal_seeded_batch(e.ctx(), k.nb, k.B, k.n.data(), k.stride, (uint32_t)e_len, seed.bytes, first_index, r.data(), eb.data(),
+                                                              status.data(), 0);
+    if (st == ZKP_OK)
+      for (size_t b = 0; b < k.B; b++) {
+        out[b].first.r = BigInt::from_limbs(&r[b * k.kw], k.kw);
+        out[b].second.bytes.assign(&eb[b * 32], &eb[b * 32] + e_len);
+      }
+    detail::ChaChaRng::wipe(r.data(), r.size() * 4);
+    detail::ChaChaRng::wipe(eb.data(), eb.size());
+    e.check(st, "zkp_range_verifier_reveal_seeded_batch");
+    statuses_ok(status, "RangeProof::verifier_commit: no r below n in 128 attempts");
+    return out;
+  }
+  // :195-208 for B sessions, one Result per session: one zkp_range_verify_commit_batch per kernel width.  A session the fixed layout cannot
+  // carry — a negative or over-wide r or com, an e of more than 32 bytes, a key outside the domain above — goes through verify_commit, the
+  // single-session host path, and is merged in (a key that path cannot carry either is Result::unsupported).
+  static std::vector<Result> verify_commit_batch(const std::vector<EncryptionKey>& keys, const std::vector<Commitment>& coms, const std::vector<ChallengeRandomness>& rs,
+                                                 const std::vector<ChallengeBits>& es) {
+    Engine& e = Engine::instance();
+    const size_t B = coms.size();
+    if (rs.size() != B || es.size() != B || (B && keys.size() != 1 && keys.size() != B))
+      throw std::invalid_argument("RangeProof::verify_commit_batch: one commitment, one r and one e per session, one key or one key per session");
+    std::vector<Result> out(B, Result(false));
+    auto key_of = [&](size_t b) -> const EncryptionKey& { return keys.size() == 1 ? keys[0] : keys[b]; };
+    std::vector<uint8_t> carried(B, 0);
+    for (size_t b = 0; b < B; b++) {
+      const BigInt& n = key_of(b).n;
+      if (commit_key_ok(n)) {
+        const uint32_t kw = width_for(n) / 32;
+        carried[b] = !coms[b].com.is_negative() && coms[b].com.fits_limbs(2 * kw) && !rs[b].r.is_negative() && rs[b].r.fits_limbs(kw) && es[b].bytes.size() <= 32;
+      }
+      if (carried[b]) continue;
+      try { out[b] = verify_commit(key_of(b), coms[b], rs[b], es[b]); }
+      catch (const Panic& p) { out[b] = Result::panicked(p.what()); }
+      catch (const std::exception& x) { out[b] = Result::unsupported(x.what()); }
+    }
+    for (uint32_t nb : {1024u, 2048u, 4096u}) {
+      const uint32_t kw = nb / 32;
+      std::vector<size_t> idx;
+      for (size_t b = 0; b < B; b++) if (carried[b] && width_for(key_of(b).n) == nb) idx.push_back(b);
+      if (idx.empty()) continue;
+      const bool shared = keys.size() == 1;
+      const size_t cnt = idx.size();
+      std::vector<uint32_t> n((shared ? 1 : cnt) * kw), com(cnt * 2 * kw), r(cnt * kw);
+      std::vector<uint8_t> eb(cnt * 32, 0), elen(cnt), v(cnt, 9);
+      if (shared) keys[0].n.to_limbs(n.data(), kw);
+      for (size_t q = 0; q < cnt; q++) {
+        const size_t b = idx[q];
+        if (!shared) keys[b].n.to_limbs(&n[q * kw], kw);
+        coms[b].com.to_limbs(&com[q * 2 * kw], 2 * kw);
+        rs[b].r.to_limbs(&r[q * kw], kw);
+        std::memcpy(&eb[q * 32], es[b].bytes.data(), es[b].bytes.size());
+        elen[q] = (uint8_t)es[b].bytes.size();
+      }
+      e.check(zkp_range_verify_commit_batch(e.ctx(), nb, cnt, n.data(), shared ? 0 : kw, com.data(), r.data(), eb.data(), elen.data(), v.data(), 0),
+              "zkp_range_verify_commit_batch");
+      for (size_t q = 0; q < cnt; q++)
+        out[idx[q]] = v[q] == ZKP_VERDICT_MALFORMED ? Result::panicked("RangeProof::verify_commit: malformed session") : Result(v[q] == ZKP_VERDICT_ACCEPT);
+    }
+    return out;
+  }
+
   // :254-355 for B sessions on the two received documents of each: zkp_range_verifier_output_json_batch tokenises, converts and verifies on the
   // GPU.  A session it hands back (ZKP_DOC_HOST_PATH: valid documents the fixed layout cannot carry), one whose statement the layout cannot
   // carry and one whose challenge has more than 32 bytes are parsed here and go through verifier_output, which handles signed and over-wide
@@ -715,6 +814,25 @@ struct RangeProof {
 
  private:
   static void statuses_ok(const std::vector<uint8_t>& status, const char* what) { for (uint8_t s : status) if (s != 0) throw Panic(what); }
+  // the key domain of the commitment calls (include/zkp_hip.h): odd, more than 256 bits — and no wider than the widest kernel
+  static bool commit_key_ok(const BigInt& n) { return !n.is_negative() && n.is_odd() && n.bit_length() > 256 && n.bit_length() <= 4096; }
+  // the keys of a seeded commitment call as limbs: one key for B sessions (stride 0) or B keys of one width
+  struct CommitKeys { uint32_t nb = 0, kw = 0; size_t B = 0; uint64_t stride = 0; std::vector<uint32_t> n; };
+  static CommitKeys commit_keys(const std::vector<EncryptionKey>& keys, size_t sessions, const char* who) {
+    CommitKeys k;
+    k.B = sessions ? sessions : keys.size();
+    if (k.B == 0) return k;
+    if (keys.size() != 1 && keys.size() != k.B) throw std::invalid_argument(std::string(who) + ": one key, or one key per session");
+    for (const EncryptionKey& ek : keys)
+      if (!commit_key_ok(ek.n)) throw std::invalid_argument(std::string(who) + ": a key of this step is an odd integer of 257 .. 4096 bits");
+    k.nb = width_for(keys[0].n); k.kw = k.nb / 32; k.stride = keys.size() == 1 ? 0 : k.kw;
+    k.n.resize(keys.size() * k.kw);
+    for (size_t i = 0; i < keys.size(); i++) {
+      if (width_for(keys[i].n) != k.nb) throw std::invalid_argument(std::string(who) + ": the keys of one call are of one kernel width (1024, 2048 or 4096 bits)");
+      keys[i].n.to_limbs(&k.n[i * k.kw], k.kw);
+    }
+    return k;
+  }
 };
 
 // ------------------------------------------------------------------ NiCorrectKeyProof
