@@ -33,6 +33,7 @@ pub const ZKP_SEEDED_KIND_CORRECT_MESSAGE: u32 = 3;
 pub const ZKP_SEEDED_KIND_DLOG: u32 = 4;
 pub const ZKP_SEEDED_KIND_VERLIN: u32 = 5;
 pub const ZKP_SEEDED_KIND_MUL: u32 = 6;
+pub const ZKP_SEEDED_KIND_DLOG_SETUP: u32 = 8;
 pub const ZKP_DEC_OK: u8 = 0;
 pub const ZKP_DEC_INVALID: u8 = 1;
 pub const ZKP_DEC_NEGATIVE: u8 = 2;
@@ -179,6 +180,9 @@ extern "C" {
     pub fn zkp_nonce_sample_coprime_batch(ctx: *mut zkp_ctx, proof_kind: u32, n_bits: u32, batch: u64, n: *const u32, n_stride: u64, seed: *const u8, first_index: u64, out_field: *mut *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_verlin_proof_prove_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, n_stride: u64, c: *const u32, c_prime: *const u32, phi_x: *const u32, x: *const u32, x_prime: *const u32, x_double_prime: *const u32, r_x: *const u32, seed: *const u8, first_index: u64, out_phi_a: *mut u32, out_z: *mut u32, out_z_prime: *mut u32, out_z_double_prime: *mut u32, out_r_z: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_mul_proof_prove_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, n: *const u32, n_stride: u64, e_a: *const u32, e_b: *const u32, e_c: *const u32, a: *const u32, b: *const u32, r_a: *const u32, r_b: *const u32, r_c: *const u32, seed: *const u8, first_index: u64, out_f: *mut u32, out_z1: *mut u32, out_z2: *mut u32, out_e_d: *mut u32, out_e_db: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_jacobi_batch(ctx: *mut zkp_ctx, mod_bits: u32, count: u64, a: *const u32, n: *const u32, n_stride: u64, out_symbol: *mut i32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_legendre_batch(ctx: *mut zkp_ctx, mod_bits: u32, count: u64, a: *const u32, p: *const u32, p_stride: u64, out_symbol: *mut i32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_dlog_statement_setup_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, N: *const u32, seed: *const u8, first_index: u64, out_g: *mut u32, out_ni: *mut u32, out_secret: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_decimal_to_limbs_batch(ctx: *mut zkp_ctx, text: *const c_char, text_len: u64, items: *const zkp_dec_item, count: u64, dst: *mut u32, dst_words: u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_decimal_pitch(words: u32) -> u32;
     pub fn zkp_limbs_to_decimal_batch(ctx: *mut zkp_ctx, src: *const u32, src_stride: u64, words: u32, count: u64, out_text: *mut c_char, pitch: u32, out_len: *mut u32, flags: u32) -> i32;

@@ -511,6 +511,52 @@ int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t
                                          uint64_t first_index, uint32_t* out_f, uint32_t* out_z1, uint32_t* out_z2, uint32_t* out_e_d,
                                          uint32_t* out_e_db, uint8_t* out_status, uint32_t flags);
 
+/* ------------------------------------------------------------------ Jacobi symbol, legendre_symbol, DLogStatement set-up
+ * zkp_jacobi_batch: out_symbol[i] = (a[i] / n[i]), the Jacobi symbol, -1 | 0 | 1 (an int32_t: the i32 the reference's legendre_symbol returns), for odd n.  It needs neither the factors of n nor an
+ * exponentiation: a binary-GCD-shaped loop, one pair per lane (csrc/kernels_jacobi.hpp states why every step is exact).
+ * mod_bits in {1024, 2048, 4096, 8192}; a, n: mod_bits/32 words per element; n_stride = 0 (one n for the call) or mod_bits/32.  a is any
+ * value: zero and a >= n are in the domain.  n == 1 gives 1.  out_status[i] (nullable): 0, or 2 where n is even or zero (outside the
+ * domain, as zkp_modinv_batch reports its own; the symbol is 0).
+ *
+ * zkp_legendre_batch: the reference's `pub fn legendre_symbol(a, p)` (wi_dlog_proof.rs:94-107), word for word:
+ * ls = a^((p - 1) * 2^-1 mod p) mod p; out_symbol[i] = 1 if ls == 1, else -1.  It is Euler's criterion and not the Jacobi symbol:
+ * a == 0 mod p and a composite p give -1 as they do there.  mod_bits in {2048, 4096, 8192} (what zkp_modexp_batch takes: a 1024-bit
+ * prime travels zero-padded in a 2048-bit row); p_stride = 0 or mod_bits/32.  out_status[i] (nullable): 0, or ZKP_VERDICT_MALFORMED (2)
+ * where the reference panics (p even: `mod_inv(2, p).unwrap()`), and 2 also for p < 3 and a >= p (OUR domain rule, that of
+ * zkp_modinv_batch); the symbol of such an item is 0. */
+int32_t zkp_jacobi_batch(zkp_ctx* ctx, uint32_t mod_bits, uint64_t count, const uint32_t* a, const uint32_t* n, uint64_t n_stride,
+                         int32_t* out_symbol, uint8_t* out_status, uint32_t flags);
+int32_t zkp_legendre_batch(zkp_ctx* ctx, uint32_t mod_bits, uint64_t count, const uint32_t* a, const uint32_t* p, uint64_t p_stride,
+                           int32_t* out_symbol, uint8_t* out_status, uint32_t flags);
+
+/* The set-up of a DLogStatement "per definition 3 in the paper", as the reference's own tests do it before CompositeDLogProof::prove
+ * (wi_dlog_proof.rs:117-141): h1 drawn until its symbol is -1, secret < 2^256, h2 = (h1^-1)^secret mod N — the ring-Pedersen parameters
+ * N~, h1, h2 of the threshold-ECDSA protocols.  From a 32-byte seed, by the construction of the nonce streams above, unchanged, with one
+ * more kind:
+ *     kind                 slot                   field  value      draw
+ *     8 DLogSetup          0                      0      h1         sample_jacobi_minus_below(N)
+ *     8 DLogSetup          0                      1      secret     words 0 .. 7 of block 0: uniform on [0, 2^256), as sample_below(2^256) is
+ * sample_jacobi_minus_below(N): attempts t = 0, 1, ... produce exactly the candidates of sample_below(N) — the same blocks, the same
+ * top-limb mask; candidate v is accepted when v + 1 < N (the reference's sample_range(1, N - 1) draws below N - 1; v = 0 and v = 1 fall to
+ * the symbol test) AND the Jacobi symbol (v / N) == -1; at most 128 attempts, rejections of both sorts share the one counter t.
+ * Where this is STRICTER than the reference: it tests legendre(h1, p) * legendre(h1, q) with its legendre_symbol, which is -1 for
+ * h1 == 0 mod p, so it can accept an h1 that shares a factor with N — and then panics in mod_inv.  The Jacobi symbol is 0 there and the
+ * candidate is redrawn: every h1 made here is invertible.  p and q are not needed.
+ * out_g = h1, out_ni = h2 [B][kw], out_secret [B][8], kw = n_bits/32; n_bits is what zkp_dlog_prove_batch accepts.  N zero, N even and 128
+ * rejections in a row (CERTAIN for a square N, whose symbols are all 0 or 1) make that statement ZKP_VERDICT_MALFORMED in out_status
+ * [B] (nullable): its g, ni and secret are zero; the other statements are unaffected.  Chunked calls with first_index + lo equal one call.
+ * The staged seed, the device copies of secret and h1^-1 and the staged out_secret of a host-pointer call are zeroed on the device before
+ * the call's blocks are given back, on error returns too.
+ * SECURITY CONTRACT, extended.  The seed is worth the secret: whoever learns it computes the discrete logarithm this statement exists to
+ * hide.  One (seed, index) pair serves ONE statement.  `seed` is always a HOST pointer, fresh from the operating system, wiped by the
+ * caller afterwards.  A seed used here must not also be handed to zkp_dlog_prove_seeded_batch: the streams of kind 8 and kind 4 are
+ * disjoint by construction (state word 15), but one seed for the secret and for the nonce that masks it makes either leak fatal to
+ * both. */
+#define ZKP_SEEDED_KIND_DLOG_SETUP 8u
+int32_t zkp_dlog_statement_setup_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* N, const uint8_t* seed,
+                                              uint64_t first_index, uint32_t* out_g, uint32_t* out_ni, uint32_t* out_secret,
+                                              uint8_t* out_status, uint32_t flags);
+
 /* ------------------------------------------------------------------ wire format
  * The reference serialises big integers as DECIMAL strings (src/serialize.rs:1-31 `bigint`, :33-78 `vecbigint`:
  * BigInt::to_str_radix(10) / from_str_radix(s, 10) = GMP mpz_get_str / mpz_set_str).  The two L1 entry points below

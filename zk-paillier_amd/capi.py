@@ -177,6 +177,10 @@ EXPORTS = {
                                             [C.c_void_p] * 6 + [C.c_uint32]),
     "zkp_mul_proof_prove_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 8 + [C.c_char_p, C.c_uint64] +
                                          [C.c_void_p] * 6 + [C.c_uint32]),
+    "zkp_jacobi_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_legendre_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_dlog_statement_setup_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_verlin_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_verlin_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
     "zkp_multi_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -203,6 +207,7 @@ Z1_EXTRA_LIMBS = 16
 SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KIND_DLOG = 1, 2, 3, 4
 SEEDED_KIND_VERLIN, SEEDED_KIND_MUL = 5, 6
 SEEDED_KIND_RANGE_COMMIT = 7
+SEEDED_KIND_DLOG_SETUP = 8
 _lib = None
 
 
@@ -604,6 +609,22 @@ class Context:
     def dlog_prove_seeded(self, n_bits, y_bits, batch, N, g, ni, secret, seed: bytes, first_index: int, out_x, out_y, out_status=None):
         self.check(self.lib.zkp_dlog_prove_seeded_batch(self.h, n_bits, y_bits, batch, ptr(N), ptr(g), ptr(ni), ptr(secret), _seed(seed), first_index,
                                                         ptr(out_x), ptr(out_y), ptr(out_status), self._flags(N, g, ni, secret, out_x, out_y, out_status)))
+
+    # ---- the Jacobi symbol, the reference's legendre_symbol, and the seeded set-up of a DLogStatement (h1 of symbol -1, secret, h2)
+    def jacobi(self, mod_bits, count, a, n, n_stride, out_symbol, out_status=None):
+        """zkp_jacobi_batch: out_symbol (int32) = (a / n) for odd n; out_status 2 where n is even or zero"""
+        self.check(self.lib.zkp_jacobi_batch(self.h, mod_bits, count, ptr(a), ptr(n), n_stride, ptr(out_symbol), ptr(out_status),
+                                             self._flags(a, n, out_symbol, out_status)))
+
+    def legendre(self, mod_bits, count, a, p, p_stride, out_symbol, out_status=None):
+        """zkp_legendre_batch: the reference's legendre_symbol (Euler's criterion: 1 iff a^((p-1)/2) == 1 mod p, else -1)"""
+        self.check(self.lib.zkp_legendre_batch(self.h, mod_bits, count, ptr(a), ptr(p), p_stride, ptr(out_symbol), ptr(out_status),
+                                               self._flags(a, p, out_symbol, out_status)))
+
+    def dlog_statement_setup_seeded(self, n_bits, batch, N, seed: bytes, first_index: int, out_g, out_ni, out_secret, out_status=None):
+        """zkp_dlog_statement_setup_seeded_batch: g = h1 with (h1 / N) == -1, secret < 2^256, ni = (h1^-1)^secret mod N"""
+        self.check(self.lib.zkp_dlog_statement_setup_seeded_batch(self.h, n_bits, batch, ptr(N), _seed(seed), first_index, ptr(out_g), ptr(out_ni),
+                                                                  ptr(out_secret), ptr(out_status), self._flags(N, out_g, out_ni, out_secret, out_status)))
 
     # ---- seeded proving of VerlinProof and MulProof: r_a / r_d are redrawn on the GPU until they are coprime to n
     def nonce_sample_coprime(self, kind, n_bits, batch, n, n_stride, seed: bytes, first_index: int, out_fields, out_status):

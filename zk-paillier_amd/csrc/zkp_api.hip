@@ -26,6 +26,7 @@
 #include "kernels_serde_scan.hpp"
 #include "kernels_sample.hpp"
 #include "kernels_coprime.hpp"
+#include "kernels_jacobi.hpp"
 #include "route_plan.hpp"             // every size-based decision of this file and of zkp_api_proofs.inc
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
@@ -1369,6 +1370,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 #include "zkp_api_proofs.inc"
 #include "zkp_api_mul.inc"
 #include "zkp_api_seeded.inc"
+#include "zkp_api_jacobi.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE
 #include "zkp_api_multi.inc"

@@ -7,13 +7,16 @@
 //   RangeWitness    its secret counterpart (zkp_range_ni_witness)
 //   range_layout_carries   "the fixed-width layout at (kw, EF) carries this proof": every value non-negative and within its width
 //   Columns         B rows of a few fixed-width fields, one array per field (the sigma proofs, CompositeDLogProof)
+//   DLogSetupBatch  the moduli of DLogStatement::generate_batch_seeded in, (g, ni, secret, status) out
 //
 // All of it is RawBuf staging (host/staging.hpp): NOT zero-initialised, pooled and huge-page backed when large.  So every writer here
 // writes every word of the row it is given — a Mask response zero-fills w2 / r2 and an Open one stores j = 0 —, and whatever is read is
 // something a writer or the GPU call wrote.
 #pragma once
+#include <algorithm>
 #include <initializer_list>
 #include <memory>
+#include <stdexcept>
 #include <vector>
 
 #include "../../include/zkp_hip.h"
@@ -169,6 +172,35 @@ class Columns {
  private:
   std::vector<Column> cols_;
   std::vector<std::unique_ptr<RawBuf<uint32_t>>> buf_;
+};
+
+// The batch of zkp_dlog_statement_setup_seeded_batch: the moduli N in; g = h1, ni = h2, the secrets (a secret column, wiped on release) and
+// one status byte per statement out.  The moduli of one batch share a kernel width (1024, 2048 or 4096 bits: the narrowest that takes the
+// widest of them); a negative modulus or one wider than 4096 bits has no row in this layout and is refused before anything is flattened.
+struct DLogSetupBatch {
+  static uint32_t width(const std::vector<BigInt>& N) {
+    size_t bits = 0;
+    for (const BigInt& n : N) {
+      if (n.is_negative()) throw std::invalid_argument("DLogStatement::generate_batch_seeded: a negative modulus");
+      bits = std::max(bits, n.bit_length());
+    }
+    if (bits > 4096) throw std::invalid_argument("DLogStatement::generate_batch_seeded: a modulus wider than 4096 bits");
+    return bits <= 1024 ? 1024 : bits <= 2048 ? 2048 : 4096;
+  }
+  const size_t B;
+  const uint32_t n_bits, kw;
+  Columns in, out;
+  std::vector<uint8_t> status;
+  explicit DLogSetupBatch(const std::vector<BigInt>& N)
+      : B(N.size()), n_bits(width(N)), kw(n_bits / 32), in(B, {{kw, false}}), out(B, {{kw, false}, {kw, false}, {8, true}}), status(B, 9) {
+    for (size_t b = 0; b < B; b++) in.put(b, 0, N[b]);
+  }
+  uint32_t* N() { return in[0]; }
+  uint32_t* g() { return out[0]; }
+  uint32_t* ni() { return out[1]; }
+  uint32_t* secret() { return out[2]; }
+  // the first statement without a value (N zero or even, or no h1 of symbol -1 in 128 attempts: a square), B if every one has its own
+  size_t first_failed() const { size_t b = 0; while (b < B && status[b] == 0) b++; return b; }
 };
 
 }  // namespace zkproofs

@@ -10,8 +10,9 @@
 //     src/zkproofs/range_proof_ni.rs:36-128
 //   zkproofs::NiCorrectKeyProof::{proof,verify}                     NiCorrectKeyProof::{proof,verify}
 //     src/zkproofs/correct_key_ni.rs:36-100
-//   zkproofs::{CompositeDLogProof,DLogStatement}::{prove,verify}    same
+//   zkproofs::{CompositeDLogProof,DLogStatement}::{prove,verify}    same (+ DLogStatement::generate_batch_seeded)
 //     src/zkproofs/wi_dlog_proof.rs:33-91
+//   zkproofs::wi_dlog_proof::legendre_symbol (:94-107)              wi_dlog_proof::legendre_symbol, wi_dlog_proof::jacobi_symbol
 //   zkproofs::{CorrectKey,Challenge,VerificationAid,CorrectKeyProof} same (interactive, correct_key.rs:28-183)
 //   zkproofs::{VerlinProof,VerlinStatement,VerlinWitness}, gen_phi   same (verlin_proof.rs:35-165)
 //   zkproofs::{ZeroProof,ZeroStatement,ZeroWitness}                 same (zero_enc_proof.rs:26-95)
@@ -1018,7 +1019,15 @@ inline void seeded_status_ok(const std::vector<uint8_t>& status, const char* wha
 }  // namespace detail
 
 // ------------------------------------------------------------------ CompositeDLogProof
-struct DLogStatement { BigInt N, g, ni; };   // wi_dlog_proof.rs:38-43
+struct DLogStatement {                        // wi_dlog_proof.rs:38-43
+  BigInt N, g, ni;
+  // What the reference's tests do before CompositeDLogProof::prove (wi_dlog_proof.rs:117-141, "per definition 3 in the paper"), for a whole
+  // batch of moduli and without their factors: g = h1 with Jacobi symbol (h1 / N) == -1, secret < 2^256, ni = (h1^-1)^secret mod N — from
+  // one fresh OS seed expanded ON THE GPU (zkp_dlog_statement_setup_seeded_batch; the seed is worth the secrets and is wiped on every path
+  // out, the secrets travel in a column that is wiped on release).  -> (statements, secrets), one each per modulus.
+  // Panic where a modulus has no such h1: N zero or even, or a square (the reference's loop would not end).
+  static std::pair<std::vector<DLogStatement>, std::vector<BigInt>> generate_batch_seeded(const std::vector<BigInt>& N);
+};
 
 class CompositeDLogProof {
  public:
@@ -1496,6 +1505,58 @@ inline std::vector<CompositeDLogProof> CompositeDLogProof::prove_batch_seeded(co
   if (st.size() != secrets.size()) throw std::invalid_argument("CompositeDLogProof::prove_batch_seeded: one secret per statement");
   return prove_impl(st.data(), secrets.data(), st.size(), true);
 }
+
+// ---- DLogStatement::generate_batch_seeded, legendre_symbol, jacobi_symbol
+inline std::pair<std::vector<DLogStatement>, std::vector<BigInt>> DLogStatement::generate_batch_seeded(const std::vector<BigInt>& N) {
+  std::pair<std::vector<DLogStatement>, std::vector<BigInt>> r;
+  if (N.empty()) return r;
+  DLogSetupBatch q(N);                  // (refuses what the layout cannot carry before the engine or a seed exists)
+  Engine& e = Engine::instance();
+  RangeProofNi::SeedGuard seed(true);
+  e.check(zkp_dlog_statement_setup_seeded_batch(e.ctx(), q.n_bits, q.B, q.N(), seed.bytes, 0, q.g(), q.ni(), q.secret(), q.status.data(), 0),
+          "zkp_dlog_statement_setup_seeded_batch");
+  if (q.first_failed() != q.B) throw Panic("DLogStatement::generate_batch_seeded: no h1 with Jacobi symbol -1 (N zero, even or a square), statement " + std::to_string(q.first_failed()));
+  for (size_t b = 0; b < q.B; b++) {
+    r.first.push_back(DLogStatement{N[b], q.out.get(b, 0), q.out.get(b, 1)});
+    r.second.push_back(q.out.get(b, 2));
+  }
+  return r;
+}
+
+// The reference's `zkproofs::wi_dlog_proof::legendre_symbol` (wi_dlog_proof.rs:94-107) under its module's name — a namespace of its own, so
+// that programs which define a helper of that name next to `using namespace zkproofs` keep compiling — and the Jacobi symbol beside it.
+namespace wi_dlog_proof {
+// 1 if a^((p - 1) / 2) == 1 mod p, else -1: Euler's criterion, also for a == 0 mod p and for a composite p (both -1), as in the reference.
+// Panic where it panics (`mod_inv(2, p).unwrap()` for an even p); std::domain_error for p < 3 or wider than 8192 bits.
+inline int legendre_symbol(const BigInt& a, const BigInt& p) {
+  if (p.is_negative() || p < BigInt(3) || p.bit_length() > 8192) throw std::domain_error("legendre_symbol: p < 3 or wider than 8192 bits");
+  if (!p.is_odd()) throw Panic("called `Option::unwrap()` on a `None` value (mod_inv(2, p), wi_dlog_proof.rs:98)");
+  Engine& e = Engine::instance();
+  const uint32_t mb = p.bit_length() <= 2048 ? 2048 : p.bit_length() <= 4096 ? 4096 : 8192, L = mb / 32;
+  std::vector<uint32_t> av(L), pv(L);
+  a.modulus(p).to_limbs(av.data(), L);         // (mod_pow reduces its base, as mpz_powm does)
+  p.to_limbs(pv.data(), L);
+  int32_t sym = 0;
+  uint8_t st = 9;
+  e.check(zkp_legendre_batch(e.ctx(), mb, 1, av.data(), pv.data(), 0, &sym, &st, 0), "zkp_legendre_batch");
+  if (st != 0) throw std::domain_error("legendre_symbol: outside the domain");
+  return sym;
+}
+// (a / n), the Jacobi symbol: -1, 0 or 1, for an odd n > 0 of at most 8192 bits and any integer a; std::domain_error otherwise
+inline int jacobi_symbol(const BigInt& a, const BigInt& n) {
+  if (n.is_negative() || n.is_zero() || !n.is_odd() || n.bit_length() > 8192) throw std::domain_error("jacobi_symbol: n is not a positive odd integer of at most 8192 bits");
+  Engine& e = Engine::instance();
+  const uint32_t mb = n.bit_length() <= 1024 ? 1024 : n.bit_length() <= 2048 ? 2048 : n.bit_length() <= 4096 ? 4096 : 8192, L = mb / 32;
+  std::vector<uint32_t> av(L), nv(L);
+  a.modulus(n).to_limbs(av.data(), L);         // ((a / n) depends on a mod n only)
+  n.to_limbs(nv.data(), L);
+  int32_t sym = 0;
+  uint8_t st = 9;
+  e.check(zkp_jacobi_batch(e.ctx(), mb, 1, av.data(), nv.data(), 0, &sym, &st, 0), "zkp_jacobi_batch");
+  if (st != 0) throw std::domain_error("jacobi_symbol: outside the domain");
+  return sym;
+}
+}  // namespace wi_dlog_proof
 
 // ------------------------------------------------------------------ wire format (src/serialize.rs + the serde derives)
 // Writers produce what serde_json::to_string produces for the reference's types; readers go through the batched
