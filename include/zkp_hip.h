@@ -557,6 +557,34 @@ int32_t zkp_dlog_statement_setup_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uin
                                               uint64_t first_index, uint32_t* out_g, uint32_t* out_ni, uint32_t* out_secret,
                                               uint8_t* out_status, uint32_t flags);
 
+/* ------------------------------------------------------------------ Paillier decrypt and open with the factors (CRT)
+ * zkp_paillier_open_batch: for a key (p, q), n = p q, and a ciphertext c — ANY value below 2^(2 n_bits), c >= n^2 included —
+ *     x_p = (c mod p^2)^(p-1) mod p^2     L_p = (x_p - 1) / p     m_p = L_p h_p mod p      m = m_p + p ((m_q - m_p) pinv mod q)
+ *     r_p = (c mod p)^(d_p) mod p                                                          r = r_p + p ((r_q - r_p) pinv mod q)
+ * (q alike) with the per-key constants h_p = (p - (q mod p))^-1 mod p, pinv = p^-1 mod q, d_p = q^-1 mod (p - 1).  out_m is what
+ * Paillier::decrypt returns and (out_m, out_r) what Paillier::open returns (the call `correct_opening.rs:48-56` makes before
+ * verify_opening; the n-th root `extract_nroot` takes, correct_key_ni.rs:68): for c = Enc(m0, r0) with r0 coprime to n they are m0 and r0.
+ * n_bits in {1024, 2048, 4096}; p, q: hw = n_bits/64 words each, key_stride = 0 (one key for the call) or hw (one key per item);
+ * c [count][2 kw], out_m, out_r [count][kw], kw = n_bits/32, count <= 2^24.  out_r == NULL: decrypt only, the two root exponentiations are not run.
+ * The exponentiations are zkp_modexp_batch's ladder at mod_bits = max(n_bits, 2048) with n_bits/2-bit exponents — 2 rows per item, 4
+ * with out_r — and a call goes, whole, to the engine that call would go to for the same (rows, mod_bits); the rest is
+ * csrc/kernels_paillier_dec.hpp.
+ * DOMAIN (rules of THIS library; the reference has no error here and returns a number that means nothing).  out_status[i] (nullable) is
+ * 0, or ZKP_VERDICT_MALFORMED (2) — then out_m and out_r of item i are zero, and the other items are unaffected.  A KEY is bad when p or
+ * q is even or below 3, or when one of the inverses above does not exist: gcd(p, q), gcd(q, p - 1) or gcd(p, q - 1) != 1, together
+ * gcd(n, phi(n)) != 1.  No primality test is made: the formulas are applied to the key the caller gave.  An ITEM is bad when its key is,
+ * or when x_p != 1 mod p or x_q != 1 mod q — for prime factors: c shares a factor with n, c = 0 included.
+ * SECURITY CONTRACT.  For the length of the call, p and q, the constants derived from them, the exponents p - 1, q - 1, d_p, d_q, the
+ * residues and ladder results, the ladder's per-row constants (which hold the moduli p^2, q^2, p, q) and window tables, and the recovered
+ * m and r of a host-pointer call live in device blocks of the context that runs the call.  Every one of those
+ * blocks is zeroed on the stream before the call's blocks are given back, on error returns too; zkp_diag_witness_residue then reads 0.
+ * With ZKP_F_DEVICE_PTRS p, q, out_m and out_r are the caller's to wipe.  The secret exponents go through the ladder that every other
+ * exponentiation of this library uses (NiCorrectKeyProof's n^-1 mod phi among them); nothing is claimed about its timing behaviour, nor
+ * about that of the division and reduction kernels around it. */
+int32_t zkp_paillier_open_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t count, const uint32_t* p, const uint32_t* q, uint64_t key_stride,
+                                const uint32_t* c, uint32_t* out_m, uint32_t* out_r /* nullable: decrypt only */,
+                                uint8_t* out_status /* nullable */, uint32_t flags);
+
 /* ------------------------------------------------------------------ wire format
  * The reference serialises big integers as DECIMAL strings (src/serialize.rs:1-31 `bigint`, :33-78 `vecbigint`:
  * BigInt::to_str_radix(10) / from_str_radix(s, 10) = GMP mpz_get_str / mpz_set_str).  The two L1 entry points below

@@ -181,6 +181,8 @@ EXPORTS = {
     "zkp_legendre_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_dlog_statement_setup_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                           C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_paillier_open_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_uint32]),
     "zkp_verlin_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_verlin_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
     "zkp_multi_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -625,6 +627,13 @@ class Context:
         """zkp_dlog_statement_setup_seeded_batch: g = h1 with (h1 / N) == -1, secret < 2^256, ni = (h1^-1)^secret mod N"""
         self.check(self.lib.zkp_dlog_statement_setup_seeded_batch(self.h, n_bits, batch, ptr(N), _seed(seed), first_index, ptr(out_g), ptr(out_ni),
                                                                   ptr(out_secret), ptr(out_status), self._flags(N, out_g, out_ni, out_secret, out_status)))
+
+    # ---- Paillier decrypt / open with the factors: CRT under p^2, q^2 (and p, q for the randomness)
+    def paillier_open(self, n_bits, count, p, q, key_stride, c, out_m, out_r, out_status, device=False):
+        """zkp_paillier_open_batch: out_m = Dec(c), out_r = the n-th root of c mod n (None: decrypt only); out_status 2 where the key or the
+        ciphertext is outside the domain (outputs zero)"""
+        self.check(self.lib.zkp_paillier_open_batch(self.h, n_bits, count, ptr(p), ptr(q), key_stride, ptr(c), ptr(out_m), ptr(out_r), ptr(out_status),
+                                                    ZKP_F_DEVICE_PTRS if device else 0))
 
     # ---- seeded proving of VerlinProof and MulProof: r_a / r_d are redrawn on the GPU until they are coprime to n
     def nonce_sample_coprime(self, kind, n_bits, batch, n, n_stride, seed: bytes, first_index: int, out_fields, out_status):

@@ -27,6 +27,7 @@
 #include "kernels_sample.hpp"
 #include "kernels_coprime.hpp"
 #include "kernels_jacobi.hpp"
+#include "kernels_paillier_dec.hpp"
 #include "route_plan.hpp"             // every size-based decision of this file and of zkp_api_proofs.inc
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
@@ -88,6 +89,7 @@ struct zkp_ctx {
   // the regions of staging blocks that held the secrets of the most recent seeded prove / sample call (expanded witness, seed, staged x / r):
   // zeroed on the stream before the blocks went back to the cache above (Stage::wipe_now); zkp_diag_witness_residue reads them
   std::vector<std::pair<void*, size_t>> last_wiped;
+  int wiped_on = -1;                   // the secondary engine (0 | 1) whose twin ctx ran — and wiped — the most recent call with secrets; -1: this ctx did
   uint32_t* setup_flag = nullptr;      // device word: k_setup ORs the status of every modulus it rejects into it
   uint32_t* setup_flag_host = nullptr; // its pinned host mirror
   int device = 0;
@@ -182,7 +184,8 @@ static int32_t zkp_caught(zkp_ctx* c, int32_t st, const char* what) noexcept {
   X(zkp_mul_proof_prove_batch) X(zkp_mul_proof_verify_batch) X(zkp_correct_message_prove_batch) X(zkp_correct_message_verify_batch)           \
   X(zkp_diag_basen) X(zkp_diag_basen_last) X(zkp_diag_set_enc_form) X(zkp_diag_set_r2l) X(zkp_diag_r2l_last) X(zkp_diag_set_r2l_lanes) X(zkp_diag_r2l_lanes_last) X(zkp_diag_set_key_cache) X(zkp_diag_key_cache_state) \
   X(zkp_diag_set_fuse_hash) X(zkp_diag_last_fused_hash)                                                                            \
-  X(zkp_json_sigma_batch) X(zkp_json_write_sigma_batch) X(zkp_sigma_verify_json_batch)
+  X(zkp_json_sigma_batch) X(zkp_json_write_sigma_batch) X(zkp_sigma_verify_json_batch)                                         \
+  X(zkp_paillier_open_batch) X(zkp_diag_witness_residue)
 
 struct LatEngine {
   void* handle = nullptr;
@@ -308,6 +311,7 @@ struct Stage {
     if (wipe.empty()) return;
     for (auto& w : wipe) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);
     c->last_wiped.swap(wipe);
+    c->wiped_on = -1;
     wipe.clear();
   }
   // An error return between the fork onto the ctx's second stream and the join: the kernels there may still read the staging
@@ -586,12 +590,16 @@ static int32_t side_stream(zkp_ctx* c) {
   return ZKP_OK;
 }
 
-template <int G, class K> static int32_t table_for(zkp_ctx* c, K kernel, uint64_t items, unsigned* blocks_out) {
+// the grid of a persistent launch of `kernel` over `items` and the bytes of its window tables
+template <int G, class K> static size_t table_bytes(zkp_ctx* c, K kernel, uint64_t items, unsigned* blocks_out) {
   using LL = LdsLayout<G>;
   const uint64_t need = (items + LL::GROUPS_PER_BLOCK - 1) / LL::GROUPS_PER_BLOCK;
   const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(need, (uint64_t)resident_blocks<G>(c, kernel)));
   *blocks_out = blocks;
-  return ensure(c, c->table, (size_t)blocks * LL::GROUPS_PER_BLOCK * TAB * Geo<G>::L * sizeof(uint32_t));
+  return (size_t)blocks * LL::GROUPS_PER_BLOCK * TAB * Geo<G>::L * sizeof(uint32_t);
+}
+template <int G, class K> static int32_t table_for(zkp_ctx* c, K kernel, uint64_t items, unsigned* blocks_out) {
+  return ensure(c, c->table, table_bytes<G>(c, kernel, items, blocks_out));
 }
 
 constexpr bool PAIR_LADDER_BUILD = ZKP_W <= 9;            // the pair kernels (route_plan.hpp: pair_ladder) are instantiated in the latency engine only
@@ -1371,6 +1379,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 #include "zkp_api_mul.inc"
 #include "zkp_api_seeded.inc"
 #include "zkp_api_jacobi.inc"
+#include "zkp_api_paillier_dec.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE
 #include "zkp_api_multi.inc"

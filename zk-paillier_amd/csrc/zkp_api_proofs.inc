@@ -395,6 +395,14 @@ extern "C" int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* c, const zkp_range_n
 extern "C" int32_t zkp_diag_witness_residue(zkp_ctx* c, uint64_t* out_nonzero_words) try {
   if (!c || !out_nonzero_words) return ZKP_EINVAL;
   *out_nonzero_words = 0;
+#ifndef ZKP_SECONDARY_ENGINE
+  // the most recent call with secrets ran whole on a secondary engine's twin ctx: its blocks, its wipe, its answer
+  if (c->wiped_on >= 0 && c->eng[c->wiped_on] && c->eng_ctx[c->wiped_on]) {
+    const int32_t st = c->eng[c->wiped_on]->p_zkp_diag_witness_residue(c->eng_ctx[c->wiped_on], out_nonzero_words);
+    if (st) { try { c->err = c->eng[c->wiped_on]->p_zkp_last_error_string(c->eng_ctx[c->wiped_on]); } catch (...) {} }
+    return st;
+  }
+#endif
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->last_wiped.empty()) return ZKP_OK;
