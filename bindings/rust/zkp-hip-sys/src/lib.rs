@@ -184,6 +184,7 @@ extern "C" {
     pub fn zkp_legendre_batch(ctx: *mut zkp_ctx, mod_bits: u32, count: u64, a: *const u32, p: *const u32, p_stride: u64, out_symbol: *mut i32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_dlog_statement_setup_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, N: *const u32, seed: *const u8, first_index: u64, out_g: *mut u32, out_ni: *mut u32, out_secret: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_paillier_open_batch(ctx: *mut zkp_ctx, n_bits: u32, count: u64, p: *const u32, q: *const u32, key_stride: u64, c: *const u32, out_m: *mut u32, out_r: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_correct_key_ni_prove_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, p: *const u32, q: *const u32, salt: *const u8, salt_len: u32, out_n: *mut u32, out_sigma: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_decimal_to_limbs_batch(ctx: *mut zkp_ctx, text: *const c_char, text_len: u64, items: *const zkp_dec_item, count: u64, dst: *mut u32, dst_words: u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_decimal_pitch(words: u32) -> u32;
     pub fn zkp_limbs_to_decimal_batch(ctx: *mut zkp_ctx, src: *const u32, src_stride: u64, words: u32, count: u64, out_text: *mut c_char, pitch: u32, out_len: *mut u32, flags: u32) -> i32;

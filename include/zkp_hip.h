@@ -585,6 +585,35 @@ int32_t zkp_paillier_open_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t count, c
                                 const uint32_t* c, uint32_t* out_m, uint32_t* out_r /* nullable: decrypt only */,
                                 uint8_t* out_status /* nullable */, uint32_t flags);
 
+/* ------------------------------------------------------------------ NiCorrectKeyProof::proof for whole batches of keys (CRT n-th roots)
+ * zkp_correct_key_ni_prove_batch: for key b = (p, q) (correct_key_ni.rs:42-71; one key per proof — a proof is about its key)
+ *     n = p q      rho_i = mask_generation(bit_length(n), H(n, H(salt), i)) mod n,  i = 0..10      sigma_i = rho_i^(n^-1 mod phi(n)) mod n
+ * with sigma_i computed as upstream's extract_nroot does:
+ *     s_p = (rho_i mod p)^(d_p) mod p,  s_q alike      sigma_i = s_p + p ((s_q - s_p) pinv mod q)
+ * d_p = q^-1 mod (p - 1) (= n^-1 mod (p - 1)), d_q = p^-1 mod (q - 1), pinv = p^-1 mod q.  bit_length(n) is the key's own, not n_bits.
+ * n_bits in {1024, 2048, 4096}; p, q [batch][hw], hw = n_bits/64; salt: HOST bytes in both memory modes, as in verify; out_n [batch][kw]
+ * (nullable), out_sigma [batch][11][kw], kw = n_bits/32; batch <= 2^24, batch == 0 is ZKP_OK.  ZKP_EINVAL: a null ctx, p, q or out_sigma,
+ * another n_bits, salt_len without salt, a flag bit other than ZKP_F_DEVICE_PTRS.  (out_n, out_sigma) are what
+ * zkp_correct_key_ni_verify_batch and zkp_json_write_correct_key_proof_batch take.
+ * The exponentiations are zkp_modexp_batch's ladder at mod_bits = 2048 (= max(n_bits/2, 2048): the narrowest group) with n_bits/2-bit
+ * exponents, 22 rows per key, and a call goes, whole, to the engine that call would go to for the same (rows, mod_bits); rho comes from
+ * the verifier's hash kernels over the device-resident n; the rest is csrc/kernels_ck_prove.hpp and the key kernels of
+ * csrc/kernels_paillier_dec.hpp.
+ * DOMAIN (rules of THIS library, those of zkp_paillier_open_batch; the reference's `mod_inv(..).unwrap()` panics on such a key).
+ * out_status[b] (nullable) is 0, or ZKP_VERDICT_MALFORMED (2) — then out_sigma[b] and out_n[b] are zero, and the other keys are
+ * unaffected.  A key is bad when p or q is even or below 3, or when gcd(p, q), gcd(q, p - 1) or gcd(p, q - 1) != 1.  No primality test is
+ * made: the formulas are applied to the key the caller gave, and for prime p and q their value is rho_i^(n^-1 mod phi(n)) mod n.  There is
+ * no per-root status: a rho_i that shares a factor with n has the value the formulas give (for prime factors still rho_i^d mod n).
+ * SECURITY CONTRACT.  For the length of the call, p and q, the constants derived from them (d_p, d_q, pinv), the residues rho mod p and
+ * rho mod q and the ladder's results, the ladder's per-row constants (which hold the moduli p, q) and window tables live in device blocks
+ * of the context that runs the call.  Every one of those blocks is zeroed on the stream before the call's blocks are given back, on error
+ * returns too; zkp_diag_witness_residue then reads 0.  rho, n and sigma are public.  With ZKP_F_DEVICE_PTRS the caller's p and q are the
+ * caller's to wipe.  The secret exponents go through the ladder that every other exponentiation of this library uses; nothing is claimed
+ * about its timing behaviour, nor about that of the division and reduction kernels around it. */
+int32_t zkp_correct_key_ni_prove_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, const uint32_t* p, const uint32_t* q,
+                                       const uint8_t* salt, uint32_t salt_len, uint32_t* out_n /* nullable */, uint32_t* out_sigma,
+                                       uint8_t* out_status /* nullable */, uint32_t flags);
+
 /* ------------------------------------------------------------------ wire format
  * The reference serialises big integers as DECIMAL strings (src/serialize.rs:1-31 `bigint`, :33-78 `vecbigint`:
  * BigInt::to_str_radix(10) / from_str_radix(s, 10) = GMP mpz_get_str / mpz_set_str).  The two L1 entry points below

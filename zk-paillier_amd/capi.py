@@ -183,6 +183,8 @@ EXPORTS = {
                                                           C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_paillier_open_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_uint32]),
+    "zkp_correct_key_ni_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_verlin_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_verlin_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
     "zkp_multi_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -561,6 +563,13 @@ class Context:
         self.check(self.lib.zkp_correct_key_ni_verify_batch(self.h, n_bits, batch, ptr(n), ptr(sigma),
                                                             C.cast(sb, C.c_void_p) if sb else None, len(salt),
                                                             ptr(out_verdict), self._flags(n, sigma, out_verdict)))
+
+    def correct_key_ni_prove(self, n_bits, batch, p, q, salt: bytes, out_n, out_sigma, out_status=None):
+        """zkp_correct_key_ni_prove_batch: one proof per key (p, q), the n-th roots by CRT on the GPU.  p, q: [batch][n_bits / 64];
+        out_n (or None): [batch][n_bits / 32]; out_sigma: [batch][11][n_bits / 32]; out_status (or None): 2 where the key is outside
+        the domain (its n and roots zero).  numpy arrays, or torch cuda tensors (all of them); the salt is host bytes in both modes."""
+        self.check(self.lib.zkp_correct_key_ni_prove_batch(self.h, n_bits, batch, ptr(p), ptr(q), salt if salt else None, len(salt), ptr(out_n),
+                                                           ptr(out_sigma), ptr(out_status), self._flags(p, q, out_n, out_sigma, out_status)))
 
     def dlog_prove(self, n_bits, y_bits, batch, N, g, ni, secret, r, out_x, out_y):
         self.check(self.lib.zkp_dlog_prove_batch(self.h, n_bits, y_bits, batch, ptr(N), ptr(g), ptr(ni), ptr(secret),

@@ -192,7 +192,7 @@ struct PdecKeyArgs {
   const uint32_t* p; const uint32_t* q; uint64_t key_stride;   // [nkeys][hw]
   uint32_t* inv_a; uint32_t* inv_m;                            // [4 nkeys][hw]   operands and moduli of the inverse kernel
   const uint32_t* inv; const uint8_t* inv_status;              // [4 nkeys][hw], [4 nkeys]   its results (part b)
-  uint32_t* hp; uint32_t* hq; uint32_t* dp; uint32_t* dq;      // [nkeys][hw]   (pinv is row 1 of inv)
+  uint32_t* hp; uint32_t* hq; uint32_t* dp; uint32_t* dq;      // [nkeys][hw]   (pinv is row 1 of inv); hp, hq nullable
   uint8_t* kst;                                                // [nkeys] 0 | 2
   uint64_t nkeys; int hw;
 };
@@ -235,13 +235,13 @@ __global__ void __launch_bounds__(64) k_pdec_key_b(PdecKeyArgs a) {
   const uint32_t* Q = a.q + key * a.key_stride;
   bool ok = a.kst[key] == 0;
   for (int row = 0; row < 4; row++) ok = ok && a.inv_status[key * 4 + row] == ZKP_INV_OK;
-  uint32_t* hp = a.hp + key * (uint64_t)hw;
-  uint32_t* hq = a.hq + key * (uint64_t)hw;
+  uint32_t* hp = a.hp ? a.hp + key * (uint64_t)hw : nullptr;  // (hp, hq null: a caller that takes roots only, kernels_ck_prove.hpp)
+  uint32_t* hq = a.hq ? a.hq + key * (uint64_t)hw : nullptr;
   uint32_t* dp = a.dp + key * (uint64_t)hw;
   uint32_t* dq = a.dq + key * (uint64_t)hw;
   a.kst[key] = ok ? 0 : 2;
   if (!ok) {
-    for (int w = 0; w < hw; w++) { hp[w] = 0u; hq[w] = 0u; dp[w] = 0u; dq[w] = 0u; }
+    for (int w = 0; w < hw; w++) { if (hp) hp[w] = 0u; if (hq) hq[w] = 0u; dp[w] = 0u; dq[w] = 0u; }
     return;
   }
   uint32_t* x = pd_lds + threadIdx.x;                          // 2 hw words: M y, then the exact division's running value
@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(64) k_pdec_key_b(PdecKeyArgs a) {
     uint32_t* h = side ? hq : hp;
     uint32_t* d = side ? dq : dp;
     uint32_t borrow = 0;
-    for (int w = 0; w < hw; w++) {                             // h = F - u   (0 < u < F)
+    for (int w = 0; h && w < hw; w++) {                        // h = F - u   (0 < u < F)
       const uint64_t v = (uint64_t)F[w] - u[w] - borrow;
       h[w] = (uint32_t)v;
       borrow = (uint32_t)(v >> 63);

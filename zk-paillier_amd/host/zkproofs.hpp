@@ -8,7 +8,7 @@
 //   zkproofs::{MulProof, CorrectMessageProof}::{prove,verify}, BigInt::mod_inv    MulProof, CorrectMessageProof, mod_inv_batch
 //   zkproofs::RangeProof::{verifier_commit,verify_commit,generate_encrypted_pairs,generate_proof,verifier_output}   RangeProof::*
 //     src/zkproofs/range_proof_ni.rs:36-128
-//   zkproofs::NiCorrectKeyProof::{proof,verify}                     NiCorrectKeyProof::{proof,verify}
+//   zkproofs::NiCorrectKeyProof::{proof,verify}                     NiCorrectKeyProof::{proof,verify}   (+ proof_batch, verify_batch)
 //     src/zkproofs/correct_key_ni.rs:36-100
 //   zkproofs::{CompositeDLogProof,DLogStatement}::{prove,verify}    same (+ DLogStatement::generate_batch_seeded)
 //     src/zkproofs/wi_dlog_proof.rs:33-91
@@ -923,6 +923,43 @@ class NiCorrectKeyProof {
     NiCorrectKeyProof p;
     for (size_t i = 0; i < M2; i++) p.sigma_vec.push_back(BigInt::from_limbs(&out[i * kw], kw));
     return p;
+  }
+  // The same for many keys in ONE zkp_correct_key_ni_prove_batch per kernel width (the widths are grouped as verify_batch groups them; a key
+  // whose factors do not both fit half its width takes the next one): n, rho and the n-th roots — by upstream's extract_nroot, CRT under p
+  // and q — are computed on the GPU, n^-1 mod phi is never formed, and the staging that carries p and q is wiped on release.  A key the call
+  // marks ZKP_VERDICT_MALFORMED (an even or trivial factor, gcd(n, phi(n)) != 1), or a factor that is not positive, is a Panic naming the
+  // key's index, as `mod_inv(..).unwrap()` is in the reference; a factor wider than 2048 bits throws std::length_error.
+  static std::vector<NiCorrectKeyProof> proof_batch(const std::vector<const DecryptionKey*>& keys, const uint8_t* salt = SALT_STRING, size_t salt_len = 4) {
+    Engine& e = Engine::instance();
+    std::vector<NiCorrectKeyProof> out(keys.size());
+    std::vector<uint32_t> width(keys.size());
+    for (size_t k = 0; k < keys.size(); k++) {
+      const DecryptionKey& dk = *keys[k];
+      if (dk.p.is_negative() || dk.q.is_negative() || dk.p.is_zero() || dk.q.is_zero()) throw Panic("NiCorrectKeyProof::proof_batch: key " + std::to_string(k) + " is outside the domain (a factor is not positive)");
+      const size_t fb = std::max(dk.p.bit_length(), dk.q.bit_length());
+      if (fb > 2048) throw std::length_error("NiCorrectKeyProof::proof_batch: key " + std::to_string(k) + ": factor wider than 2048 bits");
+      uint32_t nb = width_for(dk.p * dk.q);
+      while (fb > nb / 2) nb *= 2;
+      width[k] = nb;
+    }
+    for (uint32_t nb : {1024u, 2048u, 4096u}) {
+      const uint32_t kw = nb / 32, hw = nb / 64;
+      std::vector<size_t> idx;
+      for (size_t k = 0; k < keys.size(); k++) if (width[k] == nb) idx.push_back(k);
+      if (idx.empty()) continue;
+      RawBuf<uint32_t> p(idx.size() * hw, true), q(idx.size() * hw, true);                       // (secret: wiped on release)
+      std::vector<uint32_t> sg(idx.size() * M2 * kw);
+      std::vector<uint8_t> st(idx.size(), 9);
+      for (size_t j = 0; j < idx.size(); j++) { keys[idx[j]]->p.to_limbs(&p[j * hw], hw); keys[idx[j]]->q.to_limbs(&q[j * hw], hw); }
+      const int32_t rc = zkp_correct_key_ni_prove_batch(e.ctx(), nb, idx.size(), p.data(), q.data(), salt, (uint32_t)salt_len, nullptr, sg.data(), st.data(), 0);
+      p.wipe_now(); q.wipe_now();
+      e.check(rc, "zkp_correct_key_ni_prove_batch");
+      for (size_t j = 0; j < idx.size(); j++) {
+        if (st[j] != 0) throw Panic("NiCorrectKeyProof::proof_batch: key " + std::to_string(idx[j]) + " is outside the domain (ZKP_VERDICT_MALFORMED)");
+        for (size_t i = 0; i < M2; i++) out[idx[j]].sigma_vec.push_back(BigInt::from_limbs(&sg[(j * M2 + i) * kw], kw));
+      }
+    }
+    return out;
   }
   // correct_key_ni.rs:73-100 for many (key, proof) pairs in ONE zkp_correct_key_ni_verify_batch (keys of one kernel width per call; the
   // widths are grouped here).  sigma_i is prover-chosen: any size, either sign — the reference only uses it as mod_pow(sigma_i, n, n),
