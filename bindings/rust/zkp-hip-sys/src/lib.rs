@@ -34,6 +34,7 @@ pub const ZKP_SEEDED_KIND_DLOG: u32 = 4;
 pub const ZKP_SEEDED_KIND_VERLIN: u32 = 5;
 pub const ZKP_SEEDED_KIND_MUL: u32 = 6;
 pub const ZKP_SEEDED_KIND_DLOG_SETUP: u32 = 8;
+pub const ZKP_SEEDED_KIND_KEYGEN: u32 = 9;
 pub const ZKP_DEC_OK: u8 = 0;
 pub const ZKP_DEC_INVALID: u8 = 1;
 pub const ZKP_DEC_NEGATIVE: u8 = 2;
@@ -185,6 +186,9 @@ extern "C" {
     pub fn zkp_dlog_statement_setup_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, N: *const u32, seed: *const u8, first_index: u64, out_g: *mut u32, out_ni: *mut u32, out_secret: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_paillier_open_batch(ctx: *mut zkp_ctx, n_bits: u32, count: u64, p: *const u32, q: *const u32, key_stride: u64, c: *const u32, out_m: *mut u32, out_r: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_correct_key_ni_prove_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, p: *const u32, q: *const u32, salt: *const u8, salt_len: u32, out_n: *mut u32, out_sigma: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_probable_prime_batch(ctx: *mut zkp_ctx, bits: u32, count: u64, w: *const u32, rounds: u32, seed: *const u8, first_index: u64, out_verdict: *mut u8, flags: u32) -> i32;
+    pub fn zkp_next_prime_batch(ctx: *mut zkp_ctx, bits: u32, count: u64, start: *const u32, rounds: u32, seed: *const u8, first_index: u64, out_prime: *mut u32, out_offset: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_paillier_keygen_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, rounds: u32, seed: *const u8, first_index: u64, out_p: *mut u32, out_q: *mut u32, out_n: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_decimal_to_limbs_batch(ctx: *mut zkp_ctx, text: *const c_char, text_len: u64, items: *const zkp_dec_item, count: u64, dst: *mut u32, dst_words: u64, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_decimal_pitch(words: u32) -> u32;
     pub fn zkp_limbs_to_decimal_batch(ctx: *mut zkp_ctx, src: *const u32, src_stride: u64, words: u32, count: u64, out_text: *mut c_char, pitch: u32, out_len: *mut u32, flags: u32) -> i32;

@@ -614,6 +614,57 @@ int32_t zkp_correct_key_ni_prove_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t b
                                        const uint8_t* salt, uint32_t salt_len, uint32_t* out_n /* nullable */, uint32_t* out_sigma,
                                        uint8_t* out_status /* nullable */, uint32_t flags);
 
+/* ------------------------------------------------------------------ probable primes, next prime, seeded Paillier key generation
+ * Three layers of one piece of code (csrc/kernels_prime.hpp).  bits in {512, 1024, 2048} is the width of a value, pw = bits/32 words; these
+ * are the factor widths of n_bits in {1024, 2048, 4096}.  The rule below is THIS library's published rule (tests/prime_model.py restates
+ * it); it is not a claim of parity with upstream's keygen, whose shape it keeps: draw, set the low and the top bit, walk +2 through trial
+ * division and strong tests, redraw.
+ *   T: all odd primes below 6370 (the bound of the NiCorrectKeyProof verifier's primorial test).
+ *   sprp(w, a), w odd > 3, 2 <= a <= w - 2: w - 1 = 2^s d with d odd, y = a^d mod w; passes iff y == 1, or y == w - 1, or
+ *     y^(2^j) == w - 1 for some 1 <= j <= s - 1.
+ *   Bases: base 0 is 2.  For round r = 1 .. rounds and L = bit_length(w), a_r = 2 + v, v = the first ceil((L - 2) / 32) keystream words from
+ *     block 0 on of the stream below, as limbs, masked to L - 2 bits: a_r in [2, 2^(L-2) + 1], a subset of [2, w - 2].  The bases depend on
+ *     (seed, index, field, r) and on L only: all candidates of one window share them.
+ *   Stream: the nonce-stream construction above, unchanged (state words 13, 14 = index = first_index + i; word 15 = 0x80000000 |
+ *     kind << 20 | slot << 4 | field), with one more kind:
+ *       kind        slot              field   value
+ *       9 Keygen    0                 0 / 1   start of attempt t for p / q: the first pw words of blocks [t nb, (t + 1) nb), nb = ceil(pw / 16),
+ *                                             then bit 0 and bit bits - 1 set
+ *       9 Keygen    r (1 .. rounds)   2 / 3   base a_r for p / q          (zkp_probable_prime_batch and zkp_next_prime_batch: field 2)
+ *   is_probable_prime(w), any w < 2^bits, in this order: w < 2 -> 0; w == 2 -> 1; w even -> 0; for each l in T: w == l -> 1, l | w -> 0;
+ *     w < 6370^2 -> 1 (exact: a composite below that has a factor in T); otherwise 1 iff sprp(w, 2) and sprp(w, a_r) for every r <= rounds.
+ *     0 <= rounds <= 64; rounds == 0 is the base-2 test alone.
+ *   next_prime(start): c_j = (start | 1) + 2 j, j = 0 .. 511; the first c_j < 2^bits, in order of j, with is_probable_prime(c_j) == 1, else none.
+ *   Key b: for p (field 0) and q (field 1), attempts t = 0, 1, .., at most 128, take next_prime(start_t) with that factor's bases; the first
+ *     attempt that finds one ends the search.  n = p q has n_bits or n_bits - 1 bits.  ZKP_VERDICT_MALFORMED (2) with zero p, q, n when
+ *     either search used up its attempts or p == q; the other keys are unaffected.  With equal-width primes gcd(n, phi(n)) = 1 follows
+ *     from p != q: a key made here is in the domain of zkp_paillier_open_batch.  No safe primes, no congruence conditions.
+ * zkp_probable_prime_batch: out_verdict[i] = is_probable_prime(w[i]), w [count][pw].
+ * zkp_next_prime_batch: out_prime [count][pw], out_offset [count] (j; nullable), out_status [count] (nullable; 0, or 2: none in the window,
+ *   then out_prime and out_offset of the item are zero).
+ * zkp_paillier_keygen_seeded_batch: out_p, out_q [batch][hw], hw = n_bits/64; out_n [batch][kw] (nullable), kw = n_bits/32; out_status
+ *   [batch] (nullable).
+ * `seed` (32 bytes) is a HOST pointer in both memory modes; it may be null only when rounds == 0, in the first two calls.
+ * ZKP_F_DEVICE_PTRS is the only flag.  count, batch <= 2^20; 0 is ZKP_OK.  ZKP_EINVAL: a null ctx, a null required pointer, another width,
+ * rounds > 64, an unknown flag; nothing is launched then.  A call split with first_index + lo equals the one call.
+ * The exponentiations are zkp_modexp_batch's ladder at mod_bits = 2048 (narrower candidates travel zero-padded) with bits-bit exponents.
+ * The calls run on the engine of the context that receives them, as zkp_dlog_statement_setup_seeded_batch does.
+ * SECURITY CONTRACT, in the words of the two calls above: the seed is worth the key.  Every block of the context that held a start, a
+ * candidate, a residue or a survivor map, a ladder row, the ladder's constants records and window tables (they hold the candidates as
+ * moduli), a base, or the staged w / start / out_p / out_q / out_prime of a host-pointer call is registered secret with the call's stage
+ * and zeroed on the stream before the call's blocks are given back, on error returns too; zkp_diag_witness_residue then reads 0.  With
+ * ZKP_F_DEVICE_PTRS the caller's arrays are the caller's to wipe.  Nothing is claimed about timing: the number of attempts, of ladder rows
+ * and of squarings depends on the secret, as upstream's loop count does. */
+#define ZKP_SEEDED_KIND_KEYGEN 9u
+int32_t zkp_probable_prime_batch(zkp_ctx* ctx, uint32_t bits, uint64_t count, const uint32_t* w, uint32_t rounds, const uint8_t* seed,
+                                 uint64_t first_index, uint8_t* out_verdict, uint32_t flags);
+int32_t zkp_next_prime_batch(zkp_ctx* ctx, uint32_t bits, uint64_t count, const uint32_t* start, uint32_t rounds, const uint8_t* seed,
+                             uint64_t first_index, uint32_t* out_prime, uint32_t* out_offset /* nullable */,
+                             uint8_t* out_status /* nullable */, uint32_t flags);
+int32_t zkp_paillier_keygen_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, uint32_t rounds, const uint8_t* seed,
+                                         uint64_t first_index, uint32_t* out_p, uint32_t* out_q, uint32_t* out_n /* nullable */,
+                                         uint8_t* out_status /* nullable */, uint32_t flags);
+
 /* ------------------------------------------------------------------ wire format
  * The reference serialises big integers as DECIMAL strings (src/serialize.rs:1-31 `bigint`, :33-78 `vecbigint`:
  * BigInt::to_str_radix(10) / from_str_radix(s, 10) = GMP mpz_get_str / mpz_set_str).  The two L1 entry points below

@@ -104,6 +104,16 @@ int32_t zkp_diag_key_cache_state(zkp_ctx* ctx, int32_t which, uint32_t* out);
  * zkp_ctx_release_staging has freed them).  0 is the only good answer; 0 as well before the first seeded call. */
 int32_t zkp_diag_witness_residue(zkp_ctx* ctx, uint64_t* out_nonzero_words);
 
+/* The table of the probable-prime test (include/zkp_hip.h: all odd primes below 6370): the number of entries and the last one, read from
+ * the host copy of the ONE compile-time initialiser that also fills the device table (csrc/kernels_prime.hpp).  Needs no context and no GPU. */
+int32_t zkp_diag_prime_table(uint32_t* out_count, uint32_t* out_last);
+
+/* The prime search behind zkp_next_prime_batch and zkp_paillier_keygen_seeded_batch runs C rows per unresolved slot and round,
+ * C = target_rows / (slots left), at least `chunk` and at most 64 — tuning quantities: no result depends on them.  chunk in 1 .. 64 and
+ * target_rows in 1 .. 2^20 set them for this ctx (target_rows = 1: a fixed chunk), 0 restores the built-in value, a negative one leaves it.
+ * out_rows and out_rounds (nullable): the ladder rows and the rounds of the most recent search of this ctx (tools/dev/keygen_ab.py). */
+int32_t zkp_diag_prime_search(zkp_ctx* ctx, int32_t chunk, int64_t target_rows, uint64_t* out_rows, uint64_t* out_rounds);
+
 /* The most recent call of this ctx that read documents through the device scanner (zkp_range_ni_verify_json_batch,
  * zkp_correct_key_ni_verify_json_batch, zkp_dlog_verify_json_batch, any of the six zkp_json_*_batch readers — zkp_json_dlog_statement_batch and
  * zkp_json_dlog_proof_batch among them — with ZKP_F_DEVICE_PTRS): the documents the scanner took itself, and the documents it left to the host

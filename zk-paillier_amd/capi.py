@@ -60,6 +60,8 @@ DIAG_EXPORTS = {
     "zkp_diag_set_key_cache": (C.c_int32, [C.c_void_p, C.c_int32]),
     "zkp_diag_key_cache_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
     "zkp_diag_witness_residue": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "zkp_diag_prime_table": (C.c_int32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "zkp_diag_prime_search": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkp_diag_last_json_scan": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkp_diag_last_json_scan_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
 }
@@ -185,6 +187,11 @@ EXPORTS = {
                                             C.c_void_p, C.c_uint32]),
     "zkp_correct_key_ni_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_probable_prime_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "zkp_next_prime_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint32]),
+    "zkp_paillier_keygen_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_verlin_proof_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.c_uint32]),
     "zkp_verlin_proof_verify_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 + [C.c_uint32]),
     "zkp_multi_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -570,6 +577,24 @@ class Context:
         the domain (its n and roots zero).  numpy arrays, or torch cuda tensors (all of them); the salt is host bytes in both modes."""
         self.check(self.lib.zkp_correct_key_ni_prove_batch(self.h, n_bits, batch, ptr(p), ptr(q), salt if salt else None, len(salt), ptr(out_n),
                                                            ptr(out_sigma), ptr(out_status), self._flags(p, q, out_n, out_sigma, out_status)))
+
+    def probable_prime(self, bits, count, w, rounds, seed, first_index, out_verdict):
+        """zkp_probable_prime_batch: out_verdict[i] = is_probable_prime(w[i]) by the rule of include/zkp_hip.h (trial division by the odd
+        primes below 6370, base 2, `rounds` seeded bases).  w: [count][bits / 32]; seed: 32 host bytes, or None when rounds == 0."""
+        self.check(self.lib.zkp_probable_prime_batch(self.h, bits, count, ptr(w), rounds, _seed(seed), first_index, ptr(out_verdict),
+                                                     self._flags(w, out_verdict)))
+
+    def next_prime(self, bits, count, start, rounds, seed, first_index, out_prime, out_offset=None, out_status=None):
+        """zkp_next_prime_batch: the first probable prime among (start | 1) + 2 j, j < 512, below 2^bits; out_offset (or None): j;
+        out_status (or None): 2 where the window holds none (prime and offset zero)."""
+        self.check(self.lib.zkp_next_prime_batch(self.h, bits, count, ptr(start), rounds, _seed(seed), first_index, ptr(out_prime), ptr(out_offset),
+                                                 ptr(out_status), self._flags(start, out_prime, out_offset, out_status)))
+
+    def paillier_keygen_seeded(self, n_bits, batch, rounds, seed, first_index, out_p, out_q, out_n=None, out_status=None):
+        """zkp_paillier_keygen_seeded_batch: key b from (seed, first_index + b), primes found on the GPU.  out_p, out_q: [batch][n_bits / 64];
+        out_n (or None): [batch][n_bits / 32]; out_status (or None): 2 for a malformed key (p, q, n zero).  The seed is worth the keys."""
+        self.check(self.lib.zkp_paillier_keygen_seeded_batch(self.h, n_bits, batch, rounds, _seed(seed), first_index, ptr(out_p), ptr(out_q), ptr(out_n),
+                                                             ptr(out_status), self._flags(out_p, out_q, out_n, out_status)))
 
     def dlog_prove(self, n_bits, y_bits, batch, N, g, ni, secret, r, out_x, out_y):
         self.check(self.lib.zkp_dlog_prove_batch(self.h, n_bits, y_bits, batch, ptr(N), ptr(g), ptr(ni), ptr(secret),

@@ -29,6 +29,7 @@
 #include "kernels_jacobi.hpp"
 #include "kernels_paillier_dec.hpp"
 #include "kernels_ck_prove.hpp"
+#include "kernels_prime.hpp"
 #include "route_plan.hpp"             // every size-based decision of this file and of zkp_api_proofs.inc
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
 #define ZKP_HAS_BASEN 1
@@ -125,6 +126,9 @@ struct zkp_ctx {
   hipStream_t split_stream = nullptr;
   hipEvent_t ev_split[2] = {nullptr, nullptr};
   int last_split = 0;            // proofs the most recent RangeProofNi call sent to the latency engine beside the mid engine (0: it was not split)
+  int prime_chunk = 0;           // zkp_diag_prime_search: the least rows per slot and round of the prime search (0: PRIME_C, csrc/zkp_api_prime.inc)
+  uint64_t prime_target = 0;     // ... and the rows a round aims at (0: PRIME_TARGET_ROWS)
+  uint64_t prime_rows = 0, prime_rounds = 0;     // ladder rows and rounds of the most recent prime search
   int key_cache = 1;             // keep the constants of the ONE key of a shared-key call across calls (setup_tag below); $ZKP_KEY_CACHE=0 at zkp_ctx_create or zkp_diag_set_key_cache turn it off
   int host_chunks = -1;          // $ZKP_HOST_CHUNKS at zkp_ctx_create: unset (-1) or 1 = a host-pointer call is one block, N = N equal blocks, 0 = uneven blocks (host_blocks)
   std::string err;
@@ -1382,6 +1386,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 #include "zkp_api_jacobi.inc"
 #include "zkp_api_paillier_dec.inc"
 #include "zkp_api_ck_prove.inc"
+#include "zkp_api_prime.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE
 #include "zkp_api_multi.inc"

@@ -193,6 +193,39 @@ struct Paillier {
     if (o.malformed) throw Panic("Paillier::open: the key or the ciphertext is outside the domain (ZKP_VERDICT_MALFORMED)");
     return {o.m, o.r};
   }
+  // [upstream kzen-paillier KeyGeneration] by the published rule of zkp_paillier_keygen_seeded_batch (include/zkp_hip.h): key b comes from
+  // (seed, first_index + b), its primes are found on the GPU, ONE call for the whole list.  n_bits in {1024, 2048, 4096}; `seed` is 32
+  // bytes and worth every key made from it: one (seed, index) pair serves one key, and the caller wipes the seed.  A key the call reports
+  // ZKP_VERDICT_MALFORMED (a search that used up its attempts, p == q) throws Panic.  The limb copies of the factors are wiped.
+  static std::vector<Keypair> keypair_batch_seeded(uint32_t n_bits, size_t count, const uint8_t* seed, uint64_t first_index = 0, uint32_t rounds = 5) {
+    Engine& e = Engine::instance();
+    const size_t hw = n_bits / 64;
+    std::vector<uint32_t> p(count * hw), q(count * hw);
+    std::vector<uint8_t> st(count);
+    const int32_t rc = zkp_paillier_keygen_seeded_batch(e.ctx(), n_bits, count, rounds, seed, first_index, p.data(), q.data(), nullptr, st.data(), 0);
+    std::vector<Keypair> out;
+    if (rc == ZKP_OK) {
+      out.reserve(count);
+      for (size_t b = 0; b < count; b++) out.push_back(Keypair{BigInt::from_limbs(&p[b * hw], hw), BigInt::from_limbs(&q[b * hw], hw)});
+    }
+    detail::ChaChaRng::wipe(p.data(), p.size() * 4);
+    detail::ChaChaRng::wipe(q.data(), q.size() * 4);
+    e.check(rc, "zkp_paillier_keygen_seeded_batch");
+    for (size_t b = 0; b < count; b++)
+      if (st[b] != 0) throw Panic("Paillier::keypair_batch_seeded: key " + std::to_string(b) + " is malformed (ZKP_VERDICT_MALFORMED)");
+    return out;
+  }
+  // [upstream Paillier::keypair_with_modulus_size / Paillier::keypair (2048)]: a seed fresh from the operating system, one key, the seed wiped
+  static Keypair keypair_with_modulus_size(uint32_t n_bits) {
+    struct Seed {
+      uint8_t bytes[32];
+      Seed() { detail::ChaChaRng::os_random(bytes, sizeof bytes); }
+      ~Seed() { detail::ChaChaRng::wipe(bytes, sizeof bytes); }
+    } seed;
+    return keypair_batch_seeded(n_bits, 1, seed.bytes)[0];
+  }
+  static Keypair keypair() { return keypair_with_modulus_size(2048); }
+
   // CorrectOpening::verify_opening (correct_opening.rs:17-30): `encrypt_with_chosen_randomness(ek, m, r) == c`
   static bool verify_opening(const EncryptionKey& ek, const BigInt& m, const BigInt& r, const BigInt& c) {
     return encrypt_with_chosen_randomness(ek, m, r) == c;
@@ -236,6 +269,27 @@ inline BigInt mod_pow(const BigInt& base, const BigInt& exp, const BigInt& modul
   base.modulus(modulus).to_limbs(bb.data(), L); exp.to_limbs(ee.data(), L); modulus.to_limbs(mm.data(), L);   // mpz_powm: a negative base gives the residue in [0, m)
   e.check(zkp_modexp_batch(e.ctx(), mb, mb, 1, bb.data(), ee.data(), L, mm.data(), L, out.data(), 0), "zkp_modexp_batch");
   return BigInt::from_limbs(out.data(), L);
+}
+
+// is_probable_prime of zkp_probable_prime_batch (include/zkp_hip.h) for a list of non-negative integers of at most 2048 bits: trial division by
+// the odd primes below 6370, the strong test to base 2 and `rounds` (<= 64) strong tests to bases drawn from (seed, first_index + i); seed
+// (32 bytes) may be null when rounds == 0.  ONE GPU call at the narrowest width that carries every value.  A negative value is not prime.
+inline std::vector<bool> is_probable_prime_batch(const std::vector<BigInt>& values, uint32_t rounds = 0, const uint8_t* seed = nullptr, uint64_t first_index = 0) {
+  Engine& e = Engine::instance();
+  const size_t cnt = values.size();
+  size_t widest = 0;
+  for (const BigInt& v : values) if (!v.is_negative()) widest = std::max(widest, v.bit_length());
+  if (widest > 2048) throw std::length_error("is_probable_prime_batch: value wider than 2048 bits");
+  const uint32_t bits = widest <= 512 ? 512 : widest <= 1024 ? 1024 : 2048, pw = bits / 32;
+  std::vector<uint32_t> w(cnt * pw);               // (zero: a negative value is tested as 0)
+  std::vector<uint8_t> verdict(cnt);
+  for (size_t i = 0; i < cnt; i++) if (!values[i].is_negative()) values[i].to_limbs(&w[i * pw], pw);
+  const int32_t rc = cnt ? zkp_probable_prime_batch(e.ctx(), bits, cnt, w.data(), rounds, seed, first_index, verdict.data(), 0) : ZKP_OK;
+  detail::ChaChaRng::wipe(w.data(), w.size() * 4);
+  e.check(rc, "zkp_probable_prime_batch");
+  std::vector<bool> out(cnt);
+  for (size_t i = 0; i < cnt; i++) out[i] = verdict[i] == 1;
+  return out;
 }
 
 // batched BigInt::mod_pow over one modulus: out[i] = bases[i]^exps[i or 0] mod modulus (ONE zkp_modexp_batch)
