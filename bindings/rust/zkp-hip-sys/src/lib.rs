@@ -34,6 +34,14 @@ pub const ZKP_SEEDED_KIND_DLOG: u32 = 4;
 pub const ZKP_SEEDED_KIND_VERLIN: u32 = 5;
 pub const ZKP_SEEDED_KIND_MUL: u32 = 6;
 pub const ZKP_SEEDED_KIND_DLOG_SETUP: u32 = 8;
+pub const ZKP_CORRECT_KEY_ROUNDS: u32 = 40;
+pub const ZKP_SEEDED_KIND_CORRECT_KEY: u32 = 10;
+pub const ZKP_CK_PROVE_OK: u32 = 0;
+pub const ZKP_CK_PROVE_SN_NOT_COPRIME: u32 = 1;
+pub const ZKP_CK_PROVE_Z_NOT_COPRIME: u32 = 2;
+pub const ZKP_CK_PROVE_RN_NOT_COPRIME: u32 = 3;
+pub const ZKP_CK_PROVE_E_MISMATCH: u32 = 4;
+pub const ZKP_CK_PROVE_BAD_KEY: u32 = 5;
 pub const ZKP_SEEDED_KIND_KEYGEN: u32 = 9;
 pub const ZKP_DEC_OK: u8 = 0;
 pub const ZKP_DEC_INVALID: u8 = 1;
@@ -186,6 +194,10 @@ extern "C" {
     pub fn zkp_dlog_statement_setup_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, N: *const u32, seed: *const u8, first_index: u64, out_g: *mut u32, out_ni: *mut u32, out_secret: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_paillier_open_batch(ctx: *mut zkp_ctx, n_bits: u32, count: u64, p: *const u32, q: *const u32, key_stride: u64, c: *const u32, out_m: *mut u32, out_r: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_correct_key_ni_prove_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, p: *const u32, q: *const u32, salt: *const u8, salt_len: u32, out_n: *mut u32, out_sigma: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_correct_key_challenge_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, rounds: u32, n: *const u32, n_stride: u64, s: *const u32, r: *const u32, out_sn: *mut u32, out_e: *mut u32, out_z: *mut u32, out_s_digest: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_correct_key_challenge_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, rounds: u32, n: *const u32, n_stride: u64, seed: *const u8, first_index: u64, out_sn: *mut u32, out_e: *mut u32, out_z: *mut u32, out_s_digest: *mut u32, out_status: *mut u8, flags: u32) -> i32;
+    pub fn zkp_correct_key_prove_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, rounds: u32, p: *const u32, q: *const u32, sn: *const u32, e: *const u32, z: *const u32, out_s_digest: *mut u32, out_error: *mut u8, flags: u32) -> i32;
+    pub fn zkp_correct_key_verify_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, rounds: u32, n: *const u32, n_stride: u64, seed: *const u8, first_index: u64, proof_s_digest: *const u32, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_probable_prime_batch(ctx: *mut zkp_ctx, bits: u32, count: u64, w: *const u32, rounds: u32, seed: *const u8, first_index: u64, out_verdict: *mut u8, flags: u32) -> i32;
     pub fn zkp_next_prime_batch(ctx: *mut zkp_ctx, bits: u32, count: u64, start: *const u32, rounds: u32, seed: *const u8, first_index: u64, out_prime: *mut u32, out_offset: *mut u32, out_status: *mut u8, flags: u32) -> i32;
     pub fn zkp_paillier_keygen_seeded_batch(ctx: *mut zkp_ctx, n_bits: u32, batch: u64, rounds: u32, seed: *const u8, first_index: u64, out_p: *mut u32, out_q: *mut u32, out_n: *mut u32, out_status: *mut u8, flags: u32) -> i32;

@@ -614,6 +614,82 @@ int32_t zkp_correct_key_ni_prove_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t b
                                        const uint8_t* salt, uint32_t salt_len, uint32_t* out_n /* nullable */, uint32_t* out_sigma,
                                        uint8_t* out_status /* nullable */, uint32_t flags);
 
+/* ------------------------------------------------------------------ interactive CorrectKey for whole batches of sessions
+ * CorrectKey::challenge / prove / verify (src/zkproofs/correct_key.rs:64-171).  A session has K rounds (`rounds`, 1 .. 256; the reference's
+ * STATISTICAL_ERROR_FACTOR is ZKP_CORRECT_KEY_ROUNDS), the same for every session of a call.  kw = n_bits/32, hw = n_bits/64, n_bits in
+ * {1024, 2048, 4096}; batch * K <= 2^24, batch == 0 is ZKP_OK.  Digests (e, s_digest) are 8 little-endian words: the number
+ * compute_digest returns (utils.rs:9-22).  ZKP_EINVAL, no byte touched: a null ctx, another n_bits, K outside 1 .. 256, batch * K above
+ * 2^24, an n_stride other than 0 or kw, a null required pointer, a flag bit other than ZKP_F_DEVICE_PTRS.
+ *
+ * zkp_correct_key_challenge_batch (correct_key.rs:64-102 with the s_i, r_i the reference draws at :67-70, :80-83 as inputs): for session b
+ * under n (n_stride 0: one key for the batch, or kw: one per session) and round i
+ *     sn_i = s_i^n mod n     rn_i = r_i^n mod n     e = compute_digest(n, sn.., rn..)     z_i = r_i s_i^e mod n     s_digest = compute_digest(s..)
+ * s, r [B][K][kw] are taken as given, any kw-word value (mod_pow reduces its base; s_digest hashes s as given).  out_sn, out_z [B][K][kw],
+ * out_e [B][8]: the Challenge; out_s_digest [B][8] (nullable): the VerificationAid.  The exponentiations are zkp_modexp_batch's ladder at
+ * mod_bits = max(n_bits, 2048): 2 K B rows with the n_bits-bit exponent n and K B rows with the 256-bit exponent e, under one shared
+ * modulus (n_stride 0) or per-row moduli; the call goes, whole, to the engine zkp_modexp_batch would choose for the larger launch.
+ * DOMAIN (rule of THIS library).  out_status[b] (nullable) is 0, or ZKP_VERDICT_MALFORMED (2) for an n that is even (zero included) or 1:
+ * every output of that session is zero, the other sessions are unaffected.
+ *
+ * zkp_correct_key_challenge_seeded_batch: what the reference's challenge takes.  s and r are expanded ON THE DEVICE from a 32-byte seed by
+ * the construction of the nonce streams above, unchanged (state words 13, 14 = index = first_index + b; word 15 = 0x80000000 | kind << 20 |
+ * slot << 4 | field), with one more kind (tests/ck_inter_model.py restates it):
+ *     kind                 slot                   field  value      draw
+ *     10 CorrectKey        i, i < K               0      s_i        sample_below(n)
+ *     10 CorrectKey        i, i < K               1      r_i        sample_below(n)
+ * sample_below is the rule above word for word, at most 128 attempts; a round does not depend on K.  A sampler failure (n == 0, 128
+ * rejected attempts) makes the session ZKP_VERDICT_MALFORMED with zero outputs, as a key outside the domain does.  A call split with
+ * first_index + lo equals the one call.  zkp_nonce_sample_batch does not serve this kind.
+ *
+ * zkp_correct_key_verify_seeded_batch (correct_key.rs:164-171 without a stored aid): regenerates s of (seed, first_index + b) under n,
+ * hashes it and compares with proof_s_digest[b].  out_verdict[b]: ZKP_VERDICT_ACCEPT, ZKP_VERDICT_REJECT, or ZKP_VERDICT_MALFORMED where
+ * the seeded challenge is.  The sampler and the hash only: no ladder, the call runs on the context that receives it.  The aid never leaves
+ * the device: the verifier keeps 32 bytes between its messages.
+ *
+ * SECURITY CONTRACT of the three.  s and s_digest are the verifier's secret until the proof has arrived: a prover who learns either answers
+ * without the key.  The seed is worth both.  A (seed, index) pair belongs to ONE session: under another key it repeats s and r.  Draw the
+ * seed from the operating system and wipe it after the verify.  `seed` is a HOST pointer in both memory modes.  The staged seed, every
+ * device copy of s and r (those reduced under n included), s^e, the regenerated digest and the staged out_s_digest of a host-pointer call
+ * are zeroed on the stream before the call's blocks are given back, on error returns too; zkp_diag_witness_residue then reads 0.  With
+ * ZKP_F_DEVICE_PTRS the caller's s, r and out_s_digest are the caller's to wipe.
+ *
+ * zkp_correct_key_prove_batch (correct_key.rs:104-162): for key b = (p, q) [B][hw] and the challenge (sn [B][K][kw], e [B][8], z [B][K][kw])
+ *     n = p q
+ *     rn_i mod p = (z_i mod p)^(n mod (p-1)) (sn_i mod p)^((p-1) - e mod (p-1)) mod p     (q alike)      rn_i = CRT(rn_p, rn_q)
+ *     root_i     = CRT((sn_i mod p)^(d_p) mod p, (sn_i mod q)^(d_q) mod q)                d_p = q^-1 mod (p-1)   (upstream's extract_nroot)
+ *     out_s_digest[b] = compute_digest(root..)
+ * six rows per round of zkp_modexp_batch's ladder at mod_bits = 2048 (= max(n_bits/2, 2048)) with n_bits/2-bit exponents, and the call
+ * goes, whole, to the engine that call would go to for the same (6 K B rows, mod_bits).  phi, phi - e mod phi and n^-1 mod phi are never
+ * formed; the rest is csrc/kernels_ck_inter.hpp and the key kernels of csrc/kernels_paillier_dec.hpp.  sn and z are any kw-word values.
+ * out_error[b] (nullable): 0, or the reference's first error in its order — the variants of CorrectKeyProveError in declaration order,
+ * ZKP_CK_PROVE_* 1 .. 4 — or ZKP_CK_PROVE_BAD_KEY (5, rule of THIS library: the key domain of zkp_paillier_open_batch, tested first).  On
+ * any non-zero code out_s_digest[b] is zero; the other sessions are unaffected.  No primality test is made: for prime p and q the values are
+ * the reference's, for other factors they are what the formulas above give.
+ * SECURITY CONTRACT: that of zkp_correct_key_ni_prove_batch.  In addition the residues of sn and z, the three exponent pairs, the ladder's
+ * rows, constants records and window tables and the roots are registered secret and zeroed before the call's blocks are given back, on
+ * error returns too.  n, rn, the error codes and the digest are public. */
+#define ZKP_CORRECT_KEY_ROUNDS 40 /* src/zkproofs/correct_key.rs:26 */
+#define ZKP_SEEDED_KIND_CORRECT_KEY 10u
+#define ZKP_CK_PROVE_OK 0
+#define ZKP_CK_PROVE_SN_NOT_COPRIME 1 /* SniNotCoprimeWithN */
+#define ZKP_CK_PROVE_Z_NOT_COPRIME 2  /* ZiNotCoprimeWithN */
+#define ZKP_CK_PROVE_RN_NOT_COPRIME 3 /* RniNotCoprimeWithN */
+#define ZKP_CK_PROVE_E_MISMATCH 4     /* EWasntComputedCorrectly */
+#define ZKP_CK_PROVE_BAD_KEY 5
+int32_t zkp_correct_key_challenge_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, uint32_t rounds, const uint32_t* n, uint64_t n_stride,
+                                        const uint32_t* s, const uint32_t* r, uint32_t* out_sn, uint32_t* out_e, uint32_t* out_z,
+                                        uint32_t* out_s_digest /* nullable */, uint8_t* out_status /* nullable */, uint32_t flags);
+int32_t zkp_correct_key_challenge_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, uint32_t rounds, const uint32_t* n,
+                                               uint64_t n_stride, const uint8_t* seed, uint64_t first_index, uint32_t* out_sn, uint32_t* out_e,
+                                               uint32_t* out_z, uint32_t* out_s_digest /* nullable */, uint8_t* out_status /* nullable */,
+                                               uint32_t flags);
+int32_t zkp_correct_key_prove_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, uint32_t rounds, const uint32_t* p, const uint32_t* q,
+                                    const uint32_t* sn, const uint32_t* e, const uint32_t* z, uint32_t* out_s_digest,
+                                    uint8_t* out_error /* nullable */, uint32_t flags);
+int32_t zkp_correct_key_verify_seeded_batch(zkp_ctx* ctx, uint32_t n_bits, uint64_t batch, uint32_t rounds, const uint32_t* n,
+                                            uint64_t n_stride, const uint8_t* seed, uint64_t first_index, const uint32_t* proof_s_digest,
+                                            uint8_t* out_verdict, uint32_t flags);
+
 /* ------------------------------------------------------------------ probable primes, next prime, seeded Paillier key generation
  * Three layers of one piece of code (csrc/kernels_prime.hpp).  bits in {512, 1024, 2048} is the width of a value, pw = bits/32 words; these
  * are the factor widths of n_bits in {1024, 2048, 4096}.  The rule below is THIS library's published rule (tests/prime_model.py restates

@@ -187,6 +187,12 @@ EXPORTS = {
                                             C.c_void_p, C.c_uint32]),
     "zkp_correct_key_ni_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_uint32]),
+    "zkp_correct_key_challenge_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64] + [C.c_void_p] * 7 + [C.c_uint32]),
+    "zkp_correct_key_challenge_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64] +
+                                               [C.c_void_p] * 5 + [C.c_uint32]),
+    "zkp_correct_key_prove_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32] + [C.c_void_p] * 7 + [C.c_uint32]),
+    "zkp_correct_key_verify_seeded_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64,
+                                                        C.c_void_p, C.c_void_p, C.c_uint32]),
     "zkp_probable_prime_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "zkp_next_prime_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint32]),
@@ -219,6 +225,9 @@ SEEDED_KIND_ZERO, SEEDED_KIND_CIPHERTEXT, SEEDED_KIND_CORRECT_MESSAGE, SEEDED_KI
 SEEDED_KIND_VERLIN, SEEDED_KIND_MUL = 5, 6
 SEEDED_KIND_RANGE_COMMIT = 7
 SEEDED_KIND_DLOG_SETUP = 8
+SEEDED_KIND_CORRECT_KEY = 10
+CORRECT_KEY_ROUNDS = 40
+CK_PROVE_BAD_KEY = 5          # out_error of correct_key_prove: 1 .. 4 are the reference's CorrectKeyProveError variants
 _lib = None
 
 
@@ -577,6 +586,32 @@ class Context:
         the domain (its n and roots zero).  numpy arrays, or torch cuda tensors (all of them); the salt is host bytes in both modes."""
         self.check(self.lib.zkp_correct_key_ni_prove_batch(self.h, n_bits, batch, ptr(p), ptr(q), salt if salt else None, len(salt), ptr(out_n),
                                                            ptr(out_sigma), ptr(out_status), self._flags(p, q, out_n, out_sigma, out_status)))
+
+    # ---- the interactive CorrectKey for whole batches of sessions: K rounds each; digests are [batch][8] little-endian words
+    def correct_key_challenge(self, n_bits, batch, K, n, n_stride, s, r, out_sn, out_e, out_z, out_s_digest=None, out_status=None):
+        """zkp_correct_key_challenge_batch: sn = s^n, e = H(n, sn, r^n), z = r s^e mod n, s_digest = H(s) from the caller's s, r [batch][K][kw];
+        out_status (or None): 2 where n is even or 1 (that session's outputs zero)."""
+        self.check(self.lib.zkp_correct_key_challenge_batch(self.h, n_bits, batch, K, ptr(n), n_stride, ptr(s), ptr(r), ptr(out_sn), ptr(out_e), ptr(out_z),
+                                                            ptr(out_s_digest), ptr(out_status),
+                                                            self._flags(n, s, r, out_sn, out_e, out_z, out_s_digest, out_status)))
+
+    def correct_key_challenge_seeded(self, n_bits, batch, K, n, n_stride, seed: bytes, first_index: int, out_sn, out_e, out_z, out_s_digest=None,
+                                     out_status=None):
+        """zkp_correct_key_challenge_seeded_batch: the same with s, r expanded on the GPU from (seed, first_index + b); the seed is host bytes"""
+        self.check(self.lib.zkp_correct_key_challenge_seeded_batch(self.h, n_bits, batch, K, ptr(n), n_stride, _seed(seed), first_index, ptr(out_sn),
+                                                                   ptr(out_e), ptr(out_z), ptr(out_s_digest), ptr(out_status),
+                                                                   self._flags(n, out_sn, out_e, out_z, out_s_digest, out_status)))
+
+    def correct_key_prove(self, n_bits, batch, K, p, q, sn, e, z, out_s_digest, out_error=None):
+        """zkp_correct_key_prove_batch: one answer per key (p, q) [batch][n_bits / 64]; out_error (or None): 0, the reference's error 1 .. 4,
+        or 5 for a key outside the domain (the digest is zero then)."""
+        self.check(self.lib.zkp_correct_key_prove_batch(self.h, n_bits, batch, K, ptr(p), ptr(q), ptr(sn), ptr(e), ptr(z), ptr(out_s_digest),
+                                                        ptr(out_error), self._flags(p, q, sn, e, z, out_s_digest, out_error)))
+
+    def correct_key_verify_seeded(self, n_bits, batch, K, n, n_stride, seed: bytes, first_index: int, proof_s_digest, out_verdict):
+        """zkp_correct_key_verify_seeded_batch: the verdict from the s of (seed, first_index + b), regenerated and hashed on the GPU"""
+        self.check(self.lib.zkp_correct_key_verify_seeded_batch(self.h, n_bits, batch, K, ptr(n), n_stride, _seed(seed), first_index, ptr(proof_s_digest),
+                                                                ptr(out_verdict), self._flags(n, proof_s_digest, out_verdict)))
 
     def probable_prime(self, bits, count, w, rounds, seed, first_index, out_verdict):
         """zkp_probable_prime_batch: out_verdict[i] = is_probable_prime(w[i]) by the rule of include/zkp_hip.h (trial division by the odd

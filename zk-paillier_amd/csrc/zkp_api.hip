@@ -29,6 +29,7 @@
 #include "kernels_jacobi.hpp"
 #include "kernels_paillier_dec.hpp"
 #include "kernels_ck_prove.hpp"
+#include "kernels_ck_inter.hpp"
 #include "kernels_prime.hpp"
 #include "route_plan.hpp"             // every size-based decision of this file and of zkp_api_proofs.inc
 #if ZKP_W == 36 || ZKP_W == 18 || ZKP_W == 9
@@ -190,7 +191,8 @@ static int32_t zkp_caught(zkp_ctx* c, int32_t st, const char* what) noexcept {
   X(zkp_diag_basen) X(zkp_diag_basen_last) X(zkp_diag_set_enc_form) X(zkp_diag_set_r2l) X(zkp_diag_r2l_last) X(zkp_diag_set_r2l_lanes) X(zkp_diag_r2l_lanes_last) X(zkp_diag_set_key_cache) X(zkp_diag_key_cache_state) \
   X(zkp_diag_set_fuse_hash) X(zkp_diag_last_fused_hash)                                                                            \
   X(zkp_json_sigma_batch) X(zkp_json_write_sigma_batch) X(zkp_sigma_verify_json_batch)                                         \
-  X(zkp_paillier_open_batch) X(zkp_diag_witness_residue) X(zkp_correct_key_ni_prove_batch)
+  X(zkp_paillier_open_batch) X(zkp_diag_witness_residue) X(zkp_correct_key_ni_prove_batch)                                        \
+  X(zkp_correct_key_challenge_batch) X(zkp_correct_key_challenge_seeded_batch) X(zkp_correct_key_prove_batch)
 
 struct LatEngine {
   void* handle = nullptr;
@@ -1386,6 +1388,7 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
 #include "zkp_api_jacobi.inc"
 #include "zkp_api_paillier_dec.inc"
 #include "zkp_api_ck_prove.inc"
+#include "zkp_api_ck_inter.inc"
 #include "zkp_api_prime.inc"
 #include "zkp_api_serde.inc"
 #ifndef ZKP_SECONDARY_ENGINE

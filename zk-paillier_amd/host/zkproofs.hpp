@@ -1129,6 +1129,135 @@ struct CorrectKey {
   }
   // :164-171
   static Result verify(const CorrectKeyProof& proof, const VerificationAid& va) { return Result(proof.s_digest == va.s_digest); }
+
+  // ---- whole batches of sessions, one GPU call per step and kernel width (include/zkp_hip.h: zkp_correct_key_challenge_seeded_batch,
+  // zkp_correct_key_prove_batch, zkp_correct_key_verify_seeded_batch).  The verifier keeps a VerifierSeed between its messages instead of
+  // an aid per session: session b of a call is (seed, first_index + b), its s and r are expanded ON THE GPU, and verify_batch_seeded
+  // regenerates s there.  s and its digest are the verifier's secret until the proof has arrived; a (seed, index) belongs to ONE session.
+  struct VerifierSeed {
+    uint8_t bytes[32];
+    VerifierSeed() { std::memset(bytes, 0, sizeof bytes); }
+    static VerifierSeed fresh() { VerifierSeed s; detail::ChaChaRng::os_random(s.bytes, sizeof s.bytes); return s; }
+    ~VerifierSeed() { detail::ChaChaRng::wipe(bytes, sizeof bytes); }
+  };
+  // calls f(lo, hi, nb) for every run [lo, hi) of consecutive keys of one kernel width (a batch of one width: one run, one GPU call)
+  template <class F> static void width_runs(const std::vector<EncryptionKey>& keys, const char* who, F&& f) {
+    for (const EncryptionKey& k : keys)
+      if (k.n.is_negative() || k.n.is_zero() || k.n.bit_length() > 4096) throw std::invalid_argument(std::string(who) + ": a key is a positive integer of at most 4096 bits");
+    for (size_t lo = 0; lo < keys.size();) {
+      const uint32_t nb = width_for(keys[lo].n);
+      size_t hi = lo + 1;
+      while (hi < keys.size() && width_for(keys[hi].n) == nb) hi++;
+      f(lo, hi, nb);
+      lo = hi;
+    }
+  }
+  // :64-102 for one session per key; aids (nullable) receives the VerificationAids.  A key the call marks ZKP_VERDICT_MALFORMED (even, or no
+  // s below n in 128 attempts) is a Panic naming the session.
+  static std::vector<Challenge> challenge_batch_seeded(const std::vector<EncryptionKey>& keys, const VerifierSeed& seed, uint64_t first_index,
+                                                       std::vector<VerificationAid>* aids, size_t K = STATISTICAL_ERROR_FACTOR) {
+    Engine& e = Engine::instance();
+    std::vector<Challenge> out(keys.size());
+    if (aids) aids->assign(keys.size(), VerificationAid{});
+    width_runs(keys, "CorrectKey::challenge_batch_seeded", [&](size_t lo, size_t hi, uint32_t nb) {
+      const size_t B = hi - lo, kw = nb / 32;
+      std::vector<uint32_t> n(B * kw), sn(B * K * kw), z(B * K * kw), ee(B * 8);
+      RawBuf<uint32_t> sd(aids ? B * 8 : 0, true);                                            // (secret until the proof has arrived: wiped on release)
+      std::vector<uint8_t> st(B, 9);
+      for (size_t b = 0; b < B; b++) keys[lo + b].n.to_limbs(&n[b * kw], kw);
+      e.check(zkp_correct_key_challenge_seeded_batch(e.ctx(), nb, B, (uint32_t)K, n.data(), kw, seed.bytes, first_index + lo, sn.data(), ee.data(), z.data(),
+                                                     aids ? sd.data() : nullptr, st.data(), 0), "zkp_correct_key_challenge_seeded_batch");
+      for (size_t b = 0; b < B; b++) {
+        if (st[b] != 0) throw Panic("CorrectKey::challenge_batch_seeded: session " + std::to_string(lo + b) + ": the key is outside the domain (ZKP_VERDICT_MALFORMED)");
+        Challenge& c = out[lo + b];
+        for (size_t i = 0; i < K; i++) { c.sn.push_back(BigInt::from_limbs(&sn[(b * K + i) * kw], kw)); c.z.push_back(BigInt::from_limbs(&z[(b * K + i) * kw], kw)); }
+        c.e = BigInt::from_limbs(&ee[b * 8], 8);
+        if (aids) (*aids)[lo + b].s_digest = BigInt::from_limbs(&sd[b * 8], 8);
+      }
+    });
+    return out;
+  }
+  static std::vector<Challenge> challenge_batch_seeded(const std::vector<EncryptionKey>& keys, const VerifierSeed& seed, uint64_t first_index = 0) {
+    return challenge_batch_seeded(keys, seed, first_index, nullptr);
+  }
+  static std::vector<Challenge> challenge_batch_seeded(const std::vector<EncryptionKey>& keys, const VerifierSeed& seed, uint64_t first_index,
+                                                       std::vector<VerificationAid>& aids) {
+    return challenge_batch_seeded(keys, seed, first_index, &aids);
+  }
+  // :164-171 against the s of (seed, first_index + b), regenerated and hashed on the GPU: one Result per session.  A digest that is no
+  // 256-bit number equals no digest (Err); a session whose seeded challenge panics, panics here.
+  static std::vector<Result> verify_batch_seeded(const std::vector<EncryptionKey>& keys, const VerifierSeed& seed, uint64_t first_index,
+                                                 const std::vector<CorrectKeyProof>& proofs, size_t K = STATISTICAL_ERROR_FACTOR) {
+    Engine& e = Engine::instance();
+    if (proofs.size() != keys.size()) throw std::invalid_argument("CorrectKey::verify_batch_seeded: one proof per key");
+    std::vector<Result> out(keys.size(), Result(false));
+    width_runs(keys, "CorrectKey::verify_batch_seeded", [&](size_t lo, size_t hi, uint32_t nb) {
+      const size_t B = hi - lo, kw = nb / 32;
+      std::vector<uint32_t> n(B * kw), pd(B * 8, 0);
+      std::vector<uint8_t> v(B, 9), fits(B, 0);
+      for (size_t b = 0; b < B; b++) {
+        keys[lo + b].n.to_limbs(&n[b * kw], kw);
+        const BigInt& d = proofs[lo + b].s_digest;
+        if ((fits[b] = !d.is_negative() && d.fits_limbs(8))) d.to_limbs(&pd[b * 8], 8);
+      }
+      e.check(zkp_correct_key_verify_seeded_batch(e.ctx(), nb, B, (uint32_t)K, n.data(), kw, seed.bytes, first_index + lo, pd.data(), v.data(), 0),
+              "zkp_correct_key_verify_seeded_batch");
+      for (size_t b = 0; b < B; b++)
+        out[lo + b] = v[b] == ZKP_VERDICT_MALFORMED ? Result::panicked("CorrectKey::challenge: the key is outside the domain") : Result(fits[b] && v[b] == ZKP_VERDICT_ACCEPT);
+    });
+    return out;
+  }
+  // :104-162 for one (key, challenge) pair per session in ONE zkp_correct_key_prove_batch per kernel width (grouped as
+  // NiCorrectKeyProof::proof_batch groups them): n, the residues, rn and the n-th roots — CRT under p and q — are computed on the GPU; phi,
+  // phi - e mod phi and n^-1 mod phi are never formed, and the staging that carries p and q is wiped on release.  A session the call's shape
+  // cannot hold — |sn| != |z|, a number of rounds other than the batch's (that of its first session), e negative or >= 2^256, a value
+  // negative or wider than the key's width, a factor that is not positive or wider than 2048 bits — and a key the call reports as outside
+  // its domain goes through prove(), the single-session path, unchanged.
+  static std::vector<ProveResult> prove_batch(const std::vector<const DecryptionKey*>& keys, const std::vector<Challenge>& challenges) {
+    Engine& e = Engine::instance();
+    if (keys.size() != challenges.size()) throw std::invalid_argument("CorrectKey::prove_batch: one challenge per key");
+    const size_t N = keys.size();
+    std::vector<ProveResult> out(N, ProveResult{false, CorrectKeyProof{}, CorrectKeyProveError::EWasntComputedCorrectly});
+    const size_t K = N ? challenges[0].sn.size() : 0;
+    std::vector<uint32_t> width(N, 0);                                                        // 0: the single-session path
+    for (size_t k = 0; k < N; k++) {
+      const DecryptionKey& dk = *keys[k];
+      const Challenge& c = challenges[k];
+      if (K < 1 || K > 256 || c.sn.size() != K || c.z.size() != K || c.e.is_negative() || !c.e.fits_limbs(8)) continue;
+      if (dk.p.is_negative() || dk.q.is_negative() || dk.p.is_zero() || dk.q.is_zero() || std::max(dk.p.bit_length(), dk.q.bit_length()) > 2048) continue;
+      uint32_t nb = width_for(dk.p * dk.q);
+      while (std::max(dk.p.bit_length(), dk.q.bit_length()) > nb / 2) nb *= 2;
+      bool fits = true;
+      for (size_t i = 0; i < K; i++) fits = fits && !c.sn[i].is_negative() && c.sn[i].fits_limbs(nb / 32) && !c.z[i].is_negative() && c.z[i].fits_limbs(nb / 32);
+      if (fits) width[k] = nb;
+    }
+    for (uint32_t nb : {1024u, 2048u, 4096u}) {
+      const uint32_t kw = nb / 32, hw = nb / 64;
+      std::vector<size_t> idx;
+      for (size_t k = 0; k < N; k++) if (width[k] == nb) idx.push_back(k);
+      if (idx.empty()) continue;
+      const size_t B = idx.size();
+      RawBuf<uint32_t> p(B * hw, true), q(B * hw, true);                                      // (secret: wiped on release)
+      std::vector<uint32_t> sn(B * K * kw), z(B * K * kw), ee(B * 8), sd(B * 8);
+      std::vector<uint8_t> err(B, 9);
+      for (size_t j = 0; j < B; j++) {
+        const Challenge& c = challenges[idx[j]];
+        keys[idx[j]]->p.to_limbs(&p[j * hw], hw); keys[idx[j]]->q.to_limbs(&q[j * hw], hw);
+        for (size_t i = 0; i < K; i++) { c.sn[i].to_limbs(&sn[(j * K + i) * kw], kw); c.z[i].to_limbs(&z[(j * K + i) * kw], kw); }
+        c.e.to_limbs(&ee[j * 8], 8);
+      }
+      const int32_t rc = zkp_correct_key_prove_batch(e.ctx(), nb, B, (uint32_t)K, p.data(), q.data(), sn.data(), ee.data(), z.data(), sd.data(), err.data(), 0);
+      p.wipe_now(); q.wipe_now();
+      e.check(rc, "zkp_correct_key_prove_batch");
+      for (size_t j = 0; j < B; j++) {
+        if (err[j] == ZKP_CK_PROVE_BAD_KEY) width[idx[j]] = 0;
+        else if (err[j] == ZKP_CK_PROVE_OK) out[idx[j]] = ProveResult{true, CorrectKeyProof{BigInt::from_limbs(&sd[j * 8], 8)}, CorrectKeyProveError::EWasntComputedCorrectly};
+        else out[idx[j]].err = (CorrectKeyProveError)(err[j] - 1);
+      }
+    }
+    for (size_t k = 0; k < N; k++) if (width[k] == 0) out[k] = prove(*keys[k], challenges[k]);
+    return out;
+  }
 };
 
 // ------------------------------------------------------------------ seeded proving of the sigma proofs (zkp_*_prove_seeded_batch)
