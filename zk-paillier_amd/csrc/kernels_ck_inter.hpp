@@ -108,8 +108,8 @@ __global__ void __launch_bounds__(256) k_cki_verdict(const uint32_t* __restrict_
 
 // ---- prove: split, one round per pair of lanes (one lane per factor F).  Rows 6 j + 2 t + side of the ladder, zero-padded to the row width:
 //   t = 0: (z mod F)^(n mod (F-1))      t = 1: (sn mod F)^((F-1) - e mod (F-1))      t = 2: (sn mod F)^(d_F)
-// n mod (F-1) and e mod (F-1) are real reductions: no primality or size test is made on F.  A round of a bad key gets bases and exponents zero
-// under the modulus 3, as k_ck_prove_split's rows do.
+// n mod (F-1) and e mod (F-1) are real reductions: no primality or size test is made on F.  A round of a bad key gets three null rows
+// (pd_row_null).
 constexpr int CKI_ROWS = 6;                                    // half-width rows per round
 struct CkiProveSplitArgs {
   const uint32_t* sn; const uint32_t* z;                       // [items][kw], any values
@@ -133,11 +133,7 @@ __global__ void __launch_bounds__(64) k_cki_prove_split(CkiProveSplitArgs a) {
   const int side = (int)(gid & 1);
   const uint64_t r0 = CKI_ROWS * item + side;
   if (a.kst[key] != 0) {
-    for (int t = 0; t < 3; t++) {
-      uint32_t* m = a.mods + (r0 + 2 * t) * (uint64_t)rw; uint32_t* b = a.base + (r0 + 2 * t) * (uint64_t)rw; uint32_t* e = a.exp + (r0 + 2 * t) * (uint64_t)hw;
-      for (int w = 0; w < rw; w++) { m[w] = w == 0 ? 3u : 0u; b[w] = 0u; }
-      for (int w = 0; w < hw; w++) e[w] = 0u;
-    }
+    for (int t = 0; t < 3; t++) pd_row_null(a.mods + (r0 + 2 * t) * (uint64_t)rw, a.base + (r0 + 2 * t) * (uint64_t)rw, a.exp + (r0 + 2 * t) * (uint64_t)hw, rw, hw);
     return;
   }
   uint32_t* x = pd_lds + threadIdx.x;                          // kw + 1 words
@@ -153,7 +149,7 @@ __global__ void __launch_bounds__(64) k_cki_prove_split(CkiProveSplitArgs a) {
     const uint32_t* V = (t == 0 ? a.z : a.sn) + item * (uint64_t)kw;
     for (int w = 0; w < kw; w++) x[w * S] = V[w];
     pd_mod(x, kw, F, 1, hw, mn, S);
-    for (int w = 0; w < rw; w++) { m[w] = w < hw ? F[w] : 0u; b[w] = w < hw ? x[w * S] : 0u; }
+    pd_row_put(m, b, rw, F, hw, x, S);
     // the exponent
     if (t == 0) {
       const uint32_t* N = a.n + key * (uint64_t)kw;
@@ -170,9 +166,7 @@ __global__ void __launch_bounds__(64) k_cki_prove_split(CkiProveSplitArgs a) {
         e[w] = (uint32_t)d;
         borrow = (uint32_t)(d >> 63);
       }
-    } else {
-      for (int w = 0; w < hw; w++) e[w] = D[w];
-    }
+    } else pd_exp_put(e, D, hw);
   }
 }
 
@@ -185,7 +179,6 @@ struct CkiProveFinishArgs {
   uint32_t* rn; uint32_t* root;                                // [items][kw]
   uint64_t items; uint32_t K; int hw, rw;
 };
-constexpr size_t cki_prove_finish_lds_words_per_lane(int hw) { return 6 * (size_t)hw + 1; }
 
 __global__ void __launch_bounds__(64) k_cki_prove_finish(CkiProveFinishArgs a) {
   extern __shared__ __align__(16) uint32_t pd_lds[];
@@ -203,24 +196,17 @@ __global__ void __launch_bounds__(64) k_cki_prove_finish(CkiProveFinishArgs a) {
   const uint32_t* Q = a.q + key * (uint64_t)hw;
   const uint32_t* pinv = a.pinv + key * a.pinv_stride;
   const uint32_t* R = a.rows + CKI_ROWS * item * (uint64_t)rw;
-  uint32_t* x = pd_lds + threadIdx.x;                          // kw + 1 words
-  uint32_t* mn = x + (size_t)(kw + 1) * S;                     // hw words
-  uint32_t* d = mn + (size_t)hw * S;                           // hw words
-  uint32_t* vp = d + (size_t)hw * S;                           // hw words
-  uint32_t* vq = vp + (size_t)hw * S;                          // hw words
+  const PdCrtLds l(pd_lds, hw, S);
   for (int side = 0; side < 2; side++) {                       // the product of rows t = 0 and t = 1 under this side's factor
-    uint32_t* v = side ? vq : vp;
+    uint32_t* v = side ? l.vq : l.vp;
     for (int w = 0; w < hw; w++) v[w * S] = R[(uint64_t)side * rw + w];
-    pd_mul(x, v, hw, R + (uint64_t)(2 + side) * rw, 1, hw, S);
-    pd_mod(x, kw, side ? Q : P, 1, hw, mn, S);
-    for (int w = 0; w < hw; w++) v[w * S] = x[w * S];
+    pd_mul(l.x, v, hw, R + (uint64_t)(2 + side) * rw, 1, hw, S);
+    pd_mod(l.x, kw, side ? Q : P, 1, hw, l.mn, S);
+    for (int w = 0; w < hw; w++) v[w * S] = l.x[w * S];
   }
-  pd_crt(orn, true, vp, vq, P, Q, pinv, x, mn, d, hw, S);
-  for (int side = 0; side < 2; side++) {
-    uint32_t* v = side ? vq : vp;
-    for (int w = 0; w < hw; w++) v[w * S] = R[(uint64_t)(4 + side) * rw + w];
-  }
-  pd_crt(ort, true, vp, vq, P, Q, pinv, x, mn, d, hw, S);
+  pd_crt(orn, true, l, P, Q, pinv, hw, S);
+  pd_load_pair(l.vp, l.vq, R + 4 * (uint64_t)rw, rw, hw, S);
+  pd_crt(ort, true, l, P, Q, pinv, hw, S);
 }
 
 // ---- gcd(n, v) != 1 for the 3 K B values sn (class 0), z (class 1) and rn (class 2), one per lane: share[class * items + item].

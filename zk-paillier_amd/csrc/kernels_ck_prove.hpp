@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(64) k_ck_prove_n(const uint32_t* __restrict__ 
 }
 
 // ---- split, one root per pair of lanes (one lane per factor): rows 2 j and 2 j + 1 of the ladder are item j under p and q, zero-padded to
-// the row width.  A root of a bad key gets base and exponent zero under the modulus 3, as k_pdec_split's rows do.
+// the row width.  A root of a bad key gets the null row (pd_row_null).
 struct CkProveSplitArgs {
   const uint32_t* mgf;                                         // [items][kw + 8]   what the hash kernels wrote
   const uint32_t* p; const uint32_t* q;                        // [nkeys][hw]
@@ -59,16 +59,12 @@ __global__ void __launch_bounds__(64) k_ck_prove_split(CkProveSplitArgs a) {
   const uint32_t* F = (side ? a.q : a.p) + key * (uint64_t)hw;
   const uint32_t* D = (side ? a.dq : a.dp) + key * (uint64_t)hw;
   uint32_t* m = a.mods + gid * (uint64_t)rw; uint32_t* b = a.base + gid * (uint64_t)rw; uint32_t* e = a.exp + gid * (uint64_t)hw;
-  if (a.kst[key] != 0) {
-    for (int w = 0; w < rw; w++) { m[w] = w == 0 ? 3u : 0u; b[w] = 0u; }
-    for (int w = 0; w < hw; w++) e[w] = 0u;
-    return;
-  }
+  if (a.kst[key] != 0) { pd_row_null(m, b, e, rw, hw); return; }
   const uint32_t* R = a.mgf + item * (uint64_t)mw;
   for (int w = 0; w < mw; w++) x[w * S] = R[w];
   pd_mod(x, mw, F, 1, hw, mn, S);
-  for (int w = 0; w < rw; w++) { m[w] = w < hw ? F[w] : 0u; b[w] = w < hw ? x[w * S] : 0u; }
-  for (int w = 0; w < hw; w++) e[w] = D[w];
+  pd_row_put(m, b, rw, F, hw, x, S);
+  pd_exp_put(e, D, hw);
 }
 
 // ---- finish, one root per lane: the recombination (pd_crt); the lane of a key's root 0 writes the key's status and zeroes the n of a bad key.
@@ -82,7 +78,6 @@ struct CkProveFinishArgs {
   uint8_t* status;                                             // [nkeys]
   uint64_t items; int hw, rw;
 };
-constexpr size_t ck_prove_finish_lds_words_per_lane(int hw) { return 6 * (size_t)hw + 1; }
 
 __global__ void __launch_bounds__(64) k_ck_prove_finish(CkProveFinishArgs a) {
   extern __shared__ __align__(16) uint32_t pd_lds[];
@@ -105,17 +100,9 @@ __global__ void __launch_bounds__(64) k_ck_prove_finish(CkProveFinishArgs a) {
   const uint32_t* P = a.p + key * (uint64_t)hw;
   const uint32_t* Q = a.q + key * (uint64_t)hw;
   const uint32_t* pinv = a.pinv + key * a.pinv_stride;
-  uint32_t* x = pd_lds + threadIdx.x;                          // kw + 1 words
-  uint32_t* mn = x + (size_t)(kw + 1) * S;                     // hw words
-  uint32_t* d = mn + (size_t)hw * S;                           // hw words
-  uint32_t* vp = d + (size_t)hw * S;                           // hw words: s_p
-  uint32_t* vq = vp + (size_t)hw * S;                          // hw words: s_q
-  for (int side = 0; side < 2; side++) {
-    const uint32_t* X = a.rows + (2 * item + side) * (uint64_t)rw;
-    uint32_t* v = side ? vq : vp;
-    for (int w = 0; w < hw; w++) v[w * S] = X[w];
-  }
-  pd_crt(os, true, vp, vq, P, Q, pinv, x, mn, d, hw, S);
+  const PdCrtLds l(pd_lds, hw, S);                             // vp, vq: s_p, s_q
+  pd_load_pair(l.vp, l.vq, a.rows + 2 * item * (uint64_t)rw, rw, hw, S);
+  pd_crt(os, true, l, P, Q, pinv, hw, S);
 }
 
 }  // namespace zkp

@@ -17,6 +17,8 @@
 //  * the inverse modulo the EVEN p - 1: with M = p - 1 and y = M^-1 mod q (odd modulus: k_modinv), M y = 1 + t q, so t = (M y - 1) / q is an
 //    exact division, and -t q = 1 mod M: d_p = M - t (0 < t < M, as 0 < y < q).
 // h_q needs no inverse of its own: (q - (p mod q))^-1 = -(p^-1) = q - pinv mod q.
+// The split and finish kernels of kernels_ck_prove.hpp and kernels_ck_inter.hpp compute other rows with the same pieces: the ladder-row
+// writers (pd_row_null, pd_row_put, pd_exp_put), pd_load_pair, and the recombination pd_crt over its LDS carve PdCrtLds.
 //
 // Data layout: as kernels_gcd.hpp — one value per lane, operands in thread-interleaved LDS (word w of this lane at x[w * S]).  Trip counts
 // depend on the operands' lengths only, but nothing here is claimed to run in constant time (the quotient correction and the add-back are
@@ -185,6 +187,66 @@ __device__ __forceinline__ bool pd_odd_ge3(const uint32_t* v, int n) {
   return (v[0] & 1u) && big;
 }
 
+// ---- what the split and finish kernels of the calls that hold p and q share (kernels_ck_prove.hpp, kernels_ck_inter.hpp)
+// The ladder's row of an item under a bad key: base and exponent zero under the modulus 3 (the ladder refuses a modulus below 2 bits or an
+// even one for the whole call).  m, b: rw words, e: hw words.
+__device__ __forceinline__ void pd_row_null(uint32_t* m, uint32_t* b, uint32_t* e, int rw, int hw) {
+  for (int w = 0; w < rw; w++) { m[w] = w == 0 ? 3u : 0u; b[w] = 0u; }
+  for (int w = 0; w < hw; w++) e[w] = 0u;
+}
+// m <- the factor F, b <- the reduced base x (LDS): nf words each, zero-padded to the row width rw
+__device__ __forceinline__ void pd_row_put(uint32_t* m, uint32_t* b, int rw, const uint32_t* F, int nf, const uint32_t* x, int S) {
+  for (int w = 0; w < rw; w++) { m[w] = w < nf ? F[w] : 0u; b[w] = w < nf ? x[w * S] : 0u; }
+}
+__device__ __forceinline__ void pd_exp_put(uint32_t* e, const uint32_t* src, int hw) {
+  for (int w = 0; w < hw; w++) e[w] = src[w];
+}
+// vp, vq <- the first hw words of the p-side row at `rows` and of the q-side row behind it
+__device__ __forceinline__ void pd_load_pair(uint32_t* vp, uint32_t* vq, const uint32_t* rows, int rw, int hw, int S) {
+  for (int w = 0; w < hw; w++) vp[w * S] = rows[w];
+  for (int w = 0; w < hw; w++) vq[w * S] = rows[rw + w];
+}
+
+// The recombination's LDS of one lane, thread-interleaved: x (2 hw + 1 words), then mn, d, vp, vq (hw words each).
+struct PdCrtLds {
+  uint32_t* x; uint32_t* mn; uint32_t* d; uint32_t* vp; uint32_t* vq;
+  __device__ __forceinline__ PdCrtLds(uint32_t* lds, int hw, int S)
+      : x(lds + threadIdx.x), mn(x + (size_t)(2 * hw + 1) * S), d(mn + (size_t)hw * S), vp(d + (size_t)hw * S), vq(vp + (size_t)hw * S) {}
+};
+constexpr size_t pd_crt_lds_words_per_lane(int hw) { return 6 * (size_t)hw + 1; }
+
+// out[0 .. 2 hw) = vp + P ((vq - vp) pinv mod Q), or zeros.  l.vp < P and l.vq < Q are kept.
+__device__ __forceinline__ void pd_crt(uint32_t* out, bool ok, const PdCrtLds& l, const uint32_t* P, const uint32_t* Q, const uint32_t* pinv, int hw, int S) {
+  uint32_t* const x = l.x; uint32_t* const mn = l.mn; uint32_t* const d = l.d;
+  const uint32_t* const vp = l.vp; const uint32_t* const vq = l.vq;
+  for (int w = 0; w < hw; w++) x[w * S] = vp[w * S];
+  pd_mod(x, hw, Q, 1, hw, mn, S);                              // vp mod q   (p > q: vp may exceed q)
+  uint32_t borrow = 0;
+  for (int w = 0; w < hw; w++) {
+    const uint64_t t = (uint64_t)vq[w * S] - x[w * S] - borrow;
+    d[w * S] = (uint32_t)t;
+    borrow = (uint32_t)(t >> 63);
+  }
+  if (borrow) {                                                // negative: + q
+    uint32_t c = 0;
+    for (int w = 0; w < hw; w++) {
+      const uint64_t t = (uint64_t)d[w * S] + Q[w] + c;
+      d[w * S] = (uint32_t)t;
+      c = (uint32_t)(t >> 32);
+    }
+  }
+  pd_mul(x, d, hw, pinv, 1, hw, S);
+  pd_mod(x, 2 * hw, Q, 1, hw, mn, S);
+  for (int w = 0; w < hw; w++) d[w * S] = x[w * S];
+  pd_mul(x, d, hw, P, 1, hw, S);                               // p u <= p (q - 1), + vp < n: no carry out of 2 hw words
+  uint32_t c = 0;
+  for (int w = 0; w < 2 * hw; w++) {
+    const uint64_t t = (uint64_t)x[w * S] + (w < hw ? vp[w * S] : 0u) + c;
+    out[w] = ok ? (uint32_t)t : 0u;
+    c = (uint32_t)(t >> 32);
+  }
+}
+
 // ---- key preparation, one key per lane.  Part a writes the four rows of the inverse kernel:
 //   0: (q mod p)^-1 mod p = -h_p      1: (p mod q)^-1 mod q = pinv = -h_q      2: ((p - 1) mod q)^-1 mod q      3: ((q - 1) mod p)^-1 mod p
 // A key with an even p or q, or one below 3, gets zero rows (outside k_modinv's domain: status, no work) and key status 2.
@@ -304,24 +366,20 @@ __global__ void __launch_bounds__(64) k_pdec_split(PdecSplitArgs a) {
   const uint32_t* D = (side ? a.dq : a.dp) + key * (uint64_t)hw;
   const uint64_t r0 = 2 * item + side, r1 = 2 * a.count + 2 * item + side;
   uint32_t* m0 = a.mods + r0 * rw; uint32_t* b0 = a.base + r0 * rw; uint32_t* e0 = a.exp + r0 * hw;
-  if (bad) {
-    for (int w = 0; w < rw; w++) { m0[w] = w == 0 ? 3u : 0u; b0[w] = 0u; }
-    for (int w = 0; w < hw; w++) e0[w] = 0u;
-  } else {
+  if (bad) pd_row_null(m0, b0, e0, rw, hw);
+  else {
     for (int w = 0; w < 2 * kw; w++) x[w * S] = C[w];
     pd_mod(x, 2 * kw, F2, 1, kw, mn, S);
-    for (int w = 0; w < rw; w++) { m0[w] = w < kw ? F2[w] : 0u; b0[w] = w < kw ? x[w * S] : 0u; }
+    pd_row_put(m0, b0, rw, F2, kw, x, S);
     for (int w = 0; w < hw; w++) e0[w] = w == 0 ? F[0] - 1u : F[w];
   }
   if (!a.roots) return;
   uint32_t* m1 = a.mods + r1 * rw; uint32_t* b1 = a.base + r1 * rw; uint32_t* e1 = a.exp + r1 * hw;
-  if (bad) {
-    for (int w = 0; w < rw; w++) { m1[w] = w == 0 ? 3u : 0u; b1[w] = 0u; }
-    for (int w = 0; w < hw; w++) e1[w] = 0u;
-  } else {
+  if (bad) pd_row_null(m1, b1, e1, rw, hw);
+  else {
     pd_mod(x, kw, F, 1, hw, mn, S);                            // (c mod p^2) mod p
-    for (int w = 0; w < rw; w++) { m1[w] = w < hw ? F[w] : 0u; b1[w] = w < hw ? x[w * S] : 0u; }
-    for (int w = 0; w < hw; w++) e1[w] = D[w];
+    pd_row_put(m1, b1, rw, F, hw, x, S);
+    pd_exp_put(e1, D, hw);
   }
 }
 
@@ -335,38 +393,6 @@ struct PdecFinishArgs {
   uint8_t* status;                                             // [count]
   uint64_t count; int hw, rw;
 };
-constexpr size_t pdec_finish_lds_words_per_lane(int hw) { return 6 * (size_t)hw + 1; }
-
-// out[0 .. 2 hw) = vp + P ((vq - vp) pinv mod Q), or zeros.  vp < P and vq < Q: hw words of LDS each (kept); x: 2 hw + 1, mn, d: hw words.
-__device__ __forceinline__ void pd_crt(uint32_t* out, bool ok, const uint32_t* vp, const uint32_t* vq, const uint32_t* P, const uint32_t* Q,
-                                       const uint32_t* pinv, uint32_t* x, uint32_t* mn, uint32_t* d, int hw, int S) {
-  for (int w = 0; w < hw; w++) x[w * S] = vp[w * S];
-  pd_mod(x, hw, Q, 1, hw, mn, S);                              // vp mod q   (p > q: vp may exceed q)
-  uint32_t borrow = 0;
-  for (int w = 0; w < hw; w++) {
-    const uint64_t t = (uint64_t)vq[w * S] - x[w * S] - borrow;
-    d[w * S] = (uint32_t)t;
-    borrow = (uint32_t)(t >> 63);
-  }
-  if (borrow) {                                                // negative: + q
-    uint32_t c = 0;
-    for (int w = 0; w < hw; w++) {
-      const uint64_t t = (uint64_t)d[w * S] + Q[w] + c;
-      d[w * S] = (uint32_t)t;
-      c = (uint32_t)(t >> 32);
-    }
-  }
-  pd_mul(x, d, hw, pinv, 1, hw, S);
-  pd_mod(x, 2 * hw, Q, 1, hw, mn, S);
-  for (int w = 0; w < hw; w++) d[w * S] = x[w * S];
-  pd_mul(x, d, hw, P, 1, hw, S);                               // p u <= p (q - 1), + vp < n: no carry out of 2 hw words
-  uint32_t c = 0;
-  for (int w = 0; w < 2 * hw; w++) {
-    const uint64_t t = (uint64_t)x[w * S] + (w < hw ? vp[w * S] : 0u) + c;
-    out[w] = ok ? (uint32_t)t : 0u;
-    c = (uint32_t)(t >> 32);
-  }
-}
 
 __global__ void __launch_bounds__(64) k_pdec_finish(PdecFinishArgs a) {
   extern __shared__ __align__(16) uint32_t pd_lds[];
@@ -384,11 +410,8 @@ __global__ void __launch_bounds__(64) k_pdec_finish(PdecFinishArgs a) {
   const uint32_t* P = a.p + key * a.key_stride;
   const uint32_t* Q = a.q + key * a.key_stride;
   const uint32_t* pinv = a.pinv + key * a.pinv_stride;
-  uint32_t* x = pd_lds + threadIdx.x;                          // kw + 1 words
-  uint32_t* mn = x + (size_t)(kw + 1) * S;                     // hw words
-  uint32_t* d = mn + (size_t)hw * S;                           // hw words: L, then the recombination's difference
-  uint32_t* vp = d + (size_t)hw * S;                           // hw words: m_p | r_p
-  uint32_t* vq = vp + (size_t)hw * S;                          // hw words: m_q | r_q
+  const PdCrtLds l(pd_lds, hw, S);                             // d: L, then the recombination's difference; vp, vq: m_p | r_p, m_q | r_q
+  uint32_t* const x = l.x; uint32_t* const d = l.d;
   bool ok = true;
   for (int side = 0; side < 2; side++) {
     const uint32_t* F = side ? Q : P;
@@ -400,18 +423,14 @@ __global__ void __launch_bounds__(64) k_pdec_finish(PdecFinishArgs a) {
     const bool exact = pd_divexact(x, kw, F, 1, hw, d, hw, S);
     ok = ok && exact && !zero;
     pd_mul(x, d, hw, h, 1, hw, S);
-    pd_mod(x, kw, F, 1, hw, mn, S);
-    uint32_t* v = side ? vq : vp;
+    pd_mod(x, kw, F, 1, hw, l.mn, S);
+    uint32_t* v = side ? l.vq : l.vp;
     for (int w = 0; w < hw; w++) v[w * S] = x[w * S];
   }
-  pd_crt(om, ok, vp, vq, P, Q, pinv, x, mn, d, hw, S);
+  pd_crt(om, ok, l, P, Q, pinv, hw, S);
   if (orr) {
-    for (int side = 0; side < 2; side++) {
-      const uint32_t* X = a.rows + (2 * a.count + 2 * item + side) * (uint64_t)rw;
-      uint32_t* v = side ? vq : vp;
-      for (int w = 0; w < hw; w++) v[w * S] = X[w];
-    }
-    pd_crt(orr, ok, vp, vq, P, Q, pinv, x, mn, d, hw, S);
+    pd_load_pair(l.vp, l.vq, a.rows + (2 * a.count + 2 * item) * (uint64_t)rw, rw, hw, S);
+    pd_crt(orr, ok, l, P, Q, pinv, hw, S);
   }
   a.status[item] = ok ? 0 : 2;
 }

@@ -6,7 +6,7 @@
 //                    from them the survivor map; the rules for values below 6370^2 are decided here, such values never reach the ladder
 //   k_prime_rows     C ladder rows per unresolved slot: the next C survivors under base 2; for a slot whose candidate passed base 2, its
 //                    random bases first and the following survivors behind them — modulus c_j, exponent d = (c_j - 1) >> s
-//   (pdec_ladder's kernels: y = base^d mod c_j)
+//   (SecretLadder's kernels: y = base^d mod c_j)
 //   k_prime_tail     one row per lane: y == 1, y == c_j - 1, or up to s - 1 squarings (pd_mul, pd_mod) looking for c_j - 1
 //   k_prime_pick     per slot, what the verdicts of its rows mean: dead candidates leave the map, the first base-2 pass becomes the
 //                    candidate, a candidate that passed every base resolves the slot, an empty map ends the window

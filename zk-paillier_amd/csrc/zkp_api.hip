@@ -266,6 +266,14 @@ static bool route_latency(zkp_ctx* c, uint64_t items, uint32_t mod_bits, bool on
   if ((c) && route_latency((c), (items), (mod_bits), (one_key))) return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__));
 #define ZKP_ROUTE_VERIFY(c, items, mod_bits, one_key, fn, ...)                              \
   if ((c) && route_latency((c), (items), (mod_bits), (one_key), true)) return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__));
+// A call that handles p, q or anything derived from them goes to the engine zkp_modexp_batch would pick for its ladder (rows, mod_bits) WHOLE:
+// every block that holds a secret then belongs to the ONE ctx that runs the call and is wiped by that ctx's Stage.  wiped_on names the twin
+// for zkp_diag_witness_residue.  The entry point validates its arguments and returns on an empty batch first: the twin is never asked to.
+#define ZKP_ROUTE_WHOLE(c, rows, mod_bits, fn, ...)                                         \
+  if (route_latency((c), (rows), (mod_bits))) {                                             \
+    (c)->wiped_on = (c)->lat_ctx == (c)->eng_ctx[1] ? 1 : 0;                                \
+    return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__));             \
+  }
 // (diagnostics: only when the caller PINNED the latency engine)
 #define ZKP_ROUTE_PINNED(c, fn, ...)                                                        \
   if ((c) && engine_with((c)->route, (c)->route.geometry) >= 0) { select_engine((c), engine_with((c)->route, (c)->route.geometry)); return lat_forward_plain((c), (c)->lat->p_##fn((c)->lat_ctx, __VA_ARGS__)); }
@@ -273,6 +281,7 @@ static bool route_latency(zkp_ctx* c, uint64_t items, uint32_t mod_bits, bool on
 #define ZKP_ROUTE(c, items, mod_bits, fn, ...)
 #define ZKP_ROUTE_ENC(c, items, mod_bits, one_key, fn, ...)
 #define ZKP_ROUTE_VERIFY(c, items, mod_bits, one_key, fn, ...)
+#define ZKP_ROUTE_WHOLE(c, rows, mod_bits, fn, ...)
 #define ZKP_ROUTE_PINNED(c, fn, ...)
 #endif
 
@@ -358,6 +367,10 @@ struct Stage {
     owned.push_back(b);
     return b.p;
   }
+  // a block of this call for `count` values that no caller sees; null once a take has failed (st says why, and nothing is launched)
+  template <class T> T* scratch(size_t count) { return st ? nullptr : (T*)take(count * sizeof(T)); }
+  // ... registered secret: every block that holds a witness, a nonce, a seed's expansion or a value derived from p or q
+  template <class T> T* secret_scratch(size_t count) { T* p = scratch<T>(count); secret(p, count * sizeof(T)); return p; }
   template <class T> const T* in(const T* p, size_t count) {
     if (dev || !p || st) return p;
     void* d = take(count * sizeof(T));

@@ -1,8 +1,8 @@
 // zkp_api_ck_inter.inc — host side of the interactive CorrectKey for whole batches of sessions (kernels_ck_inter.hpp); included by zkp_api.hip
 // behind zkp_api_ck_prove.inc.  The challenge runs the ladder zkp_modexp_batch uses (run_setup, modexp_core) under the verifier's n, the
-// existing product (modmul_ctx) and k_hash_list; its seeded form puts a configuration of k_nonce_sample in front.  The prove runs the key
-// kernels and the half-width secret ladder of zkp_api_paillier_dec.inc (pdec_ladder) as zkp_correct_key_ni_prove_batch does.  A call that
-// zkp_modexp_batch would hand to a secondary engine for its larger launch goes there WHOLE: one ctx's Stage owns — and wipes — every secret block.
+// existing product (modmul_ctx) and hash_list; its seeded form puts the sampler (nonce_sample_run) in front.  The prove runs the shared
+// pieces of zkp_api_paillier_dec.inc — crt_keys_prepare, ladder_rows_take, SecretLadder — over six half-width rows per round.  The challenge
+// and the prove go to one engine whole (ZKP_ROUTE_WHOLE, by the larger launch).
 
 static bool cki_args_ok(uint32_t n_bits, uint64_t batch, uint32_t K, uint32_t flags) {
   return key_bits_ok(n_bits) && K >= 1 && K <= 256 && batch <= (1ull << 24) && batch * K <= (1ull << 24) && !(flags & ~(uint32_t)ZKP_F_DEVICE_PTRS);
@@ -12,27 +12,13 @@ static bool cki_args_ok(uint32_t n_bits, uint64_t batch, uint32_t K, uint32_t fl
 // Every pointer is device memory; status is written for every session.
 static int32_t cki_sample(zkp_ctx* c, uint32_t n_bits, uint64_t B, uint32_t K, const uint32_t* n, uint64_t n_stride, const uint32_t* key, uint64_t first_index,
                           uint32_t* s_out, uint32_t* r_out, uint8_t* status) {
-  int32_t st;
-  if ((st = ensure(c, c->scratch[S_SAMPLE_META], B * 8))) return st;
-  const uint32_t kw = n_bits / 32;
   NonceSampleArgs a{};
-  a.key = key; a.n = n; a.n_stride = n_stride;
-  a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p; a.status = status;
-  a.first_index = first_index; a.batch = B; a.kw = kw; a.kind = ZKP_SEEDED_KIND_CORRECT_KEY; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
+  a.key = key; a.n = n; a.n_stride = n_stride; a.status = status;
+  a.first_index = first_index; a.batch = B; a.kw = n_bits / 32; a.kind = ZKP_SEEDED_KIND_CORRECT_KEY;
   uint32_t* const fields[2] = {s_out, r_out};
   for (uint32_t f = 0; f < 2; f++)
     if (fields[f]) { a.below[a.nbelow] = fields[f]; a.below_field[a.nbelow] = f; a.below_per[a.nbelow] = K; a.below_slot0[a.nbelow] = 0; a.nbelow++; }
-  hipLaunchKernelGGL(k_nonce_prep, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, a);
-  const uint64_t G = kw / 16, tasks = B * K * a.nbelow;
-  const dim3 grid((unsigned)((tasks * G + 255) / 256));
-  switch (G) {
-    case 2: hipLaunchKernelGGL(k_nonce_sample<2>, grid, dim3(256), 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL(k_nonce_sample<4>, grid, dim3(256), 0, c->stream, a); break;
-    default: hipLaunchKernelGGL(k_nonce_sample<8>, grid, dim3(256), 0, c->stream, a); break;
-  }
-  hipLaunchKernelGGL(k_nonce_fixup, dim3((unsigned)((B * K * kw / 4 + 255) / 256)), dim3(256), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  return nonce_sample_run(c, a, ND_NONE);
 }
 
 // The challenge on device memory.  status holds the sampler's verdicts on entry when `seeded`.  Blocks of `s`: base (s and r under n) and s^e
@@ -43,9 +29,8 @@ static int32_t cki_challenge_impl(zkp_ctx* c, Stage& s, uint32_t n_bits, uint64_
   const uint32_t kw = n_bits / 32;
   const uint64_t items = B * K, nrows = n_stride ? 2 * items : 1;
   const bool per_row = n_stride != 0;
-  auto tmp = [&](size_t words, bool secret) { uint32_t* b = s.st ? nullptr : (uint32_t*)s.take(words * 4); if (secret) s.secret(b, words * 4); return b; };
-  uint32_t *base = tmp(2 * items * kw, true), *se = tmp(items * kw, true);
-  uint32_t *nrow = tmp(nrows * kw, false), *pw = tmp(2 * items * kw, false), *erow = tmp(items * 8, false);
+  uint32_t *base = s.secret_scratch<uint32_t>(2 * items * kw), *se = s.secret_scratch<uint32_t>(items * kw);
+  uint32_t *nrow = s.scratch<uint32_t>(nrows * kw), *pw = s.scratch<uint32_t>(2 * items * kw), *erow = s.scratch<uint32_t>(items * 8);
   if (s.st) return s.st;
   const int lanes = 16;
   hipLaunchKernelGGL(k_cki_chal_status, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, n, n_stride, (int)kw, B, seeded ? 1 : 0, status);
@@ -57,23 +42,13 @@ static int32_t cki_challenge_impl(zkp_ctx* c, Stage& s, uint32_t n_bits, uint64_
   if ((st = run_setup<G>(c, nrow, per_row ? kw : 0, (int)kw, 0, nrows, c->consts))) return st;
   // sn | rn: 2 K B rows with the n_bits-bit exponent n
   if ((st = modexp_core<G>(c, n_bits, 2 * items, base, nrow, per_row ? kw : 0, per_row, pw, (int)kw))) return st;
-  HashListArgs h{};
-  h.op[0] = {n, n_stride, 0, kw, 1};
-  h.op[1] = {pw, (uint64_t)K * kw, kw, kw, K};
-  h.op[2] = {pw + items * kw, (uint64_t)K * kw, kw, kw, K};
-  h.nops = 3; h.batch = B; h.e = out_e;
-  hipLaunchKernelGGL(k_hash_list, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, h);
+  if ((st = hash_list(c, B, {{n, n_stride, 0, kw, 1}, {pw, (uint64_t)K * kw, kw, kw, K}, {pw + items * kw, (uint64_t)K * kw, kw, kw, K}}, out_e))) return st;
   hipLaunchKernelGGL(k_repeat_rows, dim3((unsigned)((items * 8 + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)out_e, (uint64_t)8, 8u, K, items, erow);
   HIPCHK(c, hipGetLastError());
   // s^e: K B rows with a 256-bit exponent, under the records of the first K B rows
   if ((st = modexp_core<G>(c, 256, items, base, erow, 8, per_row, se, (int)kw))) return st;
   if ((st = modmul_ctx<G>(c, c->consts, per_row, items, base + items * kw, 0, se, 0, out_z, (int)kw))) return st;
-  if (out_sd) {
-    HashListArgs d{};
-    d.op[0] = {ds, (uint64_t)K * kw, kw, kw, K};
-    d.nops = 1; d.batch = B; d.e = out_sd;
-    hipLaunchKernelGGL(k_hash_list, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, d);
-  }
+  if (out_sd && (st = hash_list(c, B, {{ds, (uint64_t)K * kw, kw, kw, K}}, out_sd))) return st;
   CkiChalFinishArgs fa{pw, status, out_sn, out_z, out_e, out_sd, items, K, (int)kw};
   hipLaunchKernelGGL(k_cki_chal_finish, dim3((unsigned)((items * kw + 255) / 256)), dim3(256), 0, c->stream, fa);
   HIPCHK(c, hipGetLastError());
@@ -94,14 +69,13 @@ static int32_t cki_challenge(zkp_ctx* c, uint32_t n_bits, uint64_t batch, uint32
   uint32_t* dsd = s.out(out_sd, batch * 8);
   uint8_t* dst = s.out(out_status, batch);
   if (!s.dev) s.secret(dsd, batch * 8 * 4);                  // (host arrays: the staged copy is wiped behind the D2H)
-  if (!s.st && !dst) dst = (uint8_t*)s.take(batch);
+  if (!dst) dst = s.scratch<uint8_t>(batch);
   const uint32_t *dsv = nullptr, *drv = nullptr;
   int32_t st = s.st;
   if (seed) {
     const uint32_t* key = (const uint32_t*)s.host_in(seed, 32);
     s.secret(key, 32);
-    uint32_t* f[2] = {nullptr, nullptr};
-    for (uint32_t*& b : f) { b = s.st ? nullptr : (uint32_t*)s.take(items * kw * 4); s.secret(b, items * kw * 4); }
+    uint32_t* f[2] = {s.secret_scratch<uint32_t>(items * kw), s.secret_scratch<uint32_t>(items * kw)};
     if (!(st = s.st)) st = cki_sample(c, n_bits, batch, K, dn, n_stride, key, first_index, f[0], f[1], dst);
     dsv = f[0]; drv = f[1];
   } else {
@@ -124,13 +98,8 @@ extern "C" int32_t zkp_correct_key_challenge_batch(zkp_ctx* c, uint32_t n_bits, 
     c->err = "zkp_correct_key_challenge_batch: invalid argument"; return ZKP_EINVAL;
   }
   if (batch == 0) return ZKP_OK;
-#ifndef ZKP_SECONDARY_ENGINE
-  if (route_latency(c, 2 * (uint64_t)K * batch, n_bits < 2048 ? 2048 : n_bits)) {       // (zkp_modexp_batch's rule for the larger launch)
-    c->wiped_on = c->lat_ctx == c->eng_ctx[1] ? 1 : 0;
-    return lat_forward_plain(c, c->lat->p_zkp_correct_key_challenge_batch(c->lat_ctx, n_bits, batch, K, n, n_stride, sv, rv, out_sn, out_e, out_z, out_s_digest,
-                                                                          out_status, flags));
-  }
-#endif
+  ZKP_ROUTE_WHOLE(c, 2 * (uint64_t)K * batch, n_bits < 2048 ? 2048 : n_bits, zkp_correct_key_challenge_batch,       // (the larger launch)
+                  n_bits, batch, K, n, n_stride, sv, rv, out_sn, out_e, out_z, out_s_digest, out_status, flags)
   HIPCHK(c, hipSetDevice(c->device));
   return cki_challenge(c, n_bits, batch, K, n, n_stride, sv, rv, nullptr, 0, out_sn, out_e, out_z, out_s_digest, out_status, flags);
 } ZKP_CATCH(c)
@@ -143,13 +112,8 @@ extern "C" int32_t zkp_correct_key_challenge_seeded_batch(zkp_ctx* c, uint32_t n
     c->err = "zkp_correct_key_challenge_seeded_batch: invalid argument"; return ZKP_EINVAL;
   }
   if (batch == 0) return ZKP_OK;
-#ifndef ZKP_SECONDARY_ENGINE
-  if (route_latency(c, 2 * (uint64_t)K * batch, n_bits < 2048 ? 2048 : n_bits)) {
-    c->wiped_on = c->lat_ctx == c->eng_ctx[1] ? 1 : 0;
-    return lat_forward_plain(c, c->lat->p_zkp_correct_key_challenge_seeded_batch(c->lat_ctx, n_bits, batch, K, n, n_stride, seed, first_index, out_sn, out_e, out_z,
-                                                                                 out_s_digest, out_status, flags));
-  }
-#endif
+  ZKP_ROUTE_WHOLE(c, 2 * (uint64_t)K * batch, n_bits < 2048 ? 2048 : n_bits, zkp_correct_key_challenge_seeded_batch,
+                  n_bits, batch, K, n, n_stride, seed, first_index, out_sn, out_e, out_z, out_s_digest, out_status, flags)
   HIPCHK(c, hipSetDevice(c->device));
   return cki_challenge(c, n_bits, batch, K, n, n_stride, nullptr, nullptr, seed, first_index, out_sn, out_e, out_z,
                        out_s_digest, out_status, flags);
@@ -174,22 +138,15 @@ extern "C" int32_t zkp_correct_key_verify_seeded_batch(zkp_ctx* c, uint32_t n_bi
   uint8_t* dv = s.out(out_verdict, batch);
   const uint32_t* key = (const uint32_t*)s.host_in(seed, 32);
   s.secret(key, 32);
-  uint32_t* dsv = s.st ? nullptr : (uint32_t*)s.take(items * kw * 4); s.secret(dsv, items * kw * 4);
-  uint32_t* dig = s.st ? nullptr : (uint32_t*)s.take(batch * 8 * 4); s.secret(dig, batch * 8 * 4);
-  uint8_t* dst = s.st ? nullptr : (uint8_t*)s.take(batch);
-  int32_t st = s.st;
-  if (!st) st = cki_sample(c, n_bits, batch, K, dn, n_stride, key, first_index, dsv, nullptr, dst);
-  if (!st) {
-    hipLaunchKernelGGL(k_cki_chal_status, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, dn, n_stride, (int)kw, batch, 1, dst);
-    HashListArgs d{};
-    d.op[0] = {dsv, (uint64_t)K * kw, kw, kw, K};
-    d.nops = 1; d.batch = batch; d.e = dig;
-    hipLaunchKernelGGL(k_hash_list, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, d);
-    hipLaunchKernelGGL(k_cki_verdict, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)dig, dpd, (const uint8_t*)dst, batch, dv);
-    if (hipGetLastError() != hipSuccess) { c->err = "zkp_correct_key_verify_seeded_batch: launch"; st = ZKP_EDEVICE; }
-  }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  uint32_t *dsv = s.secret_scratch<uint32_t>(items * kw), *dig = s.secret_scratch<uint32_t>(batch * 8);
+  uint8_t* dst = s.scratch<uint8_t>(batch);
+  int32_t st;
+  if ((st = s.st) || (st = cki_sample(c, n_bits, batch, K, dn, n_stride, key, first_index, dsv, nullptr, dst))) return st;
+  hipLaunchKernelGGL(k_cki_chal_status, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, dn, n_stride, (int)kw, batch, 1, dst);
+  if ((st = hash_list(c, batch, {{dsv, (uint64_t)K * kw, kw, kw, K}}, dig))) return st;
+  hipLaunchKernelGGL(k_cki_verdict, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)dig, dpd, (const uint8_t*)dst, batch, dv);
+  HIPCHK(c, hipGetLastError());
+  return s.finish();
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_correct_key_prove_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, uint32_t K, const uint32_t* p, const uint32_t* q, const uint32_t* sn,
@@ -200,15 +157,11 @@ extern "C" int32_t zkp_correct_key_prove_batch(zkp_ctx* c, uint32_t n_bits, uint
     c->err = "zkp_correct_key_prove_batch: invalid argument"; return ZKP_EINVAL;
   }
   if (batch == 0) return ZKP_OK;
-#ifndef ZKP_SECONDARY_ENGINE
-  if (route_latency(c, CKI_ROWS * (uint64_t)K * batch, MOD_BITS)) {      // (zkp_modexp_batch's rule for the ladder's rows)
-    c->wiped_on = c->lat_ctx == c->eng_ctx[1] ? 1 : 0;
-    return lat_forward_plain(c, c->lat->p_zkp_correct_key_prove_batch(c->lat_ctx, n_bits, batch, K, p, q, sn, e, z, out_s_digest, out_error, flags));
-  }
-#endif
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t hw = n_bits / 64, kw = n_bits / 32, rw = MOD_BITS / 32;
   const uint64_t items = batch * K, rows = CKI_ROWS * items;
+  ZKP_ROUTE_WHOLE(c, rows, MOD_BITS, zkp_correct_key_prove_batch, n_bits, batch, K, p, q, sn, e, z, out_s_digest, out_error, flags)
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t hw = n_bits / 64, rw = MOD_BITS / 32;
+  const uint32_t kw = n_bits / 32;
   Stage s(c, flags);
   const uint32_t* dp = s.in(p, batch * hw);
   const uint32_t* dq = s.in(q, batch * hw);
@@ -218,53 +171,32 @@ extern "C" int32_t zkp_correct_key_prove_batch(zkp_ctx* c, uint32_t n_bits, uint
   uint32_t* dsd = s.out(out_s_digest, batch * 8);
   uint8_t* derr = s.out(out_error, batch);
   if (!s.dev) { s.secret(dp, batch * hw * 4); s.secret(dq, batch * hw * 4); }
-  // everything derived from p and q: the inverse kernel's rows, the constants, the ladder's moduli, bases (the residues), exponents and results, the roots
-  auto tmp = [&](size_t words) { uint32_t* b = s.st ? nullptr : (uint32_t*)s.take(words * 4); s.secret(b, words * 4); return b; };
-  uint32_t *inv_a = tmp(4 * batch * hw), *inv_m = tmp(4 * batch * hw), *inv = tmp(4 * batch * hw), *dpe = tmp(batch * hw), *dqe = tmp(batch * hw);
-  uint32_t *mods = tmp(rows * rw), *base = tmp(rows * rw), *lad = tmp(rows * rw), *exps = tmp(rows * hw), *root = tmp(items * kw);
+  const LadderRows r = ladder_rows_take(s, rows, rw, hw);    // the bases are the residues of sn and z under p and q
+  uint32_t* root = s.secret_scratch<uint32_t>(items * kw);
   // public: n, rn, the digest of (n, sn, rn), the coprimality flags
-  uint32_t* dn = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4);
-  uint32_t* rn = s.st ? nullptr : (uint32_t*)s.take(items * kw * 4);
-  uint32_t* echk = s.st ? nullptr : (uint32_t*)s.take(batch * 8 * 4);
-  uint8_t* share = s.st ? nullptr : (uint8_t*)s.take(3 * items);
-  uint8_t* inv_st = s.st ? nullptr : (uint8_t*)s.take(4 * batch);
-  uint8_t* kst = s.st ? nullptr : (uint8_t*)s.take(batch);
-  int32_t st = s.st;
+  uint32_t *dn = s.scratch<uint32_t>(batch * kw), *rn = s.scratch<uint32_t>(items * kw), *echk = s.scratch<uint32_t>(batch * 8);
+  uint8_t* share = s.scratch<uint8_t>(3 * items);
+  if (s.st) return s.st;
   const int lanes = 16;
-  const unsigned key_blocks = (unsigned)((batch + lanes - 1) / lanes);
-  PdecKeyArgs ka{dp, dq, hw, inv_a, inv_m, inv, inv_st, nullptr, nullptr, dpe, dqe, kst, batch, (int)hw};
-  if (!st) {
-    hipLaunchKernelGGL(k_ck_prove_n, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, c->stream, dp, dq, (int)hw, batch, dn);
-    hipLaunchKernelGGL(k_pdec_key_a, dim3(key_blocks), dim3(lanes), lanes * pdec_key_lds_words_per_lane((int)hw) * 4, c->stream, ka);
-    if (hipGetLastError() != hipSuccess) { c->err = "zkp_correct_key_prove_batch: key preparation launch"; st = ZKP_EDEVICE; }
-  }
-  if (!st) st = launch_modinv(c, 4 * batch, (int)hw, inv_a, hw, inv_m, hw, inv, hw, inv_st);
-  if (!st) {
-    hipLaunchKernelGGL(k_pdec_key_b, dim3(key_blocks), dim3(lanes), lanes * pdec_key_lds_words_per_lane((int)hw) * 4, c->stream, ka);
-    CkiProveSplitArgs sa{dsn, dz, de, dn, dp, dq, dpe, dqe, kst, mods, base, exps, items, K, (int)hw, (int)rw};
-    hipLaunchKernelGGL(k_cki_prove_split, dim3((unsigned)((2 * items + lanes - 1) / lanes)), dim3(lanes), lanes * cki_prove_split_lds_words_per_lane((int)hw) * 4, c->stream, sa);
-    if (hipGetLastError() != hipSuccess || hipMemsetAsync(lad, 0, rows * rw * 4, c->stream) != hipSuccess) { c->err = "zkp_correct_key_prove_batch: split launch"; st = ZKP_EDEVICE; }
-  }
-  if (!st) st = pdec_ladder<GA>(c, s, n_bits / 2, rows, mods, base, exps, hw, lad);
-  if (!st) {
-    CkiProveFinishArgs fa{lad, dp, dq, inv + hw, 4 * hw, kst, rn, root, items, K, (int)hw, (int)rw};
-    hipLaunchKernelGGL(k_cki_prove_finish, dim3((unsigned)((items + lanes - 1) / lanes)), dim3(lanes), lanes * cki_prove_finish_lds_words_per_lane((int)hw) * 4, c->stream, fa);
-    hipLaunchKernelGGL(k_cki_prove_gcd, dim3((unsigned)((3 * items + lanes - 1) / lanes)), dim3(lanes), lanes * cki_prove_gcd_lds_words_per_lane((int)kw) * 4, c->stream,
-                       dsn, dz, (const uint32_t*)rn, (const uint32_t*)dn, (const uint8_t*)kst, items, K, (int)kw, share);
-    HashListArgs h{};
-    h.op[0] = {dn, kw, 0, (uint32_t)kw, 1};
-    h.op[1] = {dsn, (uint64_t)K * kw, kw, (uint32_t)kw, K};
-    h.op[2] = {rn, (uint64_t)K * kw, kw, (uint32_t)kw, K};
-    h.nops = 3; h.batch = batch; h.e = echk;
-    hipLaunchKernelGGL(k_hash_list, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
-    HashListArgs d{};
-    d.op[0] = {root, (uint64_t)K * kw, kw, (uint32_t)kw, K};
-    d.nops = 1; d.batch = batch; d.e = dsd;
-    hipLaunchKernelGGL(k_hash_list, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, d);
-    CkiProveMergeArgs ma{share, kst, de, echk, dsd, derr, batch, K};
-    hipLaunchKernelGGL(k_cki_prove_merge, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, ma);
-    if (hipGetLastError() != hipSuccess) { c->err = "zkp_correct_key_prove_batch: finish launch"; st = ZKP_EDEVICE; }
-  }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  hipLaunchKernelGGL(k_ck_prove_n, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, c->stream, dp, dq, (int)hw, batch, dn);
+  HIPCHK(c, hipGetLastError());
+  CrtKeys k;
+  int32_t st;
+  if ((st = crt_keys_prepare(c, s, dp, dq, hw, batch, hw, false, &k))) return st;
+  CkiProveSplitArgs sa{dsn, dz, de, dn, dp, dq, k.dp, k.dq, k.kst, r.mods, r.base, r.exps, items, K, (int)hw, (int)rw};
+  hipLaunchKernelGGL(k_cki_prove_split, dim3((unsigned)((2 * items + lanes - 1) / lanes)), dim3(lanes), lanes * cki_prove_split_lds_words_per_lane((int)hw) * 4, c->stream, sa);
+  HIPCHK(c, hipGetLastError());
+  SecretLadder<GA> ladder{c};
+  if ((st = ladder.take(s, rows)) || (st = ladder.run(n_bits / 2, rows, r.mods, r.base, r.exps, hw, r.lad))) return st;
+  CkiProveFinishArgs fa{r.lad, dp, dq, k.pinv, k.pinv_stride, k.kst, rn, root, items, K, (int)hw, (int)rw};
+  hipLaunchKernelGGL(k_cki_prove_finish, dim3((unsigned)((items + lanes - 1) / lanes)), dim3(lanes), lanes * pd_crt_lds_words_per_lane((int)hw) * 4, c->stream, fa);
+  hipLaunchKernelGGL(k_cki_prove_gcd, dim3((unsigned)((3 * items + lanes - 1) / lanes)), dim3(lanes), lanes * cki_prove_gcd_lds_words_per_lane((int)kw) * 4, c->stream,
+                     dsn, dz, (const uint32_t*)rn, (const uint32_t*)dn, k.kst, items, K, (int)kw, share);
+  HIPCHK(c, hipGetLastError());
+  if ((st = hash_list(c, batch, {{dn, kw, 0, kw, 1}, {dsn, (uint64_t)K * kw, kw, kw, K}, {rn, (uint64_t)K * kw, kw, kw, K}}, echk))) return st;
+  if ((st = hash_list(c, batch, {{root, (uint64_t)K * kw, kw, kw, K}}, dsd))) return st;
+  CkiProveMergeArgs ma{share, k.kst, de, echk, dsd, derr, batch, K};
+  hipLaunchKernelGGL(k_cki_prove_merge, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, ma);
+  HIPCHK(c, hipGetLastError());
+  return s.finish();
 } ZKP_CATCH(c)

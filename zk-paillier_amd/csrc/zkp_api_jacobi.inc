@@ -104,10 +104,9 @@ extern "C" int32_t zkp_dlog_statement_setup_seeded_batch(zkp_ctx* c, uint32_t n_
   uint32_t *dg = s.out(out_g, batch * kw), *dni = s.out(out_ni, batch * kw), *dsec = s.out(out_secret, batch * 8);
   if (!s.dev) s.secret(dsec, batch * 8 * 4);        // (host arrays: the staged copy is wiped behind the D2H)
   uint8_t* ds = s.out(out_status, batch);
-  uint32_t* h1inv = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4);
-  s.secret(h1inv, batch * kw * 4);                  // h2 = (h1^-1)^secret: whoever has h1^-1 and h2 is one discrete logarithm from the secret — wiped with it
-  uint8_t* invst = s.st ? nullptr : (uint8_t*)s.take(batch);
-  if (!s.st && !ds) ds = (uint8_t*)s.take(batch);
+  uint32_t* h1inv = s.secret_scratch<uint32_t>(batch * kw);       // h2 = (h1^-1)^secret: whoever has h1^-1 and h2 is one discrete logarithm from the secret — wiped with it
+  uint8_t* invst = s.scratch<uint8_t>(batch);
+  if (!ds) ds = s.scratch<uint8_t>(batch);
   int32_t st = s.st;
   if (!st) {
     HIPCHK(c, hipMemsetAsync(dni, 0, batch * kw * 4, c->stream));
@@ -121,7 +120,7 @@ extern "C" int32_t zkp_dlog_statement_setup_seeded_batch(zkp_ctx* c, uint32_t n_
   if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return dlog_setup_impl<G()>(c, n_bits, batch, dN, h1inv, dsec, dni); });
   if (!st) {
     hipLaunchKernelGGL(k_dlog_setup_finish, dim3((unsigned)((batch * kw + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)ds, dni, (uint32_t)kw, (uint64_t)batch);
-    if (hipGetLastError() != hipSuccess) { c->err = "k_dlog_setup_finish launch"; st = ZKP_EDEVICE; }
+    HIPCHK(c, hipGetLastError());
   }
   const int32_t fin = s.finish();
   return st ? st : fin;

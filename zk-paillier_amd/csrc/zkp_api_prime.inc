@@ -1,9 +1,9 @@
 // zkp_api_prime.inc — host side of zkp_probable_prime_batch, zkp_next_prime_batch and zkp_paillier_keygen_seeded_batch (kernels_prime.hpp);
 // included by zkp_api.hip behind zkp_api_ck_prove.inc.  The three calls are ONE search (prime_search) over slots: a loop of rounds
 // "rows -> ladder -> tail -> pick -> window -> compact" for the still-unresolved slots, on the ctx stream, in which the host reads one word
-// per round: the number of slots left.  The ladder is pdec_ladder's — run_setup under per-row moduli and modexp_core over constants records
-// and window tables that are blocks of the call's Stage, registered secret (they hold the candidates) — with the two blocks taken ONCE per
-// call, sized for the first round, instead of once per launch.  The calls run on the engine of the ctx that receives them.
+// per round: the number of slots left.  The ladder is a SecretLadder (zkp_api_paillier_dec.inc): its constants records and window tables hold
+// the candidates, so they are secret blocks of the call's Stage — taken ONCE per call, sized for the first round, and run every round.  The
+// calls run on the engine of the ctx that receives them.
 
 // Rows per slot and round: C = PRIME_TARGET_ROWS / (slots left), at least PRIME_C and at most PRIME_C_MAX.  A ladder launch of a few rows
 // takes as long as one of tens of thousands (it is one chain of products per row), so while many slots are left the rows are kept few —
@@ -12,28 +12,6 @@
 constexpr int PRIME_C = 4, PRIME_C_MAX = 64;
 constexpr uint64_t PRIME_TARGET_ROWS = 32768;
 constexpr uint64_t PRIME_SLAB_SLOTS = 8192;                  // slots in flight: 32 768 ladder rows, about 50 MB of the call's blocks
-
-struct PrimeLadder {
-  zkp_ctx* c; void* cp = nullptr; void* tp = nullptr; size_t cbytes = 0, tbytes = 0;
-  int32_t take(Stage& s, uint64_t max_rows) {
-    using CL = ConstLayout<GA>;
-    unsigned blocks = 0;
-    cbytes = max_rows * CL::WORDS * sizeof(uint32_t);
-    tbytes = table_bytes<GA>(c, k_modexp<GA, false>, max_rows, &blocks);      // (monotonic in the rows: the first round's is the largest)
-    cp = s.take(cbytes);
-    tp = s.st ? nullptr : s.take(tbytes);
-    if (s.st) return s.st;
-    s.secret(cp, cbytes); s.secret(tp, tbytes);
-    return ZKP_OK;
-  }
-  int32_t run(uint32_t exp_bits, uint64_t rows, const uint32_t* mods, const uint32_t* base, const uint32_t* exps, uint64_t exp_stride, uint32_t* out) {
-    using LL = LdsLayout<GA>;
-    PdecBorrowedBufs borrowed(c, cp, cbytes, tp, tbytes);
-    int32_t st;
-    if ((st = run_setup<GA>(c, mods, LL::NW, LL::NW, 0, rows, c->consts))) return st;
-    return modexp_core<GA>(c, exp_bits, rows, base, exps, exp_stride, true, out, LL::NW);
-  }
-};
 
 struct PrimeCall {
   int mode; uint32_t bits, rounds; uint64_t nslots, first_index;
@@ -53,20 +31,19 @@ static int32_t prime_search(zkp_ctx* c, Stage& s, const PrimeCall& q) {
   // rows of a round: left * clamp(target / left, cmin, PRIME_C_MAX) <= max(left * cmin, target); two rows at least: a one-row launch
   // would tag the borrowed constants as ONE key's record
   const uint64_t max_rows = std::max<uint64_t>(2, std::max(slab * cmin, target));
-  auto tmp = [&](size_t words) { uint32_t* b = s.st ? nullptr : (uint32_t*)s.take(words * 4); s.secret(b, words * 4); return b; };
   PrimeArgs a{};
   a.key = q.key; a.first_index = q.first_index; a.mode = q.mode; a.pw = pw; a.rounds = (int)q.rounds;
-  a.start = tmp(slab * pw); a.map = tmp(slab * PRIME_MAP_WORDS);
-  a.state = tmp(slab); a.attempt = tmp(slab); a.cand = tmp(slab); a.next_r = tmp(slab); a.found_j = tmp(slab);
-  a.mods = tmp(max_rows * PRIME_ROW_WORDS); a.base = tmp(max_rows * PRIME_ROW_WORDS); a.exp = tmp(max_rows * pw);
-  uint32_t* lad = tmp(max_rows * PRIME_ROW_WORDS);
+  a.start = s.secret_scratch<uint32_t>(slab * pw); a.map = s.secret_scratch<uint32_t>(slab * PRIME_MAP_WORDS);
+  for (uint32_t** per_slot : {&a.state, &a.attempt, &a.cand, &a.next_r, &a.found_j}) *per_slot = s.secret_scratch<uint32_t>(slab);
+  a.mods = s.secret_scratch<uint32_t>(max_rows * PRIME_ROW_WORDS); a.base = s.secret_scratch<uint32_t>(max_rows * PRIME_ROW_WORDS);
+  a.exp = s.secret_scratch<uint32_t>(max_rows * pw);
+  uint32_t* lad = s.secret_scratch<uint32_t>(max_rows * PRIME_ROW_WORDS);
   a.lad = lad;
-  a.row_j = tmp(max_rows); a.row_ok = (uint8_t*)tmp((max_rows + 3) / 4);
-  uint32_t* list[2] = {tmp(slab), tmp(slab)};
-  uint32_t* counter = tmp(1);
-  PrimeLadder ladder{c};
-  if (!s.st) (void)ladder.take(s, max_rows);
-  if (s.st) return s.st;
+  a.row_j = s.secret_scratch<uint32_t>(max_rows); a.row_ok = (uint8_t*)s.secret_scratch<uint32_t>((max_rows + 3) / 4);
+  uint32_t* list[2] = {s.secret_scratch<uint32_t>(slab), s.secret_scratch<uint32_t>(slab)};
+  uint32_t* counter = s.secret_scratch<uint32_t>(1);
+  SecretLadder<GA> ladder{c};
+  if (ladder.take(s, max_rows)) return s.st;
   // the tail: one value per lane in LDS, (4 pw + 1) words each — 64 lanes would be 65.8 KB at pw = 64, 16 lanes are 16.4 KB and leave room
   // for several blocks per compute unit (the block size of the key kernels; 32 lanes were not measured)
   const int lanes = 16;
@@ -136,11 +113,9 @@ static int32_t prime_entry(zkp_ctx* c, const char* what, int mode, uint32_t bits
   q.out_offset = s.out(out_offset, count);
   q.out_status = s.out(out_status, count);
   if (!s.dev && !s.st) { s.secret(q.in, count * pw * 4); s.secret(q.out_prime, count * pw * 4); }       // (after a failed take, in() and out() hand back the HOST pointer)
-  int32_t st = s.st;
-  if (!st) st = prime_search(c, s, q);
-  if (st && !s.st) s.st = st;                                // a call that failed copies nothing back: the caller's arrays stay as they were
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  int32_t st;
+  if ((st = s.st) || (st = prime_search(c, s, q))) return st;       // a call that failed copies nothing back: the caller's arrays stay as they were
+  return s.finish();
 }
 
 extern "C" int32_t zkp_probable_prime_batch(zkp_ctx* c, uint32_t bits, uint64_t count, const uint32_t* w, uint32_t rounds, const uint8_t* seed,
@@ -172,16 +147,14 @@ extern "C" int32_t zkp_paillier_keygen_seeded_batch(zkp_ctx* c, uint32_t n_bits,
   uint32_t* dn = s.out(out_n, batch * kw);
   q.key_status = s.out(out_status, batch);
   if (!s.dev && !s.st) { s.secret(q.out_p, batch * hw * 4); s.secret(q.out_q, batch * hw * 4); }
-  if (!s.st && !q.key_status) q.key_status = (uint8_t*)s.take(batch);
-  int32_t st = s.st;
-  if (!st) st = prime_search(c, s, q);
-  if (!st && dn) {                                           // n = p q (zero for a malformed key, whose p and q are zero)
+  if (!q.key_status) q.key_status = s.scratch<uint8_t>(batch);
+  int32_t st;
+  if ((st = s.st) || (st = prime_search(c, s, q))) return st;       // a call that failed copies nothing back: the caller's arrays stay as they were
+  if (dn) {                                                  // n = p q (zero for a malformed key, whose p and q are zero)
     hipLaunchKernelGGL(k_ck_prove_n, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, c->stream, q.out_p, q.out_q, (int)hw, batch, dn);
-    if (hipGetLastError() != hipSuccess) { c->err = "zkp_paillier_keygen_seeded_batch: product launch"; st = ZKP_EDEVICE; }
+    HIPCHK(c, hipGetLastError());
   }
-  if (st && !s.st) s.st = st;                                // a call that failed copies nothing back: the caller's arrays stay as they were
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish();
 } ZKP_CATCH(c)
 
 // measurement only (tools/dev/keygen_ab.py): chunk > 0 sets the least rows per slot and round for this ctx, target_rows > 0 the rows a round

@@ -375,7 +375,7 @@ extern "C" int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* c, const zkp_range_n
   s.secret(key, 32);
   zkp_range_ni_witness dw{};
   uint32_t* wit[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& q : wit) { q = s.st ? nullptr : (uint32_t*)s.take(rows * kw * 4); s.secret(q, rows * kw * 4); }
+  for (auto& q : wit) q = s.secret_scratch<uint32_t>(rows * kw);
   dw.w1 = wit[0]; dw.w2 = wit[1]; dw.r1 = wit[2]; dw.r2 = wit[3];
   dw.x = s.in(x, B * kw); dw.r = s.in(r, B * kw);
   if (!s.dev) { s.secret(dw.x, B * kw * 4); s.secret(dw.r, B * kw * 4); }
@@ -465,7 +465,7 @@ static int32_t range_interactive_seeded(zkp_ctx* c, const char* name, int step, 
   s.secret(key, 32);
   zkp_range_ni_witness dw{};
   uint32_t* wit[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& q : wit) { q = s.st ? nullptr : (uint32_t*)s.take(rows * kw * 4); s.secret(q, rows * kw * 4); }
+  for (auto& q : wit) q = s.secret_scratch<uint32_t>(rows * kw);
   dw.w1 = wit[0]; dw.w2 = wit[1]; dw.r1 = wit[2]; dw.r2 = wit[3];
   const uint8_t *de = nullptr, *dl = nullptr;
   if (step == 2) {

@@ -30,26 +30,15 @@ static size_t nonce_field_words(uint32_t kind, uint32_t f, uint32_t kw, uint32_t
   return (size_t)nonce_field_rows(d, K) * (d.words ? d.words : kw);
 }
 
-// every pointer is device memory; out[f] is the array of field f (null where the kind has none, or no slots); status is written for every proof
-static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, uint64_t B, uint32_t K, const uint32_t* n, uint64_t n_stride,
-                                   const uint32_t* key, uint64_t first_index, uint32_t* const out[4], uint8_t* status) {
+// The sampler's launches over filled args (everything but meta and max_attempts): k_nonce_prep, the BELOW draws, the kind's RAW or COPRIME
+// field (`fourth`; k_nonce_prep and k_nonce_sample do not read it, k_nonce_fixup zeroes it by (raw_per, raw_words): a COPRIME field is handed
+// to it as one row of kw words per proof) and the fixup.  Every pointer is device memory; status is written for every proof.
+static int32_t nonce_sample_run(zkp_ctx* c, NonceSampleArgs& a, NonceDraw fourth) {
   int32_t st;
-  if ((st = ensure(c, c->scratch[S_SAMPLE_META], B * 8))) return st;
-  const uint32_t kw = n_bits / 32;
-  NonceSampleArgs a{};
-  a.key = key; a.n = kind == ZKP_SEEDED_KIND_DLOG ? nullptr : n; a.n_stride = n_stride;
-  a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p; a.status = status;
-  a.first_index = first_index; a.batch = B; a.kw = kw; a.kind = kind; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
-  NonceDraw fourth = ND_NONE;          // the kind's RAW or COPRIME field; k_nonce_prep and k_nonce_sample do not read it, k_nonce_fixup zeroes
-  for (uint32_t f = 0; f < 4; f++) {   // it by (raw_per, raw_words): a COPRIME field is handed to it as one row of kw words per proof
-    const NonceField& d = NONCE_FIELDS[kind][f];
-    if (d.draw == ND_BELOW) {
-      a.below[a.nbelow] = out[f]; a.below_field[a.nbelow] = f; a.below_per[a.nbelow] = nonce_field_rows(d, K); a.below_slot0[a.nbelow] = d.slot0; a.nbelow++;
-    } else if (d.draw != ND_NONE) {
-      a.raw = out[f]; a.raw_field = f; a.raw_per = nonce_field_rows(d, K); a.raw_slot0 = d.slot0; a.raw_words = d.words ? d.words : kw;
-      fourth = d.draw;
-    }
-  }
+  if ((st = ensure(c, c->scratch[S_SAMPLE_META], a.batch * 8))) return st;
+  a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
+  const uint64_t B = a.batch;
+  const uint32_t kw = a.kw;
   hipLaunchKernelGGL(k_nonce_prep, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   const uint64_t G = kw / 16;
@@ -70,7 +59,7 @@ static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, u
     // As launch_modinv: latency-bound work with data-dependent trip counts, so small blocks — divergence stays among 16 lanes, several
     // wavefronts share a compute unit, and two operands per lane are 16 KB of LDS per block at kw = 128.
     const int lanes = 16;
-    NonceCoprimeArgs q{key, n, n_stride, a.meta, a.raw, status, first_index, B, kw, kind, a.raw_field, RANGE_SAMPLE_MAX_ATTEMPTS};
+    NonceCoprimeArgs q{a.key, a.n, a.n_stride, a.meta, a.raw, a.status, a.first_index, B, kw, a.kind, a.raw_field, RANGE_SAMPLE_MAX_ATTEMPTS};
     hipLaunchKernelGGL(k_nonce_coprime, dim3((unsigned)((B + lanes - 1) / lanes)), dim3(lanes), lanes * coprime_lds_words_per_lane(kw) * 4, c->stream, q);
   }
   HIPCHK(c, hipGetLastError());
@@ -80,6 +69,26 @@ static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, u
     HIPCHK(c, hipGetLastError());
   }
   return ZKP_OK;
+}
+
+// the kinds of NONCE_FIELDS: out[f] is the array of field f (null where the kind has none, or no slots)
+static int32_t nonce_sample_launch(zkp_ctx* c, uint32_t kind, uint32_t n_bits, uint64_t B, uint32_t K, const uint32_t* n, uint64_t n_stride,
+                                   const uint32_t* key, uint64_t first_index, uint32_t* const out[4], uint8_t* status) {
+  const uint32_t kw = n_bits / 32;
+  NonceSampleArgs a{};
+  a.key = key; a.n = kind == ZKP_SEEDED_KIND_DLOG ? nullptr : n; a.n_stride = n_stride; a.status = status;
+  a.first_index = first_index; a.batch = B; a.kw = kw; a.kind = kind;
+  NonceDraw fourth = ND_NONE;
+  for (uint32_t f = 0; f < 4; f++) {
+    const NonceField& d = NONCE_FIELDS[kind][f];
+    if (d.draw == ND_BELOW) {
+      a.below[a.nbelow] = out[f]; a.below_field[a.nbelow] = f; a.below_per[a.nbelow] = nonce_field_rows(d, K); a.below_slot0[a.nbelow] = d.slot0; a.nbelow++;
+    } else if (d.draw != ND_NONE) {
+      a.raw = out[f]; a.raw_field = f; a.raw_per = nonce_field_rows(d, K); a.raw_slot0 = d.slot0; a.raw_words = d.words ? d.words : kw;
+      fourth = d.draw;
+    }
+  }
+  return nonce_sample_run(c, a, fourth);
 }
 
 static bool nonce_args_ok(uint32_t kind, uint32_t n_bits, uint64_t batch, uint32_t K, uint64_t n_stride) {
@@ -145,7 +154,7 @@ struct SeededNonces {
     key = (const uint32_t*)s.host_in(seed, 32);
     s.secret(key, 32);
     for (uint32_t k = 0; k < 4; k++)
-      if (const size_t bytes = B * nonce_field_words(kind, k, n_bits / 32, K) * 4; bytes && !s.st) { f[k] = (uint32_t*)s.take(bytes); s.secret(f[k], bytes); }
+      if (const size_t words = B * nonce_field_words(kind, k, n_bits / 32, K)) f[k] = s.secret_scratch<uint32_t>(words);
     if ((st = s.st)) return;
     if ((st = ensure(c, c->scratch[S_SAMPLE_STATUS], B))) return;
     status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p;
@@ -336,8 +345,7 @@ static int32_t range_commit_seeded(zkp_ctx* c, const char* name, bool reveal, ui
     if (!s.dev) { s.secret(a.r, batch * kw * 4); s.secret(a.e_out, batch * 32); }      // (host arrays: the staged copies are wiped behind the D2H)
   } else {
     dcom = s.out(out_com, batch * 2 * kw);
-    a.r = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4); s.secret(a.r, batch * kw * 4);
-    a.m = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4); s.secret(a.m, batch * kw * 4);
+    a.r = s.secret_scratch<uint32_t>(batch * kw); a.m = s.secret_scratch<uint32_t>(batch * kw);
   }
   a.status = s.out(out_status, batch);
   a.first_index = first_index; a.batch = batch; a.kw = (uint32_t)kw; a.e_len = e_len; a.kind = ZKP_SEEDED_KIND_RANGE_COMMIT; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
@@ -377,7 +385,7 @@ extern "C" int32_t zkp_range_verify_commit_batch(zkp_ctx* c, uint32_t n_bits, ui
   const uint32_t* dr = s.in(r, batch * kw);
   a.e_in = s.in(e, batch * 32); a.e_len_in = s.in(e_len, batch);
   uint8_t* dv = s.out(out_verdict, batch);
-  a.m = s.st ? nullptr : (uint32_t*)s.take(batch * kw * 4);      // (r and e are public by now: nothing to wipe)
+  a.m = s.scratch<uint32_t>(batch * kw);           // (r and e are public by now: nothing to wipe)
   a.batch = batch; a.kw = (uint32_t)kw;
   int32_t st = s.st;
   if (!st) st = ensure(c, c->scratch[S_SAMPLE_STATUS], batch);
@@ -386,7 +394,7 @@ extern "C" int32_t zkp_range_verify_commit_batch(zkp_ctx* c, uint32_t n_bits, ui
   if (!st) st = zkp_paillier_enc_check_batch(c, n_bits, batch, a.n, n_stride, a.m, dr, nullptr, nullptr, dcom, dv, ZKP_F_DEVICE_PTRS);
   if (!st) {
     hipLaunchKernelGGL(k_range_commit_verdict, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, dv, (const uint8_t*)a.status, batch);
-    if (hipGetLastError() != hipSuccess) { c->err = "k_range_commit_verdict launch"; st = ZKP_EDEVICE; }
+    HIPCHK(c, hipGetLastError());
   }
   const int32_t fin = s.finish();
   return st ? st : fin;
