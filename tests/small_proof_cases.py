@@ -7,7 +7,10 @@ Two families of cases:
           dishonest items on both sides of the wavefront boundary and of the block boundary (`marked`).
   edges — a few dozen proofs, operand edges next to ordinary items: prover inputs 0, 1, n - 1, 2^n_bits - 1; verifier inputs an adversary
           chooses (responses with every limb set, the same residue k * n higher, values >= n^2, 0, 1, values of ragged byte length), and one
-          proof per kind whose challenge has a zero top byte (found by a seeded search here, nothing is stored).
+          proof per kind whose challenge has a zero top byte (found by a seeded search here, nothing is stored; n = 1024 only).
+          Built at 1024 and 4096 bits under per-proof keys (three, cycled) and at 2048 bits under one shared key.  At 4096 bits the
+          modulus n^2 has 8192 bits — the widest kernel geometry, a pair of groups per item and one item per wavefront on the latency
+          engine — and a batch still crosses a wavefront's claim and the block of every engine.
 
 The statements are computed with the C oracle (threads), everything else comes from the repo's DRBG.  The oracle results of a case are
 computed ONCE per process (`cached`): the `ctx` fixture runs every GPU test under several kernel families and must not multiply that work."""
@@ -46,9 +49,17 @@ def ones(words):
 
 
 def keys_for(n_bits, count):
-    """(p, q, n) triples: `count` deterministic 1024-bit keys, or the reference's fixture key at 2048 bits"""
+    """(p, q, n) triples: `count` deterministic 1024-bit keys, or the reference's fixture key at 2048 bits.  At 4096 bits no prime is
+    generated (two 2048-bit primes take CPython as long as the CPU part of the suite): the moduli of dlog_cases.keys(4096) — the
+    benchmark's key first, then products of four pooled 1024-bit primes, four in all — with p a proper prime factor of n and q = n / p,
+    which is composite in the pooled ones.  The `no_inverse` and "multiple of p" items need no more than gcd(p, n) = p."""
     if n_bits == 2048:
         return [H.fixture_key()]
+    if n_bits == 4096:
+        import dlog_cases
+        ks = dlog_cases.keys(4096)
+        assert count <= len(ks)
+        return [(p, n // p, n) for p, n in ks[:count]]
     return [H.test_key(n_bits, tag=t) for t in range(count)]
 
 
@@ -317,7 +328,7 @@ def verlin_edges(oracle, n_bits):
         set_int(a["app"], b, v["app"][b])
         short["verlin"] = b
     free = [b for b in range(bt.B) if (b % 2 == 0 or b > 17) and b not in stmt]
-    return dict(bt=bt, a=a, free=free, short=short, ragged_statements=stmt)
+    return dict(bt=bt, a=a, free=free, short=short, ragged_statements=stmt, n_minus_1=7, all_set=9)
 
 
 VERLIN_OUT = ("phi_a", "z", "zp", "zpp", "rz")
@@ -402,7 +413,7 @@ def mul_edges(oracle, n_bits):
         short["mul"] = b
     a = _mul_finish(oracle, bt, v)
     free = [b for b in range(bt.B) if b % 2 == 0 or b > 21]
-    return dict(bt=bt, a=a, free=free, short=short, f_zero=1, f_top=3, carry=7)
+    return dict(bt=bt, a=a, free=free, short=short, f_zero=1, f_top=3, carry=7, all_set=9)
 
 
 def mul_edits(cs, outs):
@@ -502,7 +513,7 @@ def cm_edges(n_bits):
     free = [b for b in range(bt.B) if b % 2 == 0 or b > 23]
     for b in free[:4]:
         rows[b]["z_sim"] = [d.below(1 << (n_bits - 8)) for _ in range(K - 1)]
-    return dict(bt=bt, K=K, a=_cm_arrays(bt, K, rows), rows=rows, free=free, short=short, duplicate=7, not_listed=9, roomy=free[:4])
+    return dict(bt=bt, K=K, a=_cm_arrays(bt, K, rows), rows=rows, free=free, short=short, duplicate=7, not_listed=9, roomy=free[:4], n_minus_1=13, all_set=19)
 
 
 def cm_k1():

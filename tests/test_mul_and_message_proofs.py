@@ -59,7 +59,9 @@ def test_oracle_modinv(oracle):
 MUL_IN = ("e_a", "e_b", "e_c", "a", "b", "r_a", "r_b", "r_c", "d", "r_d")
 
 
-def mul_cases(n_bits, keys, B, seed, honest=True):
+def mul_cases(n_bits, keys, B, seed, honest=True, oracle=None):
+    """the three ciphertexts of a row are computed by the Python model, or — `oracle` given: the GPU tests at 4096 bits, where one Enc
+    takes CPython 0.7 s — by the C oracle from the same inputs"""
     d = pm.Drbg(seed)
     kw = n_bits // 32
     rows = []
@@ -68,8 +70,15 @@ def mul_cases(n_bits, keys, B, seed, honest=True):
         a, b = d.below(n), d.below(n)
         c = a * b % n if honest else (a * b + 1) % n
         r_a, r_b, r_c, dd, r_d = (d.below(n) for _ in range(5))
-        rows.append(dict(n=n, a=a, b=b, c=c, r_a=r_a, r_b=r_b, r_c=r_c, d=dd, r_d=r_d,
-                         e_a=pm.enc(n, a, r_a), e_b=pm.enc(n, b, r_b), e_c=pm.enc(n, c, r_c)))
+        rows.append(dict(n=n, a=a, b=b, c=c, r_a=r_a, r_b=r_b, r_c=r_c, d=dd, r_d=r_d))
+    ns = L.ints_to_limbs([q["n"] for q in rows], kw)
+    for m, r in (("a", "r_a"), ("b", "r_b"), ("c", "r_c")):
+        if oracle:
+            e = L.limbs_to_ints(oracle.paillier_enc(n_bits, ns, kw, L.ints_to_limbs([q[m] for q in rows], kw), L.ints_to_limbs([q[r] for q in rows], kw)))
+        else:
+            e = [pm.enc(q["n"], q[m], q[r]) for q in rows]
+        for q, v in zip(rows, e):
+            q["e_" + m] = v
     arr = {k: L.ints_to_limbs([q[k] for q in rows], 2 * kw if k.startswith("e_") else kw) for k in ("n",) + MUL_IN}
     return rows, arr
 
@@ -189,18 +198,22 @@ def test_gpu_modinv_matches_oracle(ctx, oracle, mod_bits):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits,shared", [(1024, False), (2048, True)])
+@pytest.mark.parametrize("n_bits,shared", [(1024, False), (2048, True), (4096, True)])
 def test_gpu_mul_proof_matches_oracle(ctx, oracle, n_bits, shared):
+    """(4096: the benchmark's key — 8192-bit n^2, the widest kernel geometry under the composition)"""
     kw = n_bits // 32
     if n_bits == 2048:
         pq = [H.fixture_key()]
+    elif n_bits == 4096:
+        pq = SC.keys_for(4096, 1)
     else:
         pq = [H.test_key(n_bits, tag=t) for t in range(1 if shared else 3)]
     keys = [k[2] for k in pq]
     B = 6
     oracle.set_threads(min(8, oracle.max_threads()))
-    rows, a = mul_cases(n_bits, keys, B, b"mul-gpu-%d" % n_bits)
-    bad_rows, bad = mul_cases(n_bits, keys, B, b"mul-gpu-bad-%d" % n_bits, honest=False)
+    by = oracle if n_bits == 4096 else None
+    rows, a = mul_cases(n_bits, keys, B, b"mul-gpu-%d" % n_bits, oracle=by)
+    bad_rows, bad = mul_cases(n_bits, keys, B, b"mul-gpu-bad-%d" % n_bits, honest=False, oracle=by)
     for k in MUL_IN:                      # proofs 4 and 5 are about a false statement (test_bad_mul_proof)
         a[k][4:] = bad[k][4:]
     a["r_c"][3] = L.int_to_limbs(pq[3 % len(pq)][0], kw)   # r_c = p: the prover's mod_inv has no result
@@ -210,6 +223,8 @@ def test_gpu_mul_proof_matches_oracle(ctx, oracle, n_bits, shared):
     fo, z1o, z2o, edo, edbo, so = oracle.mul_proof_prove(n_bits, n_arr, stride, *ins)
     fg = np.full((B, kw), 7, np.uint32); z1g, z2g, edg, edbg = (np.full((B, 2 * kw), 7, np.uint32) for _ in range(4)); sg = np.full(B, 9, np.uint8)
     ctx.mul_proof_prove(n_bits, B, n_arr, stride, *ins, fg, z1g, z2g, edg, edbg, sg)
+    if n_bits == 4096:
+        assert ctx.last_geometry() == ctx.test_geometry, "the call ran on another engine than the one this family pins"
     assert list(so) == [0, 0, 0, MALFORMED, 0, 0] and np.array_equal(so, sg)
     for name, x, y in (("f", fo, fg), ("z1", z1o, z1g), ("z2", z2o, z2g), ("e_d", edo, edg), ("e_db", edbo, edbg)):
         assert np.array_equal(x, y), name
@@ -218,6 +233,7 @@ def test_gpu_mul_proof_matches_oracle(ctx, oracle, n_bits, shared):
         vo = oracle.mul_proof_verify(n_bits, n_arr, stride, a["e_a"], a["e_b"], a["e_c"], f, z1, z2, e_d, e_db)
         vg = np.full(B, 9, np.uint8)
         ctx.mul_proof_verify(n_bits, B, n_arr, stride, a["e_a"], a["e_b"], a["e_c"], f, z1, z2, e_d, e_db, vg)
+        assert n_bits != 4096 or ctx.last_geometry() == ctx.test_geometry
         assert np.array_equal(vo, vg), (vo, vg)
         return list(vo)
     assert both(fo, z1o, z2o, edo, edbo) == [1, 1, 1, 0, 0, 0]
@@ -233,11 +249,13 @@ def test_gpu_mul_proof_matches_oracle(ctx, oracle, n_bits, shared):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits,shared,K", [(1024, False, 3), (2048, True, 2), (1024, True, 1)])
+@pytest.mark.parametrize("n_bits,shared,K", [(1024, False, 3), (2048, True, 2), (1024, True, 1), (4096, True, 2)])
 def test_gpu_correct_message_matches_oracle(ctx, oracle, n_bits, shared, K):
     kw = n_bits // 32
     if n_bits == 2048:
         pq = [H.fixture_key()]
+    elif n_bits == 4096:
+        pq = SC.keys_for(4096, 1)                  # the benchmark's key
     else:
         pq = [H.test_key(n_bits, tag=t) for t in range(1 if shared else 3)]
     keys = [k[2] for k in pq]
@@ -381,8 +399,45 @@ def test_mul_edge_cases_oracle_matches_python_model(oracle):
     assert pm.compute_digest([bt.ns[b]] + [SC.get_int(a[k], b) for k in ("e_a", "e_b", "e_c")] + [SC.get_int(o[3], b), SC.get_int(o[4], b)]) >> 248 == 0
 
 
+def test_keys_for_4096_bits_are_what_the_cases_need():
+    """CPU: the four 4096-bit moduli of small_proof_cases.keys_for — no prime is generated for them.  What the cases rely on: distinct odd
+    moduli of exactly 4096 bits, p a proper factor of n (r_c = p and e_db = k p then have no inverse modulo n^2), and p a factor of no
+    other key's modulus (an item built to have no inverse under its own key is an ordinary one under a neighbour's)"""
+    from importlib import import_module
+    ks = SC.keys_for(4096, 4)
+    assert len(ks) == 4 and len(set(n for p, q, n in ks)) == 4
+    assert ks[0] == tuple(import_module("zk-paillier_amd.synth").bench_key_4096())
+    for i, (p, q, n) in enumerate(ks):
+        assert n.bit_length() == 4096 and n & 1
+        assert 1 < p < n and n % p == 0 and q == n // p and p * q == n
+        assert H.is_probable_prime(p, rounds=4)
+        assert all(math.gcd(m, p) == 1 for j, (_, _, m) in enumerate(ks) if j != i)
+    assert [k[2] for k in SC.keys_for(4096, 3)] == [k[2] for k in ks[:3]]
+
+
+def test_mul_edge_cases_at_4096_bits_oracle_matches_python_model(oracle):
+    """CPU: the 4096-bit edge batch (per-proof keys: the benchmark's key and two products of pooled primes) is what it claims
+    (_check_mul_edges: f reaches 0 and n - 1, the sum that carries out of 128 words, z + n^2 accepted, all three verdicts among the edited
+    proofs), and the C oracle agrees with oracle/py_model.py on three of its items, proving and verifying: a, b, d with every limb set, the
+    `carry` item (a = b = d = n - 1) and an ordinary proof, whose f is 0 in the edited batch.  (Three items: one Enc takes CPython 0.7 s at
+    this width; the whole batch is compared at 1024 bits above.)"""
+    cs, o, st, vh, ed, over, wide_ed, ve = _mul_edges(oracle, 4096)
+    bt, a = cs["bt"], cs["a"]
+    assert bt.n_bits == 4096 and not bt.shared and len(set(bt.ns)) == 3
+    _check_mul_edges(cs, o, st, vh, ed, over, wide_ed, ve)
+    b_all, b_carry, b_ord = cs["all_set"], cs["carry"], cs["free"][0]
+    assert all(SC.get_int(a[k], b_all) == bt.top for k in ("a", "b", "d"))
+    assert all(SC.get_int(a[k], b_carry) == bt.ns[b_carry] - 1 for k in ("a", "b", "d"))
+    assert SC.get_int(ed["f"], b_ord) == 0 and SC.get_int(o[0], b_ord) != 0
+    for b in (b_all, b_carry, b_ord):
+        n = bt.ns[b]
+        assert tuple(SC.get_int(v, b) for v in o) == pm.mul_proof_prove(n, *[SC.get_int(a[k], b) for k in SC.MUL_IN]), b
+        got = ACCEPT if pm.mul_proof_verify(n, *[SC.get_int(ed[k], b) for k in ("e_a", "e_b", "e_c") + SC.MUL_OUT]) else REJECT
+        assert got == ve[b], b
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits", [1024, 2048])
+@pytest.mark.parametrize("n_bits", [1024, 2048, 4096])
 def test_gpu_mul_proof_operand_edges(ctx, oracle, n_bits):
     """a, b, d in {0, 1, n - 1, 2^n_bits - 1}, r_* in {1, n - 1, 2^n_bits - 1}, f = 0 and n - 1, a sum that carries out of kw words (k_modadd);
     z1, z2 >= n^2 (accepted), all ones, 0; e_d, e_db >= n^2, 0, 1, ragged, e_db = k p; a short challenge"""
@@ -392,6 +447,8 @@ def test_gpu_mul_proof_operand_edges(ctx, oracle, n_bits):
     g = tuple(SC.sentinel(v.shape) for v in o)
     sg = SC.sentinel(bt.B, np.uint8)
     ctx.mul_proof_prove(bt.n_bits, bt.B, bt.n_arr, bt.stride, *[a[k] for k in SC.MUL_IN], *g, sg)
+    if n_bits == 4096:
+        assert ctx.last_geometry() == ctx.test_geometry, "the call ran on another engine than the one this family pins"
     SC.assert_same(st, sg, "status")
     for name, x, y in zip(SC.MUL_OUT, o, g):
         SC.assert_same(x, y, name)
@@ -401,6 +458,7 @@ def test_gpu_mul_proof_operand_edges(ctx, oracle, n_bits):
     for stmt, proof, want in ((a, g, vh), (ed, [ed[k] for k in SC.MUL_OUT], ve)):
         vg = SC.sentinel(bt.B, np.uint8)
         ctx.mul_proof_verify(bt.n_bits, bt.B, bt.n_arr, bt.stride, stmt["e_a"], stmt["e_b"], stmt["e_c"], *proof, vg)
+        assert n_bits != 4096 or ctx.last_geometry() == ctx.test_geometry
         SC.assert_same(want, vg, "verdict")
 
 
@@ -544,8 +602,30 @@ def test_correct_message_edge_cases_oracle_matches_python_model(oracle):
     assert chal >> 248 == 0 and SC.get_int(o[1][b], cs["rows"][b]["valid"].index(cs["rows"][b]["msg"])) == chal
 
 
+def test_correct_message_edge_cases_at_4096_bits_oracle_matches_python_model(oracle):
+    """CPU: the 4096-bit edge batch (K = 3, per-proof keys: the benchmark's key and two products of pooled primes) is what it claims
+    (_check_cm_edges: the duplicate and the unlisted message, z + n and ciphertext + n^2 accepted, a rebalanced e_vec rejected, all three
+    verdicts among the edited proofs), and the C oracle agrees with oracle/py_model.py on three of its items, proving and verifying: the
+    simulated z at n - 1 and with every limb set, r = w = n - 1, and an ordinary proof, whose simulated z is n higher in the edited batch.
+    (Three items: one Enc takes CPython 0.7 s at this width; the whole batch is compared at 1024 bits above.)"""
+    cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1 = _cm_edges(oracle, 4096)
+    bt, K = cs["bt"], cs["K"]
+    assert bt.n_bits == 4096 and not bt.shared and len(set(bt.ns)) == 3
+    _check_cm_edges(cs, o, vh, proof, over, rebalanced, ve, k1, o1, v1)
+    b_all, b_n1, b_ord = cs["all_set"], cs["n_minus_1"], cs["free"][0]
+    assert cs["rows"][b_all]["z_sim"] == [bt.ns[b_all] - 1, bt.top]
+    assert cs["rows"][b_n1]["r"] == cs["rows"][b_n1]["w"] == bt.ns[b_n1] - 1
+    assert b_ord == over[0] and any(SC.get_int(proof[2][b_ord], k) > bt.ns[b_ord] for k in range(K))
+    for b in (b_all, b_n1, b_ord):
+        n, q = bt.ns[b], cs["rows"][b]
+        want = pm.correct_message_prove(n, q["valid"], q["msg"], q["r"], q["e_sim"], q["z_sim"], q["w"])
+        got = (SC.get_int(o[0], b), [SC.get_int(o[1][b], k) for k in range(K)], [SC.get_int(o[2][b], k) for k in range(K)], [SC.get_int(o[3][b], k) for k in range(K)])
+        assert o[4][b] == 0 and got == want, b
+        assert _model_cm_verify(n, q["valid"], *proof, b) == ve[b], b
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits", [1024, 2048])
+@pytest.mark.parametrize("n_bits", [1024, 2048, 4096])
 def test_gpu_correct_message_operand_edges(ctx, oracle, n_bits):
     """e_sim rows of 0 and 2^256 - 1 (k_cm_ei's borrow), r, w, z_sim at 0, 1, n - 1, 2^n_bits - 1, message 0, a message listed twice, an
     unlisted one (K = 3 and K = 1); e_vec rebalanced through 2^256 (k_cm_verdict's carry: REJECT, not MALFORMED), z + n and

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import small_proof_cases as SC
 from helpers import pm, L, zkp
 
 OUT_FIELDS = ("c1", "c2", "resp_kind", "resp_j", "resp_w1", "resp_r1", "resp_w2", "resp_r2")
@@ -96,11 +97,13 @@ def test_oracle_short_challenge_is_malformed(oracle):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_bits,key_bits,ef,shared", [(1024, 512, 40, True), (1024, 1024, 120, False), (2048, 2048, 40, True), (1024, 512, 1, True),
-                                                        (1024, 512, 256, True)])
+                                                        (1024, 512, 256, True), (4096, 4096, 3, True)])
 def test_gpu_interactive_matches_oracle(ctx, oracle, n_bits, key_bits, ef, shared):
     B = 4
     if key_bits == 2048:
         keys = [H.fixture_key()[2]]
+    elif key_bits == 4096:
+        keys = [SC.keys_for(4096, 1)[0][2]]        # the benchmark's key (no 2048-bit prime is generated here); 3 rows per proof: 24 Enc
     else:
         keys = [H.test_key(key_bits, tag=i)[2] for i in range(1 if shared else B)]
     cases = H.build_range_case(b"gpu-inter-%d-%d" % (n_bits, ef), keys, n_bits, B, shared=shared, ef=ef)

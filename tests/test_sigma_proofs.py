@@ -202,7 +202,7 @@ def test_sigma_edge_cases_oracle_matches_python_model(oracle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits", [1024, 2048])
+@pytest.mark.parametrize("n_bits", [1024, 2048, 4096])
 def test_gpu_zero_proof_operand_edges(ctx, oracle, n_bits):
     """r, r' in {1, n - 1, 2^n_bits - 1}; z >= n^2, all ones, 0; c and a >= n^2, 0, 1 and of ragged byte length; a short challenge"""
     cs, zo, ao, vh, ed, over, ve = _zero_edges(oracle, n_bits)
@@ -222,7 +222,7 @@ def test_gpu_zero_proof_operand_edges(ctx, oracle, n_bits):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits", [1024, 2048])
+@pytest.mark.parametrize("n_bits", [1024, 2048, 4096])
 def test_gpu_ciphertext_proof_operand_edges(ctx, oracle, n_bits):
     """x, x' in {0, 1, n - 1, 2^n_bits - 1} (both at the top: the maximal honest z1); z1 with all kw + 16 limbs set, z1 + k n (accepted);
     z2 >= n^2, all ones, 0; c and c' >= n^2, 0, 1 and of ragged byte length; a short challenge"""

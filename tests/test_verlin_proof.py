@@ -7,19 +7,31 @@ import small_proof_cases as SC
 from helpers import pm, L, zkp
 
 
-def make(n_bits, keys, B, seed, bad_last=True):
+def make(n_bits, keys, B, seed, bad_last=True, oracle=None):
+    """B statements with witness and nonces.  The statements (c, c', phi_x) are computed by the Python model, or — `oracle` given: the GPU
+    tests at 4096 bits, where one Enc takes CPython 0.7 s and gen_phi three times that — by the C oracle from the same inputs"""
     d = pm.Drbg(seed)
     kw = n_bits // 32
+    enc = (lambda n, m, r: (m, r)) if oracle else pm.enc
     rows = []
     for b in range(B):
         n = keys[b % len(keys)]
-        nn = n * n
-        c, cp = pm.enc(n, d.below(n), d.below(n)), pm.enc(n, d.below(n), d.below(n))       # the two public ciphertexts (verlin_proof.rs tests)
+        c, cp = enc(n, d.below(n), d.below(n)), enc(n, d.below(n), d.below(n))             # the two public ciphertexts (verlin_proof.rs tests)
         x, xp, xpp, rx = d.below(n), d.below(n), d.below(n), d.below(n)
-        phi_x = pm.gen_phi(n, c, cp, x, xp, xpp, rx)
+        rows.append(dict(n=n, c=c, cp=cp, phi_x=0, x=x, xp=xp, xpp=xpp, rx=rx, a=d.below(n), ap=d.below(n), app=d.below(n), ra=d.below(n)))
+    if oracle:
+        ns = L.ints_to_limbs([q["n"] for q in rows], kw)
+        wit = tuple(L.ints_to_limbs([q[k] for q in rows], kw) for k in ("x", "xp", "xpp", "rx"))
+        cs = [oracle.paillier_enc(n_bits, ns, kw, *(L.ints_to_limbs([q[k][i] for q in rows], kw) for i in (0, 1))) for k in ("c", "cp")]
+        # phi_x = gen_phi(c, c', x, x', x'', r_x): what the oracle's prover computes of its nonces (verlin_proof.rs:138-165)
+        phi = oracle.verlin_proof_prove(n_bits, ns, kw, cs[0], cs[1], np.zeros_like(cs[0]), wit, wit)[0]
+        for b, q in enumerate(rows):
+            q.update(c=L.limbs_to_int(cs[0][b]), cp=L.limbs_to_int(cs[1][b]), phi_x=L.limbs_to_int(phi[b]))
+    for b, q in enumerate(rows):
+        if not oracle:
+            q["phi_x"] = pm.gen_phi(q["n"], q["c"], q["cp"], q["x"], q["xp"], q["xpp"], q["rx"])
         if bad_last and b == B - 1:
-            phi_x = (phi_x * 2) % nn                                                         # statement no longer matches the witness
-        rows.append(dict(n=n, c=c, cp=cp, phi_x=phi_x, x=x, xp=xp, xpp=xpp, rx=rx, a=d.below(n), ap=d.below(n), app=d.below(n), ra=d.below(n)))
+            q["phi_x"] = (q["phi_x"] * 2) % (q["n"] * q["n"])                               # statement no longer matches the witness
     arr = lambda k, w: L.ints_to_limbs([q[k] for q in rows], w)
     a = {k: arr(k, 2 * kw if k in ("c", "cp", "phi_x") else kw) for k in rows[0]}
     return rows, a
@@ -39,15 +51,19 @@ def test_oracle_matches_python_model(oracle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits,shared", [(1024, False), (2048, True)])
+@pytest.mark.parametrize("n_bits,shared", [(1024, False), (2048, True), (4096, True)])
 def test_gpu_verlin_matches_oracle(ctx, oracle, n_bits, shared):
+    """(4096: the benchmark's key — 8192-bit n^2, the widest kernel geometry under the composition)"""
     kw = n_bits // 32
-    keys = [H.fixture_key()[2]] if n_bits == 2048 else [H.test_key(1024, tag=t)[2] for t in range(3)]
     B = 4
-    rows, a = make(n_bits, keys, B, b"verlin-gpu-%d" % n_bits)
+    oracle.set_threads(min(8, oracle.max_threads()))
+    if n_bits == 4096:
+        rows, a = SC.cached("verlin-gpu-4096", lambda: make(n_bits, [SC.keys_for(4096, 1)[0][2]], B, b"verlin-gpu-%d" % n_bits, oracle=oracle))
+    else:
+        keys = [H.fixture_key()[2]] if n_bits == 2048 else [H.test_key(1024, tag=t)[2] for t in range(3)]
+        rows, a = make(n_bits, keys, B, b"verlin-gpu-%d" % n_bits)
     n_arr = a["n"][:1] if shared else a["n"]
     stride = 0 if shared else kw
-    oracle.set_threads(min(8, oracle.max_threads()))
     wit, non = (a["x"], a["xp"], a["xpp"], a["rx"]), (a["a"], a["ap"], a["app"], a["ra"])
     o = oracle.verlin_proof_prove(n_bits, n_arr, stride, a["c"], a["cp"], a["phi_x"], wit, non)
     g = tuple(np.zeros_like(v) for v in o)
@@ -141,8 +157,31 @@ def test_verlin_edge_cases_oracle_matches_python_model(oracle):
     assert all(SC.get_int(o[k], 9) >> (1024 + 248) != 0 for k in (1, 2, 3))      # witness and nonces at 2^n_bits - 1: the maximal honest responses
 
 
+def test_verlin_edge_cases_at_4096_bits_oracle_matches_python_model(oracle):
+    """CPU: the 4096-bit edge batch (per-proof keys: the benchmark's key and two products of pooled primes) is what it claims — honest
+    proofs accepted, the over-wide z'' and r_z accepted, ACCEPT and REJECT both among the edited proofs — and the C oracle agrees with
+    oracle/py_model.py on three of its items, proving and verifying: witness and nonces with every limb set, witness and nonces at n - 1,
+    and an ordinary proof, which in the edited batch carries the z with all kw + 16 limbs set.  (Three items: one Enc takes CPython 0.7 s
+    at this width; the whole batch is compared at 1024 bits above.)"""
+    cs, o, vh, ed, over, ve = _verlin_edges(oracle, 4096)
+    bt, a = cs["bt"], cs["a"]
+    assert bt.n_bits == 4096 and not bt.shared and len(set(bt.ns)) == 3
+    SC.check_edge_verdicts(cs, vh, over, ve)
+    b_all, b_n1, b_ord = cs["all_set"], cs["n_minus_1"], cs["free"][0]
+    assert all(SC.get_int(a[k], b_all) == bt.top for k in SC.VERLIN_WIT + SC.VERLIN_NON)
+    assert all(SC.get_int(a[k], b_n1) == bt.ns[b_n1] - 1 for k in ("x", "xp", "xpp", "a", "ap", "app"))
+    assert SC.get_int(ed["z"], b_ord) == SC.ones(bt.kw + SC.EXTRA) and ve[b_ord] == SC.REJECT
+    for b in (b_all, b_n1, b_ord):
+        n = bt.ns[b]
+        st = [SC.get_int(a[k], b) for k in ("c", "cp", "phi_x")]
+        assert tuple(SC.get_int(v, b) for v in o) == pm.verlin_prove(n, *st, *[SC.get_int(a[k], b) for k in SC.VERLIN_WIT + SC.VERLIN_NON]), b
+        got = pm.verlin_verify(n, *[SC.get_int(ed[k], b) for k in ("c", "cp", "phi_x") + SC.VERLIN_OUT])
+        assert got == (ve[b] == SC.ACCEPT), b
+    assert all(SC.get_int(o[k], b_all) >> (4096 + 248) != 0 for k in (1, 2, 3))      # the maximal honest responses reach the extra limbs
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_bits", [1024, 2048])
+@pytest.mark.parametrize("n_bits", [1024, 2048, 4096])
 def test_gpu_verlin_operand_edges(ctx, oracle, n_bits):
     """witness and nonces in {0, 1, n - 1, 2^n_bits - 1}; z, z', z'' with all kw + 16 limbs set and k n higher (z'': accepted);
     r_z >= n^2, all ones, 0; c, c', phi_x, phi_a >= n^2, 0, 1, of ragged byte length; a short challenge"""
