@@ -63,7 +63,7 @@ def test_small_constants_everywhere():
     nonce_bits = val("wi_dlog_proof.K") + val("wi_dlog_proof.K_PRIME") + val("wi_dlog_proof.SAMPLE_S")
     assert nonce_bits == 512
     assert "BigInt::pow2(512)" in host
-    assert "modexp_core<G>(c, 512," in open(os.path.join(H.ROOT, "zk-paillier_amd", "csrc", "zkp_api_proofs.inc")).read()
+    assert "m.M.pow(512, g, r, 16, x," in open(os.path.join(H.ROOT, "zk-paillier_amd", "csrc", "zkp_api_proofs.inc")).read()
     oc = open(os.path.join(H.ROOT, "oracle", "zkp_oracle.c")).read()
     assert "v < 6370" in oc and pm.ALPHA == 6370
 

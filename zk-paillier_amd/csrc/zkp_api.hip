@@ -405,6 +405,11 @@ struct Stage {
     outs.clear();
     return st;
   }
+  // the end of an entry point whose body returned `body`: the copy-back, wipe and give-back run either way, the body's status comes first
+  int32_t finish(int32_t body) {
+    const int32_t fin = finish();
+    return body ? body : fin;
+  }
 };
 
 // ---- timing ---------------------------------------------------------------------------------
@@ -563,6 +568,24 @@ template <int G> static int32_t run_setup(zkp_ctx* c, const uint32_t* src, uint6
   uint32_t* tag = nullptr;
   if ((st = setup_tag(c, buf, count, &tag))) return st;
   hipLaunchKernelGGL(k_setup<G>, dim3(blocks), dim3(LL::THREADS), LL::BYTES_PER_BLOCK, c->stream, src, stride, src_words, square, count, (uint32_t*)buf.p, c->setup_flag, tag);
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+
+// THE two launch shapes of the kernels that are not ladders, each with its check.  launch_rows: one thread per row, 256 per block, no LDS, on
+// the ctx stream.
+template <class K, class... A> static int32_t launch_rows(zkp_ctx* c, K kernel, uint64_t rows, const A&... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, args...);
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+// launch_lanes: one item per lane with `words_per_lane` words of thread-interleaved LDS (k_modinv, k_jacobi, the coprime draws).  These kernels
+// are latency bound — dependent LDS / carry chains, data-dependent trip counts — so the blocks are small: divergence stays among LANES_PER_BLOCK
+// lanes and several wavefronts share a compute unit.
+constexpr int LANES_PER_BLOCK = 16;
+constexpr size_t LANE_LDS_BUDGET = 96 * 1024;      // bytes of LDS a block of lanes may take
+template <class K, class A> static int32_t launch_lanes(zkp_ctx* c, K kernel, uint64_t items, size_t words_per_lane, const A& args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((items + LANES_PER_BLOCK - 1) / LANES_PER_BLOCK)), dim3(LANES_PER_BLOCK), LANES_PER_BLOCK * words_per_lane * 4, c->stream, args);
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
 }
@@ -962,8 +985,7 @@ extern "C" int32_t zkp_diag_basen(zkp_ctx* c, uint32_t n_bits, const uint32_t* n
     else hipLaunchKernelGGL(k_diag_basen<BN_GB>, dim3(1), dim3(64), BASEN_DIAG_LDS, c->stream, (const uint32_t*)c->bn_consts.p, (int)op, dxa, dxb, dya, dyb, dout, dscr);
     if (hipGetLastError() != hipSuccess) st = ZKP_EDEVICE;
   }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 // diagnostic: did the most recent shared-key Paillier launch of this ctx run in base-n form?  out_lanes: lanes per n-sized integer of that
 // launch (0: there was none), out_qualified: the key passed k_setup_basen (else the n^2-sized kernel did the work)
@@ -1133,9 +1155,9 @@ extern "C" int32_t zkp_timing_get(zkp_ctx* c, double* ms, uint64_t* launches, ui
 } ZKP_CATCH(c)
 
 // ---- L1 primitives --------------------------------------------------------------------------
-// modexp over constants that are already set up in c->consts (per-item when const_stride != 0)
+// modexp over constants that are already set up in `consts` (one record, or one per item)
 template <int G>
-static int32_t modexp_core(zkp_ctx* c, uint32_t exp_bits, uint64_t count, const uint32_t* base, const uint32_t* exp, uint64_t exp_stride,
+static int32_t modexp_core(zkp_ctx* c, const DevBuf& consts, uint32_t exp_bits, uint64_t count, const uint32_t* base, const uint32_t* exp, uint64_t exp_stride,
                            bool per_item_mod, uint32_t* out, int io_words, int out_words = 0) {
   using CL = ConstLayout<G>;
   using LL = LdsLayout<G>;
@@ -1145,7 +1167,7 @@ static int32_t modexp_core(zkp_ctx* c, uint32_t exp_bits, uint64_t count, const 
     if (pair_ladder(c->route, G, count)) {                       // a few items on the latency engine: right-to-left ladder on pairs of groups
       unsigned long long* wcp = nullptr;
       if ((st = fresh_work_counter(c, &wcp))) return st;
-      ModexpArgs pa{base, exp, exp_stride, (const uint32_t*)c->consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, out, nullptr, count, (int)exp_bits, io_words,
+      ModexpArgs pa{base, exp, exp_stride, (const uint32_t*)consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, out, nullptr, count, (int)exp_bits, io_words,
                     out_words ? out_words : io_words, nullptr, wcp, {}, 0};
       const unsigned pair_blocks = (unsigned)std::max<uint64_t>(1, (count + LL::GROUPS_PER_BLOCK / 2 - 1) / (LL::GROUPS_PER_BLOCK / 2));
       {
@@ -1166,7 +1188,7 @@ static int32_t modexp_core(zkp_ctx* c, uint32_t exp_bits, uint64_t count, const 
   if (SLIDING_MODEXP && exp_stride == 0 && (st = build_schedule(c, exp, exp_bits, &sched))) return st;
   unsigned long long* wc = nullptr;
   if ((st = fresh_work_counter(c, &wc))) return st;
-  ModexpArgs a{base, exp, exp_stride, (const uint32_t*)c->consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, out, (uint32_t*)c->table.p, count, (int)exp_bits, io_words, out_words ? out_words : io_words, sched, wc, {}, 0};
+  ModexpArgs a{base, exp, exp_stride, (const uint32_t*)consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, out, (uint32_t*)c->table.p, count, (int)exp_bits, io_words, out_words ? out_words : io_words, sched, wc, {}, 0};
   {
     TimedRegion tr(c, count);
     bool launched = false;
@@ -1179,11 +1201,11 @@ static int32_t modexp_core(zkp_ctx* c, uint32_t exp_bits, uint64_t count, const 
   return ZKP_OK;
 }
 
-// Up to three exponentiations per item (per-item exponents, the same per-item moduli already set up in c->consts) in ONE
+// Up to three exponentiations per item (per-item exponents, the same per-item moduli already set up in `consts`) in ONE
 // launch: ModexpArgs::more.  Longest exponent first, so that the long chains start first.
 struct ModexpCall { uint32_t exp_bits; const uint32_t* base; const uint32_t* exp; uint64_t exp_stride; uint32_t* out; int io_words; int out_words; };
 template <int G>
-static int32_t modexp_multi(zkp_ctx* c, uint64_t count, bool per_item_mod, std::initializer_list<ModexpCall> calls_in) {
+static int32_t modexp_multi(zkp_ctx* c, const DevBuf& consts, uint64_t count, bool per_item_mod, std::initializer_list<ModexpCall> calls_in) {
   using CL = ConstLayout<G>;
   using LL = LdsLayout<G>;
   std::vector<ModexpCall> calls(calls_in);
@@ -1199,7 +1221,7 @@ static int32_t modexp_multi(zkp_ctx* c, uint64_t count, bool per_item_mod, std::
     // the launch fills the GPU anyway: one launch per exponentiation on the single-segment kernel (no segment bookkeeping in
     // its product loops)
     for (const ModexpCall& k : calls)
-      if ((st = modexp_core<G>(c, k.exp_bits, count, k.base, k.exp, k.exp_stride, per_item_mod, k.out, k.io_words, k.out_words))) return st;
+      if ((st = modexp_core<G>(c, consts, k.exp_bits, count, k.base, k.exp, k.exp_stride, per_item_mod, k.out, k.io_words, k.out_words))) return st;
     return ZKP_OK;
   }
   unsigned blocks = 0;
@@ -1208,7 +1230,7 @@ static int32_t modexp_multi(zkp_ctx* c, uint64_t count, bool per_item_mod, std::
   unsigned long long* wc = nullptr;
   if ((st = fresh_work_counter(c, &wc))) return st;
   const ModexpCall& f = calls[0];
-  ModexpArgs a{f.base, f.exp, f.exp_stride, (const uint32_t*)c->consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, f.out, (uint32_t*)c->table.p, count,
+  ModexpArgs a{f.base, f.exp, f.exp_stride, (const uint32_t*)consts.p, per_item_mod ? (uint64_t)CL::WORDS : 0, f.out, (uint32_t*)c->table.p, count,
                (int)f.exp_bits, f.io_words, f.out_words ? f.out_words : f.io_words, nullptr, wc, {}, (int)calls.size() - 1};
   for (size_t k = 1; k < calls.size(); k++) {
     const ModexpCall& m = calls[k];
@@ -1235,7 +1257,7 @@ static int32_t modexp_impl(zkp_ctx* c, uint32_t exp_bits, uint64_t count, const 
   if (st) return st;
   if ((st = run_setup<G>(c, mod, mod_stride, LL::NW, 0, nmod, c->consts))) return st;
   bool bad = false;
-  if ((st = modexp_core<G>(c, exp_bits, count, base, exp, exp_stride, mod_stride != 0, out, LL::NW))) return st;
+  if ((st = modexp_core<G>(c, c->consts, exp_bits, count, base, exp, exp_stride, mod_stride != 0, out, LL::NW))) return st;
   if ((st = read_setup_flag(c, &bad))) return st;
   if (bad) { c->err = "even or trivial modulus in batch (outputs of those items are untouched)"; return ZKP_ENONCANONICAL; }
   return ZKP_OK;
@@ -1258,8 +1280,7 @@ extern "C" int32_t zkp_modexp_batch(zkp_ctx* c, uint32_t mod_bits, uint32_t exp_
   uint32_t* dout = s.out(out, count * L);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(mod_bits), [&](auto G) { return modexp_impl<G()>(c, exp_bits, count, dbase, dexp, exp_stride, dmod, mod_stride, dout); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // THE launch of k_modmul<G>: out = a * b mod M under the constants in `consts` (one record, or one per item); a_words / b_words = 0: as out_words
@@ -1302,8 +1323,7 @@ extern "C" int32_t zkp_modmul_batch(zkp_ctx* c, uint32_t mod_bits, uint64_t coun
   uint32_t* dout = s.out(out, count * L);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(mod_bits), [&](auto G) { return modmul_impl<G()>(c, count, da, db, dm, mod_stride, dout); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // Paillier contexts: modulus n^2, group size from 2*n_bits
@@ -1359,8 +1379,7 @@ extern "C" int32_t zkp_paillier_enc_batch(zkp_ctx* c, uint32_t n_bits, uint64_t 
   uint32_t* dout = s.out(out_c, count * 2 * kw);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return enc_impl<G()>(c, n_bits, count, dn, n_stride, dm, dr, dout); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // Enc-and-compare (CorrectOpening::verify_opening, correct_opening.rs:17-30; the verifier's equality tests range_proof.rs:280-298,324-337)
@@ -1391,9 +1410,91 @@ extern "C" int32_t zkp_paillier_enc_check_batch(zkp_ctx* c, uint32_t n_bits, uin
   uint8_t* dok = s.out(out_ok, count);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return enc_check_impl<G()>(c, n_bits, count, dn, n_stride, dm, dr, da, db, dok); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
+
+// ---- the composer of the small proofs ---------------------------------------------------------------------------------------------------
+// THE launch of k_modinv: out = a^-1 mod `mod` per item (kernels_inv.hpp), five operand arrays per lane in LDS
+static int32_t launch_modinv(zkp_ctx* c, uint64_t count, int kw, const uint32_t* a, uint64_t a_stride, const uint32_t* mod, uint64_t mod_stride,
+                             uint32_t* out, uint64_t out_stride, uint8_t* status) {
+  static_assert(LANES_PER_BLOCK * modinv_lds_words_per_lane(8192 / 32) * 4 <= LANE_LDS_BUDGET, "a block of lanes of the widest operand (8192 bits) must fit its LDS");
+  return launch_lanes(c, k_modinv, count, modinv_lds_words_per_lane(kw), ModinvArgs{a, a_stride, mod, mod_stride, out, out_stride, status, count, kw});
+}
+// n^2 as 32-bit words for the inverse kernel: [keys][2kw]
+static int32_t square_words(zkp_ctx* c, const uint32_t* n, uint64_t n_stride, int kw, uint64_t nkeys, uint32_t* out) {
+  hipLaunchKernelGGL(k_square_words, dim3((unsigned)((nkeys + 63) / 64)), dim3(64), 0, c->stream, n, n_stride, kw, nkeys, out);
+  HIPCHK(c, hipGetLastError());
+  return ZKP_OK;
+}
+static int32_t hash_list(zkp_ctx* c, uint64_t batch, std::initializer_list<HashOp> ops, uint32_t* e) {
+  HashListArgs h{};
+  for (const HashOp& o : ops) h.op[h.nops++] = o;
+  h.batch = batch; h.e = e;
+  return launch_rows(c, k_hash_list, batch, h);
+}
+
+// The modular arithmetic of ONE call of a small proof (Zero / Ciphertext / Verlin / Mul / CorrectMessage / CompositeDLog, Legendre, the DLog
+// set-up), built once per *_impl: the ctx, the batch, shared or per-item keys, kw, and a sticky status.  Every operation is one line of the
+// body and launches nothing once an earlier one has failed; the body ends in `return m.st`.  The two moduli of a call are the members M and n:
+// each binds a constants buffer to the group its kernels are instantiated for, so the two cannot be mismatched.
+//   M  c->consts,  group G          the modulus the proof works under: n^2 (set up with square = 1), or N / p themselves (DLog, Legendre)
+//   n  c->consts2, group N_GROUP<G> the Paillier modulus n, for the responses that are reduced mod n
+// `count` = 0 means the batch of the composer (CorrectMessageProof composes over its B * K rows and names B where a step runs per proof).
+template <int G> struct Compose {
+  template <int GG> struct Ring {
+    Compose& m; DevBuf& consts;
+    const uint32_t* cst() const { return (const uint32_t*)consts.p; }
+    uint64_t cst_stride() const { return m.per ? (uint64_t)ConstLayout<GG>::WORDS : 0; }
+    void setup(const uint32_t* src, uint64_t stride, int square, uint64_t nkeys = 0) {
+      if (!m.st) m.st = run_setup<GG>(m.c, src, stride, (int)m.kw, square, nkeys ? nkeys : m.per ? m.batch : 1, consts);
+    }
+    // out = a * b mod the ring's modulus; a_words / b_words = 0: as out_words
+    void mul(const uint32_t* a, int a_words, const uint32_t* b, int b_words, uint32_t* out, int out_words, uint64_t count = 0) {
+      if (!m.st) m.st = modmul_ctx<GG>(m.c, consts, m.per, count ? count : m.batch, a, a_words, b, b_words, out, out_words);
+    }
+    // out = base^exp; out_words = 0: as io_words
+    void pow(uint32_t exp_bits, const uint32_t* base, const uint32_t* exp, uint64_t exp_stride, uint32_t* out, int io_words, int out_words = 0, uint64_t count = 0) {
+      if (!m.st) m.st = modexp_core<GG>(m.c, consts, exp_bits, count ? count : m.batch, base, exp, exp_stride, m.per, out, io_words, out_words);
+    }
+    void pow_multi(std::initializer_list<ModexpCall> calls) { if (!m.st) m.st = modexp_multi<GG>(m.c, consts, m.batch, m.per, calls); }
+  };
+  zkp_ctx* const c;
+  const uint64_t batch;
+  const bool per;                   // one key per item (else one for the call)
+  const uint32_t kw;
+  int32_t st = ZKP_OK;
+  const uint32_t* nn = nullptr;     // n^2 as words, one row per key (square_words)
+  Ring<G> M{*this, c->consts};
+  Ring<N_GROUP<G>> n{*this, c->consts2};
+  Compose(zkp_ctx* c_, uint64_t batch_, bool per_, uint32_t kw_) : c(c_), batch(batch_), per(per_), kw(kw_) {}
+  Compose(const Compose&) = delete;
+  Compose& operator=(const Compose&) = delete;
+  // the ctx's scratch slot `slot`, grown to `count` values; null once a step has failed
+  template <class T = uint32_t> T* buf(int slot, size_t count) {
+    if (!st) st = ensure(c, c->scratch[slot], count * sizeof(T));
+    return st ? nullptr : (T*)c->scratch[slot].p;
+  }
+  // Enc(m, r) under M's constants (enc_launch: n^2)
+  void enc(const uint32_t* key, uint64_t key_stride, const uint32_t* msg, int m_words, const uint32_t* r, int r_words, uint32_t* out, uint64_t count = 0) {
+    if (!st) st = enc_launch<G>(c, kw * 32, count ? count : batch, key, key_stride, msg, m_words, r, r_words, out);
+  }
+  // mod_inv mod n^2 and the words of n^2 it reads
+  void square_words(const uint32_t* key, uint64_t key_stride, uint64_t nkeys) {
+    uint32_t* w = buf(S_MP_NN, nkeys * 2 * kw);
+    if (!st) st = ::square_words(c, key, key_stride, (int)kw, nkeys, w);
+    nn = w;
+  }
+  void inv(const uint32_t* a, uint32_t* out, uint8_t* status) {
+    if (!st) st = launch_modinv(c, batch, (int)(2 * kw), a, 2 * kw, nn, per ? 2 * kw : 0, out, 2 * kw, status);
+  }
+  void hash(std::initializer_list<HashOp> ops, uint32_t* e, uint64_t count = 0) { if (!st) st = hash_list(c, count ? count : batch, ops, e); }
+  // a one-thread-per-row kernel of the body's own (launch_rows)
+  template <class K, class... A> void rows(K kernel, uint64_t count, const A&... args) { if (!st) st = launch_rows(c, kernel, count, args...); }
+  // verdict = lhs == rhs, word for word (MALFORMED under a key M's set-up rejected)
+  void compare(const uint32_t* lhs, const uint32_t* rhs, uint32_t words, uint8_t* verdict) {
+    rows(k_words_compare, batch, WordsCmpArgs{lhs, rhs, M.cst(), M.cst_stride(), ConstLayout<G>::OFF_ST, words, batch, verdict});
+  }
+};
 
 #include "zkp_api_proofs.inc"
 #include "zkp_api_mul.inc"

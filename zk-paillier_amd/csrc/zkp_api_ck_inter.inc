@@ -41,18 +41,15 @@ static int32_t cki_challenge_impl(zkp_ctx* c, Stage& s, uint32_t n_bits, uint64_
   int32_t st;
   if ((st = run_setup<G>(c, nrow, per_row ? kw : 0, (int)kw, 0, nrows, c->consts))) return st;
   // sn | rn: 2 K B rows with the n_bits-bit exponent n
-  if ((st = modexp_core<G>(c, n_bits, 2 * items, base, nrow, per_row ? kw : 0, per_row, pw, (int)kw))) return st;
+  if ((st = modexp_core<G>(c, c->consts, n_bits, 2 * items, base, nrow, per_row ? kw : 0, per_row, pw, (int)kw))) return st;
   if ((st = hash_list(c, B, {{n, n_stride, 0, kw, 1}, {pw, (uint64_t)K * kw, kw, kw, K}, {pw + items * kw, (uint64_t)K * kw, kw, kw, K}}, out_e))) return st;
-  hipLaunchKernelGGL(k_repeat_rows, dim3((unsigned)((items * 8 + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)out_e, (uint64_t)8, 8u, K, items, erow);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_rows(c, k_repeat_rows, items * 8, (const uint32_t*)out_e, (uint64_t)8, 8u, K, items, erow))) return st;
   // s^e: K B rows with a 256-bit exponent, under the records of the first K B rows
-  if ((st = modexp_core<G>(c, 256, items, base, erow, 8, per_row, se, (int)kw))) return st;
+  if ((st = modexp_core<G>(c, c->consts, 256, items, base, erow, 8, per_row, se, (int)kw))) return st;
   if ((st = modmul_ctx<G>(c, c->consts, per_row, items, base + items * kw, 0, se, 0, out_z, (int)kw))) return st;
   if (out_sd && (st = hash_list(c, B, {{ds, (uint64_t)K * kw, kw, kw, K}}, out_sd))) return st;
   CkiChalFinishArgs fa{pw, status, out_sn, out_z, out_e, out_sd, items, K, (int)kw};
-  hipLaunchKernelGGL(k_cki_chal_finish, dim3((unsigned)((items * kw + 255) / 256)), dim3(256), 0, c->stream, fa);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  return launch_rows(c, k_cki_chal_finish, items * kw, fa);
 }
 
 // both challenge calls: seed null = the caller's s and r
@@ -86,8 +83,7 @@ static int32_t cki_challenge(zkp_ctx* c, uint32_t n_bits, uint64_t batch, uint32
   if (!st) st = with_group<GA, GB>(group_for_bits(n_bits < 2048 ? 2048 : n_bits), [&](auto G) {
     return cki_challenge_impl<G()>(c, s, n_bits, batch, K, dn, n_stride, dsv, drv, dsn, de, dz, dsd, dst, seed != nullptr);
   });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 extern "C" int32_t zkp_correct_key_challenge_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, uint32_t K, const uint32_t* n, uint64_t n_stride,
@@ -184,8 +180,7 @@ extern "C" int32_t zkp_correct_key_prove_batch(zkp_ctx* c, uint32_t n_bits, uint
   int32_t st;
   if ((st = crt_keys_prepare(c, s, dp, dq, hw, batch, hw, false, &k))) return st;
   CkiProveSplitArgs sa{dsn, dz, de, dn, dp, dq, k.dp, k.dq, k.kst, r.mods, r.base, r.exps, items, K, (int)hw, (int)rw};
-  hipLaunchKernelGGL(k_cki_prove_split, dim3((unsigned)((2 * items + lanes - 1) / lanes)), dim3(lanes), lanes * cki_prove_split_lds_words_per_lane((int)hw) * 4, c->stream, sa);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_lanes(c, k_cki_prove_split, 2 * items, cki_prove_split_lds_words_per_lane((int)hw), sa))) return st;
   SecretLadder<GA> ladder{c};
   if ((st = ladder.take(s, rows)) || (st = ladder.run(n_bits / 2, rows, r.mods, r.base, r.exps, hw, r.lad))) return st;
   CkiProveFinishArgs fa{r.lad, dp, dq, k.pinv, k.pinv_stride, k.kst, rn, root, items, K, (int)hw, (int)rw};
@@ -196,7 +191,6 @@ extern "C" int32_t zkp_correct_key_prove_batch(zkp_ctx* c, uint32_t n_bits, uint
   if ((st = hash_list(c, batch, {{dn, kw, 0, kw, 1}, {dsn, (uint64_t)K * kw, kw, kw, K}, {rn, (uint64_t)K * kw, kw, kw, K}}, echk))) return st;
   if ((st = hash_list(c, batch, {{root, (uint64_t)K * kw, kw, kw, K}}, dsd))) return st;
   CkiProveMergeArgs ma{share, k.kst, de, echk, dsd, derr, batch, K};
-  hipLaunchKernelGGL(k_cki_prove_merge, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, ma);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_rows(c, k_cki_prove_merge, batch, ma))) return st;
   return s.finish();
 } ZKP_CATCH(c)

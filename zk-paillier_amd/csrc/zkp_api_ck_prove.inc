@@ -29,7 +29,6 @@ extern "C" int32_t zkp_correct_key_ni_prove_batch(zkp_ctx* c, uint32_t n_bits, u
   uint8_t* hash_verdict = s.scratch<uint8_t>(batch);
   if (!dst) dst = s.scratch<uint8_t>(batch);
   if (s.st) return s.st;
-  const int lanes = 16;                                      // as zkp_paillier_open_batch: one value per lane, small blocks keep divergence local
   hipLaunchKernelGGL(k_ck_prove_n, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, c->stream, dp, dq, (int)hw, batch, dn);
   CkHashArgs h{dn, (uint32_t)kw, batch, dsalt, salt_len, mgf, hash_verdict, nullptr, 0};
   if (batch <= 4ull * (uint64_t)c->route.cus) hipLaunchKernelGGL(k_ck_hash_wave, dim3((unsigned)batch), dim3(64), 0, c->stream, h);     // (ck_verify_impl's rule)
@@ -39,12 +38,10 @@ extern "C" int32_t zkp_correct_key_ni_prove_batch(zkp_ctx* c, uint32_t n_bits, u
   int32_t st;
   if ((st = crt_keys_prepare(c, s, dp, dq, hw, batch, hw, false, &k))) return st;
   CkProveSplitArgs sa{mgf, dp, dq, k.dp, k.dq, k.kst, r.mods, r.base, r.exps, items, (int)hw, (int)rw};
-  hipLaunchKernelGGL(k_ck_prove_split, dim3((unsigned)((rows + lanes - 1) / lanes)), dim3(lanes), lanes * ck_prove_split_lds_words_per_lane((int)hw) * 4, c->stream, sa);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_lanes(c, k_ck_prove_split, rows, ck_prove_split_lds_words_per_lane((int)hw), sa))) return st;
   SecretLadder<GA> ladder{c};
   if ((st = ladder.take(s, rows)) || (st = ladder.run(n_bits / 2, rows, r.mods, r.base, r.exps, hw, r.lad))) return st;
   CkProveFinishArgs fa{r.lad, dp, dq, k.pinv, k.pinv_stride, k.kst, dn, dsg, dst, items, (int)hw, (int)rw};
-  hipLaunchKernelGGL(k_ck_prove_finish, dim3((unsigned)((items + lanes - 1) / lanes)), dim3(lanes), lanes * pd_crt_lds_words_per_lane((int)hw) * 4, c->stream, fa);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_lanes(c, k_ck_prove_finish, items, pd_crt_lds_words_per_lane((int)hw), fa))) return st;
   return s.finish();
 } ZKP_CATCH(c)

@@ -2,13 +2,7 @@
 // included by zkp_api.hip.  The Jacobi kernel is the new arithmetic; the rest composes launch_modinv and the modexp ladder.
 
 static int32_t launch_jacobi(zkp_ctx* c, uint64_t count, uint32_t kw, const uint32_t* a, const uint32_t* n, uint64_t n_stride, int32_t* symbol, uint8_t* status) {
-  // As launch_modinv: latency-bound, data-dependent trip counts — small blocks keep divergence among 16 lanes; two operands per lane are
-  // 32 KB of LDS per block at kw = 256.
-  const int lanes = 16;
-  JacobiArgs q{a, n, n_stride, symbol, status, count, (int)kw};
-  hipLaunchKernelGGL(k_jacobi, dim3((unsigned)((count + lanes - 1) / lanes)), dim3(lanes), lanes * jacobi_lds_words_per_lane(kw) * 4, c->stream, q);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  return launch_lanes(c, k_jacobi, count, jacobi_lds_words_per_lane(kw), JacobiArgs{a, n, n_stride, symbol, status, count, (int)kw});
 }
 
 extern "C" int32_t zkp_jacobi_batch(zkp_ctx* c, uint32_t mod_bits, uint64_t count, const uint32_t* a, const uint32_t* n, uint64_t n_stride,
@@ -26,18 +20,17 @@ extern "C" int32_t zkp_jacobi_batch(zkp_ctx* c, uint32_t mod_bits, uint64_t coun
   uint8_t* dst = s.out(out_status, count);
   int32_t st = s.st;
   if (!st) st = launch_jacobi(c, count, (uint32_t)kw, da, dn, n_stride, dsym, dst);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // legendre_symbol (wi_dlog_proof.rs:94-107): ls = a^((p - 1) / 2) mod p on the modexp ladder, between the kernel that writes the exponent
 // and the one that compares ls with 1
 template <int G>
 static int32_t legendre_impl(zkp_ctx* c, uint32_t mod_bits, uint64_t count, const LegendreArgs& q, uint32_t* ls) {
-  using LL = LdsLayout<G>;
-  int32_t st;
-  if ((st = run_setup<G>(c, q.p, q.p_stride, LL::NW, 0, q.p_stride ? count : 1, c->consts))) return st;
-  return modexp_core<G>(c, mod_bits, count, q.base, q.exp, (uint64_t)q.kw, q.p_stride != 0, ls, LL::NW);
+  Compose<G> m(c, count, q.p_stride != 0, LdsLayout<G>::NW);
+  m.M.setup(q.p, q.p_stride, 0);
+  m.M.pow(mod_bits, q.base, q.exp, (uint64_t)q.kw, ls, LdsLayout<G>::NW);
+  return m.st;
 }
 
 extern "C" int32_t zkp_legendre_batch(zkp_ctx* c, uint32_t mod_bits, uint64_t count, const uint32_t* a, const uint32_t* p, uint64_t p_stride,
@@ -65,26 +58,24 @@ extern "C" int32_t zkp_legendre_batch(zkp_ctx* c, uint32_t mod_bits, uint64_t co
   if (!st) {
     // (an item outside the domain: base and exponent zero; under an even p the ladder stores nothing, so ls starts as zero)
     HIPCHK(c, hipMemsetAsync(ls, 0, count * kw * 4, c->stream));
-    hipLaunchKernelGGL(k_legendre_prep, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, q);
-    HIPCHK(c, hipGetLastError());
+    if ((st = launch_rows(c, k_legendre_prep, count, q))) return st;
     st = with_group<GA, GB, GC>(group_for_bits(mod_bits), [&](auto G) { return legendre_impl<G()>(c, mod_bits, count, q, ls); });
   }
   if (!st) {
     q.ls = ls;
-    hipLaunchKernelGGL(k_legendre_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, q);
-    if (hipGetLastError() != hipSuccess) { c->err = "k_legendre_finish launch"; st = ZKP_EDEVICE; }
+    st = launch_rows(c, k_legendre_finish, count, q);
   }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // ni = (h1^-1)^secret mod N under per-statement moduli (an even N: k_setup refuses it and the ladder stores nothing)
 template <int G>
 static int32_t dlog_setup_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* N, const uint32_t* h1inv, const uint32_t* secret, uint32_t* ni) {
   const uint32_t kw = n_bits / 32;
-  int32_t st;
-  if ((st = run_setup<G>(c, N, kw, (int)kw, 0, batch, c->consts))) return st;
-  return modexp_core<G>(c, 256, batch, h1inv, secret, 8, true, ni, (int)kw);
+  Compose<G> m(c, batch, true, kw);
+  m.M.setup(N, kw, 0);
+  m.M.pow(256, h1inv, secret, 8, ni, (int)kw);
+  return m.st;
 }
 
 extern "C" int32_t zkp_dlog_statement_setup_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* N, const uint8_t* seed,
@@ -110,18 +101,12 @@ extern "C" int32_t zkp_dlog_statement_setup_seeded_batch(zkp_ctx* c, uint32_t n_
   int32_t st = s.st;
   if (!st) {
     HIPCHK(c, hipMemsetAsync(dni, 0, batch * kw * 4, c->stream));
-    const int lanes = 16;                           // (as nonce_sample_launch's coprime draw)
     NonceJacobiArgs q{key, dN, dg, dsec, ds, first_index, batch, (uint32_t)kw, ZKP_SEEDED_KIND_DLOG_SETUP, RANGE_SAMPLE_MAX_ATTEMPTS};
-    hipLaunchKernelGGL(k_nonce_jacobi, dim3((unsigned)((batch + lanes - 1) / lanes)), dim3(lanes), lanes * jacobi_lds_words_per_lane((uint32_t)kw) * 4, c->stream, q);
-    HIPCHK(c, hipGetLastError());
+    st = launch_lanes(c, k_nonce_jacobi, batch, jacobi_lds_words_per_lane((uint32_t)kw), q);
     // (h1 / N) == -1 implies gcd(h1, N) == 1: every statement that has an h1 has its inverse; the zero h1 of a MALFORMED one gets zero
-    st = launch_modinv(c, batch, (int)kw, dg, kw, dN, kw, h1inv, kw, invst);
+    if (!st) st = launch_modinv(c, batch, (int)kw, dg, kw, dN, kw, h1inv, kw, invst);
   }
   if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return dlog_setup_impl<G()>(c, n_bits, batch, dN, h1inv, dsec, dni); });
-  if (!st) {
-    hipLaunchKernelGGL(k_dlog_setup_finish, dim3((unsigned)((batch * kw + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)ds, dni, (uint32_t)kw, (uint64_t)batch);
-    HIPCHK(c, hipGetLastError());
-  }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  if (!st) st = launch_rows(c, k_dlog_setup_finish, batch * kw, (const uint8_t*)ds, dni, (uint32_t)kw, (uint64_t)batch);
+  return s.finish(st);
 } ZKP_CATCH(c)

@@ -6,8 +6,9 @@
 // The ladder under secret moduli.  Here they are p^2, q^2, p and q (or prime candidates): k_setup stores them, R^2 mod p and the rest of the
 // Montgomery record in the constants buffer, and the ladder fills the window tables with powers of c mod p^2 (gcd(c - (c mod p^2), n) = p).
 // Every other caller of run_setup passes public moduli and uses the ctx's own persistent buffers; here both are blocks of the call's Stage,
-// registered secret, that stand in for c->consts and c->table for the length of a run.  The ctx's own buffers — the cached record of a key
-// among them — are untouched.  take() sizes the two blocks for the most rows any run of the call has (both sizes grow with the rows).
+// registered secret: the constants block is what run_setup and modexp_core are given, the table block stands in for c->table for the length
+// of a run.  The ctx's own buffers — the cached record of a key among them — are untouched.  take() sizes the two blocks for the most rows
+// any run of the call has (both sizes grow with the rows).
 template <int G>
 struct SecretLadder {
   zkp_ctx* c; void* cp = nullptr; void* tp = nullptr; size_t cbytes = 0, tbytes = 0;
@@ -20,20 +21,20 @@ struct SecretLadder {
     return s.st;
   }
   int32_t run(uint32_t exp_bits, uint64_t rows, const uint32_t* mods, const uint32_t* base, const uint32_t* exps, uint64_t exp_stride, uint32_t* out) {
+    // (the constants are an argument of both launchers; the window tables are the ctx's, so that block is swapped in)
     struct Borrowed {
-      zkp_ctx* c; DevBuf consts, table;
-      Borrowed(zkp_ctx* c_, void* cp, size_t cbytes, void* tp, size_t tbytes) : c(c_) {
-        consts.p = cp; consts.cap = cbytes; table.p = tp; table.cap = tbytes;
-        std::swap(c->consts, consts); std::swap(c->table, table);
-      }
+      zkp_ctx* c; DevBuf table;
+      Borrowed(zkp_ctx* c_, void* tp, size_t tbytes) : c(c_) { table.p = tp; table.cap = tbytes; std::swap(c->table, table); }
       Borrowed(const Borrowed&) = delete;
       Borrowed& operator=(const Borrowed&) = delete;
-      ~Borrowed() { std::swap(c->consts, consts); std::swap(c->table, table); }
-    } borrowed(c, cp, cbytes, tp, tbytes);
+      ~Borrowed() { std::swap(c->table, table); }
+    } borrowed(c, tp, tbytes);
+    DevBuf consts;
+    consts.p = cp; consts.cap = cbytes;
     using LL = LdsLayout<G>;
     int32_t st;
-    if ((st = run_setup<G>(c, mods, LL::NW, LL::NW, 0, rows, c->consts))) return st;
-    return modexp_core<G>(c, exp_bits, rows, base, exps, exp_stride, true, out, LL::NW);
+    if ((st = run_setup<G>(c, mods, LL::NW, LL::NW, 0, rows, consts))) return st;
+    return modexp_core<G>(c, consts, exp_bits, rows, base, exps, exp_stride, true, out, LL::NW);
   }
 };
 
@@ -52,16 +53,11 @@ static int32_t crt_keys_prepare(zkp_ctx* c, Stage& s, const uint32_t* dp, const 
   uint32_t *dpe = s.secret_scratch<uint32_t>(nkeys * hw), *dqe = s.secret_scratch<uint32_t>(nkeys * hw);
   uint8_t *inv_st = s.scratch<uint8_t>(4 * nkeys), *kst = s.scratch<uint8_t>(nkeys);
   if (s.st) return s.st;
-  const int lanes = 16;                                      // as launch_modinv: one value per lane, small blocks keep divergence local
-  const unsigned key_blocks = (unsigned)((nkeys + lanes - 1) / lanes);
-  const size_t lds = lanes * pdec_key_lds_words_per_lane((int)hw) * 4;
   PdecKeyArgs ka{dp, dq, key_stride, inv_a, inv_m, inv, inv_st, hp, hq, dpe, dqe, kst, nkeys, (int)hw};
-  hipLaunchKernelGGL(k_pdec_key_a, dim3(key_blocks), dim3(lanes), lds, c->stream, ka);
-  HIPCHK(c, hipGetLastError());
   int32_t st;
+  if ((st = launch_lanes(c, k_pdec_key_a, nkeys, pdec_key_lds_words_per_lane((int)hw), ka))) return st;
   if ((st = launch_modinv(c, 4 * nkeys, (int)hw, inv_a, hw, inv_m, hw, inv, hw, inv_st))) return st;
-  hipLaunchKernelGGL(k_pdec_key_b, dim3(key_blocks), dim3(lanes), lds, c->stream, ka);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_lanes(c, k_pdec_key_b, nkeys, pdec_key_lds_words_per_lane((int)hw), ka))) return st;
   *out = CrtKeys{inv, inv + hw, 4 * hw, dpe, dqe, hp, hq, kst};
   return ZKP_OK;
 }
@@ -102,7 +98,6 @@ extern "C" int32_t zkp_paillier_open_batch(zkp_ctx* c, uint32_t n_bits, uint64_t
   const LadderRows r = ladder_rows_take(s, rows, rw, hw);
   if (!dst) dst = s.scratch<uint8_t>(count);
   if (s.st) return s.st;
-  const int lanes = 16;                                      // as crt_keys_prepare
   hipLaunchKernelGGL(k_square_words, dim3((unsigned)((nkeys + 63) / 64)), dim3(64), 0, c->stream, dp, key_stride, (int)hw, nkeys, p2);
   hipLaunchKernelGGL(k_square_words, dim3((unsigned)((nkeys + 63) / 64)), dim3(64), 0, c->stream, dq, key_stride, (int)hw, nkeys, q2);
   HIPCHK(c, hipGetLastError());
@@ -110,8 +105,7 @@ extern "C" int32_t zkp_paillier_open_batch(zkp_ctx* c, uint32_t n_bits, uint64_t
   int32_t st;
   if ((st = crt_keys_prepare(c, s, dp, dq, key_stride, nkeys, hw, true, &k))) return st;
   PdecSplitArgs sa{dc, dp, dq, key_stride, p2, q2, k.dp, k.dq, k.kst, r.mods, r.base, r.exps, count, (int)hw, (int)rw, out_r ? 1 : 0};
-  hipLaunchKernelGGL(k_pdec_split, dim3((unsigned)((2 * count + lanes - 1) / lanes)), dim3(lanes), lanes * pdec_split_lds_words_per_lane((int)hw) * 4, c->stream, sa);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_lanes(c, k_pdec_split, 2 * count, pdec_split_lds_words_per_lane((int)hw), sa))) return st;
   st = with_group<GA, GB>(group_for_bits(mod_bits), [&](auto G) {
     SecretLadder<G()> ladder{c};
     const int32_t e = ladder.take(s, rows);
@@ -119,7 +113,6 @@ extern "C" int32_t zkp_paillier_open_batch(zkp_ctx* c, uint32_t n_bits, uint64_t
   });
   if (st) return st;
   PdecFinishArgs fa{r.lad, dp, dq, key_stride, k.hp, k.hq, k.pinv, k.pinv_stride, k.kst, dm, dr, dst, count, (int)hw, (int)rw};
-  hipLaunchKernelGGL(k_pdec_finish, dim3((unsigned)((count + lanes - 1) / lanes)), dim3(lanes), lanes * pd_crt_lds_words_per_lane((int)hw) * 4, c->stream, fa);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_lanes(c, k_pdec_finish, count, pd_crt_lds_words_per_lane((int)hw), fa))) return st;
   return s.finish();
 } ZKP_CATCH(c)

@@ -165,8 +165,7 @@ static int32_t range_prove_entry(zkp_ctx* c, const char* name, const zkp_range_n
     }
     for (size_t k = 0; k < nb && !st; k++) st = pp.d2h(blocks[k], blocks[k + 1], c->ev_pipe[2 * k + 1]);
     const int32_t fc = pp.finish();
-    const int32_t fin = s.finish();
-    return st ? st : (fc ? fc : fin);
+    return s.finish(st ? st : fc);
   }
   zkp_range_ni_proofs d = *p;
   d.n = s.in(p->n, p->n_stride ? B * kw : kw);
@@ -192,8 +191,7 @@ static int32_t range_prove_entry(zkp_ctx* c, const char* name, const zkp_range_n
   if (!st && !ds) { st = ensure(c, c->scratch[S_STATUS], B); ds = (uint8_t*)c->scratch[S_STATUS].p; }
   if (!st && ef == 0) HIPCHK(c, hipMemsetAsync(ds, 0, B, c->stream));   // no rows: nothing can go wrong
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * p->n_bits), [&](auto G) { return range_prove_impl<G()>(c, d, dw, de, dl, ds, ef, phases, dei, deli); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 // ---- a RangeProofNi call as TWO concurrent calls: where route_plan.hpp's range_split cuts it ------------------------------------------------
@@ -296,8 +294,7 @@ static int32_t range_sample_launch(zkp_ctx* c, const zkp_range_ni_proofs& d, uin
   a.third = (uint32_t*)c->scratch[S_SAMPLE_THIRD].p; a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p;
   a.w1 = w1; a.w2 = w2; a.r1 = r1; a.r2 = r2; a.status = status;
   a.first_index = first_index; a.batch = B; a.kw = kw; a.ef = ef; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
-  hipLaunchKernelGGL(k_range_sample_prep, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_rows(c, k_range_sample_prep, B, a))) return st;
   if (rows == 0) return ZKP_OK;
   const uint64_t G = kw / 16;
   const unsigned sample_blocks = (unsigned)((3 * rows * G + 255) / 256), fix_blocks = (unsigned)((rows * G + 255) / 256);
@@ -318,9 +315,7 @@ static int32_t seeded_status(zkp_ctx* c, uint8_t* ds, const uint8_t* sampler_sta
   if (!ds) return ZKP_OK;
   HIPCHK(c, hipSetDevice(c->device));
   if (!merge) HIPCHK(c, hipMemsetAsync(ds, 0, B, c->stream));
-  hipLaunchKernelGGL(k_or_bytes, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, ds, sampler_status, B);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  return launch_rows(c, k_or_bytes, B, ds, sampler_status, B);
 }
 
 extern "C" int32_t zkp_range_sample_witness_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint8_t* seed, uint64_t first_index,
@@ -348,8 +343,7 @@ extern "C" int32_t zkp_range_sample_witness_batch(zkp_ctx* c, const zkp_range_ni
   int32_t st = s.st;
   if (!st && !ds) { st = ensure(c, c->scratch[S_SAMPLE_STATUS], B); ds = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p; }
   if (!st) st = range_sample_launch(c, d, p->error_factor, key, first_index, w[0], w[1], w[2], w[3], ds);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint32_t* x, const uint32_t* r, const uint8_t* seed,
@@ -388,8 +382,7 @@ extern "C" int32_t zkp_range_ni_prove_seeded_batch(zkp_ctx* c, const zkp_range_n
   if (!st) st = range_sample_launch(c, d, (uint32_t)EF, key, first_index, wit[0], wit[1], wit[2], wit[3], sampler_status);
   if (!st) st = zkp_range_ni_prove_batch(c, &d, &dw, de, dl, ds, ZKP_F_DEVICE_PTRS);      // (a null x or r is refused there: ZKP_EINVAL, after the sampler ran)
   if (!st) st = seeded_status(c, ds, sampler_status, B, true);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_diag_witness_residue(zkp_ctx* c, uint64_t* out_nonzero_words) try {
@@ -481,8 +474,7 @@ static int32_t range_interactive_seeded(zkp_ctx* c, const char* name, int step, 
   if (!st) st = step == 1 ? zkp_range_generate_encrypted_pairs_batch(c, &d, &dw, ZKP_F_DEVICE_PTRS)
                           : zkp_range_generate_proof_batch(c, &d, &dw, de, dl, ds, ZKP_F_DEVICE_PTRS);
   if (!st) st = seeded_status(c, ds, sampler_status, B, step == 2);      // (step 1 has no status of its own: the sampler's alone)
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 extern "C" int32_t zkp_range_generate_encrypted_pairs_seeded_batch(zkp_ctx* c, const zkp_range_ni_proofs* p, const uint8_t* seed, uint64_t first_index,
                                                                    uint8_t* out_status, uint32_t flags) try {
@@ -511,8 +503,7 @@ extern "C" int32_t zkp_range_challenge_batch(zkp_ctx* c, const zkp_range_ni_proo
   int32_t st = s.st;
   if (!st) st = ensure(c, c->scratch[S_STATUS], B);
   if (!st) st = range_hash<GA>(c, d, de, dl, (uint8_t*)c->scratch[S_STATUS].p, 0);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // Names a verify's transcript hashes to the Enc launch for the length of it (c->fuse_hash points at a local of range_verify_impl): cleared
@@ -690,8 +681,7 @@ static int32_t range_verify_entry(zkp_ctx* c, const zkp_range_ni_proofs* p, cons
     }
     for (size_t k = 0; k < nb && !st; k++) st = pp.d2h(blocks[k], blocks[k + 1], c->ev_pipe[2 * k + 1]);
     const int32_t fc = pp.finish();
-    const int32_t fin = s.finish();
-    return st ? st : (fc ? fc : fin);
+    return s.finish(st ? st : fc);
   }
   zkp_range_ni_proofs d = *p;
   d.n = s.in(p->n, p->n_stride ? B * kw : kw);
@@ -706,8 +696,7 @@ static int32_t range_verify_entry(zkp_ctx* c, const zkp_range_ni_proofs* p, cons
   const uint8_t* deli = s.in(e_len_in, B);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * p->n_bits), [&](auto G) { return range_verify_impl<G()>(c, d, dv, dei, deli); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 // ---- NiCorrectKeyProof ------------------------------------------------------------------------
@@ -779,8 +768,7 @@ extern "C" int32_t zkp_correct_key_ni_verify_batch(zkp_ctx* c, uint32_t n_bits, 
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return ck_verify_impl<G()>(c, n_bits, batch, dn, dsg, dsalt, salt_len, dv); });
   if (!st && (flags & ZKP_F_DEVICE_PTRS)) { if (hipStreamSynchronize(c->stream) != hipSuccess) { st = ZKP_EDEVICE; c->err = "sync"; } }   // salt staging is freed below
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // ---- CompositeDLogProof ------------------------------------------------------------------------
@@ -792,12 +780,12 @@ template <int G>
 static int32_t dlog_prove_impl(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* N, const uint32_t* g, const uint32_t* ni,
                                const uint32_t* secret, const uint32_t* r, uint32_t* x, uint32_t* y) {
   const uint32_t kw = n_bits / 32;
-  int32_t st;
-  if ((st = run_setup<G>(c, N, kw, (int)kw, 0, batch, c->consts))) return st;
-  // x = g^r mod N, r < 2^512 (wi_dlog_proof.rs:53-55)
-  if ((st = modexp_core<G>(c, 512, batch, g, r, 16, true, x, (int)kw))) return st;
-  if ((st = ensure(c, c->scratch[S_DLOG_E], batch * 32))) return st;
-  DlogHashArgs h{N, g, ni, x, kw, batch, (uint32_t*)c->scratch[S_DLOG_E].p, nullptr, secret, r, y, y_bits / 32, 3};
+  Compose<G> m(c, batch, true, kw);
+  m.M.setup(N, kw, 0);
+  m.M.pow(512, g, r, 16, x, (int)kw);                                 // x = g^r mod N, r < 2^512 (wi_dlog_proof.rs:53-55)
+  uint32_t* e = m.buf(S_DLOG_E, batch * 8);
+  if (m.st) return m.st;
+  DlogHashArgs h{N, g, ni, x, kw, batch, e, nullptr, secret, r, y, y_bits / 32, 3};
   hipLaunchKernelGGL(k_dlog_hash, dim3((unsigned)((batch + DLOG_THREADS - 1) / DLOG_THREADS)), dim3(DLOG_THREADS), 16 * DLOG_THREADS * 4, c->stream, h);
   HIPCHK(c, hipGetLastError());
   return ZKP_OK;
@@ -817,8 +805,7 @@ extern "C" int32_t zkp_dlog_prove_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y_
   uint32_t* dy = s.out(out_y, batch * (y_bits / 32));
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return dlog_prove_impl<G()>(c, n_bits, y_bits, batch, dN, dg, dni, dsec, dr, dx, dy); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 template <int G>
@@ -826,18 +813,20 @@ static int32_t dlog_verify_impl(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, ui
                                 const uint32_t* x, const uint32_t* y, uint8_t* verdict) {
   using CL = ConstLayout<G>;
   const uint32_t kw = n_bits / 32;
-  int32_t st;
-  if ((st = run_setup<G>(c, N, kw, (int)kw, 0, batch, c->consts))) return st;
-  if ((st = ensure(c, c->scratch[S_DLOG_E], batch * 32))) return st;
-  for (int k : {S_TMP1, S_TMP2, S_TMP3}) if ((st = ensure(c, c->scratch[k], batch * kw * 4))) return st;
+  Compose<G> m(c, batch, true, kw);
+  m.M.setup(N, kw, 0);
+  uint32_t* e = m.buf(S_DLOG_E, batch * 8);
+  uint32_t *t1 = m.buf(S_TMP1, batch * kw), *t2 = m.buf(S_TMP2, batch * kw), *t3 = m.buf(S_TMP3, batch * kw);
+  if (m.st) return m.st;
   HIPCHK(c, hipMemsetAsync(c->scratch[S_TMP3].p, 0, batch * kw * 4, c->stream));
   // A call that leaves room on the GPU runs the verifier's pre-checks (N > 2^128 and the two GCDs: ~1 ms on one lane per
   // proof, needed only by the final compare) on the second stream, next to the exponentiations; the challenge stays here.
   const bool two = batch <= 16ull * (uint64_t)c->route.cus;      // (64 wavefronts of pre-checks at most)
-  DlogHashArgs h{N, g, ni, x, kw, batch, (uint32_t*)c->scratch[S_DLOG_E].p, verdict, nullptr, nullptr, nullptr, 0, two ? 1u : 3u};
+  DlogHashArgs h{N, g, ni, x, kw, batch, e, verdict, nullptr, nullptr, nullptr, 0, two ? 1u : 3u};
   const dim3 hash_grid((unsigned)((batch + DLOG_THREADS - 1) / DLOG_THREADS));
   const size_t hash_lds = (16 + 2 * kw) * DLOG_THREADS * 4;
   if (two) {
+    int32_t st;
     if ((st = side_stream(c))) return st;
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));            // inputs staged
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
@@ -849,16 +838,12 @@ static int32_t dlog_verify_impl(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, ui
   }
   hipLaunchKernelGGL(k_dlog_hash, hash_grid, dim3(DLOG_THREADS), hash_lds, c->stream, h);
   HIPCHK(c, hipGetLastError());
-  uint32_t *t1 = (uint32_t*)c->scratch[S_TMP1].p, *t2 = (uint32_t*)c->scratch[S_TMP2].p, *t3 = (uint32_t*)c->scratch[S_TMP3].p;
-  // ni^e (:81) and g^y (:82) side by side in one launch
-  if ((st = modexp_multi<G>(c, batch, true, {{256, ni, (const uint32_t*)c->scratch[S_DLOG_E].p, 8, t1, (int)kw, 0},
-                                             {y_bits, g, y, y_bits / 32, t2, (int)kw, 0}}))) return st;
-  if ((st = modmul_ctx<G>(c, c->consts, true, batch, t1, 0, t2, 0, t3, (int)kw))) return st;                                // mod_mul :83
+  m.M.pow_multi({{256, ni, e, 8, t1, (int)kw, 0}, {y_bits, g, y, y_bits / 32, t2, (int)kw, 0}});      // ni^e (:81) and g^y (:82) side by side in one launch
+  m.M.mul(t1, 0, t2, 0, t3, (int)kw);                                                                 // mod_mul :83
+  if (m.st) return m.st;
   if (two) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); c->side_busy = false; }
-  DlogCmpArgs q{x, t3, (const uint32_t*)c->consts.p, (uint64_t)CL::WORDS, CL::OFF_ST, kw, batch, verdict};
-  hipLaunchKernelGGL(k_dlog_compare, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, q);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  m.rows(k_dlog_compare, batch, DlogCmpArgs{x, t3, m.M.cst(), (uint64_t)CL::WORDS, CL::OFF_ST, kw, batch, verdict});
+  return m.st;
 }
 
 extern "C" int32_t zkp_dlog_verify_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* N, const uint32_t* g,
@@ -874,28 +859,12 @@ extern "C" int32_t zkp_dlog_verify_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y
   uint8_t* dv = s.out(out_verdict, batch);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB>(group_for_bits(n_bits), [&](auto G) { return dlog_verify_impl<G()>(c, n_bits, y_bits, batch, dN, dg, dni, dx, dy, dv); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // ---- ZeroProof / CiphertextProof (SURVEY §8(f) rank 1): compositions of the same kernels ---------------
 static bool sigma_args_ok(uint32_t n_bits, uint64_t batch, uint64_t n_stride) {
   return key_bits_ok(n_bits) && batch <= (1ull << 24) && (n_stride == 0 || n_stride == n_bits / 32);
-}
-
-static int32_t sigma_hash(zkp_ctx* c, const SigmaHashArgs& h) {
-  hipLaunchKernelGGL(k_sigma_hash, dim3((unsigned)((h.batch + 255) / 256)), dim3(256), 0, c->stream, h);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
-}
-// verdict = lhs == rhs, word for word (MALFORMED under a key the set-up rejected; the constants are c->consts)
-template <int G>
-static int32_t words_compare(zkp_ctx* c, bool per_item, uint64_t batch, const uint32_t* lhs, const uint32_t* rhs, uint32_t words, uint8_t* verdict) {
-  using CL = ConstLayout<G>;
-  WordsCmpArgs q{lhs, rhs, (const uint32_t*)c->consts.p, per_item ? (uint64_t)CL::WORDS : 0, CL::OFF_ST, words, batch, verdict};
-  hipLaunchKernelGGL(k_words_compare, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, q);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
 }
 
 // commit: out_commit = Enc(m', r');  e = H(n, c, commit);  [z1 = x' + x e];  z = r' * r^e mod n^2
@@ -904,16 +873,15 @@ static int32_t sigma_prove_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, con
                                 const uint32_t* x, const uint32_t* r, const uint32_t* x_prime, const uint32_t* r_prime, uint32_t* out_z1,
                                 uint32_t* out_z, uint32_t* out_commit) {
   const uint32_t kw = n_bits / 32;
-  const uint64_t nkeys = n_stride ? batch : 1;
-  int32_t st;
-  if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, nkeys, c->consts))) return st;
-  if ((st = enc_launch<G>(c, n_bits, batch, n, n_stride, x_prime, x_prime ? 0 : -1, r_prime, 0, out_commit))) return st;
-  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
-  if ((st = ensure(c, c->scratch[S_TMP1], batch * 2 * kw * 4))) return st;
-  if ((st = sigma_hash(c, {n, n_stride, cc, out_commit, kw, batch, (uint32_t*)c->scratch[S_E].p, x, x_prime, out_z1, kw + ZKP_Z1_EXTRA_LIMBS}))) return st;
-  uint32_t* t1 = (uint32_t*)c->scratch[S_TMP1].p;
-  if ((st = modexp_core<G>(c, 256, batch, r, (const uint32_t*)c->scratch[S_E].p, 8, n_stride != 0, t1, (int)kw, (int)(2 * kw)))) return st;   // r^e mod nn
-  return modmul_ctx<G>(c, c->consts, n_stride != 0, batch, r_prime, (int)kw, t1, (int)(2 * kw), out_z, (int)(2 * kw));
+  const int w1 = (int)kw, w2 = (int)(2 * kw);
+  Compose<G> m(c, batch, n_stride != 0, kw);
+  m.M.setup(n, n_stride, 1);
+  m.enc(n, n_stride, x_prime, x_prime ? 0 : -1, r_prime, 0, out_commit);
+  uint32_t *e = m.buf(S_E, batch * 8), *t1 = m.buf(S_TMP1, batch * 2 * kw);
+  m.rows(k_sigma_hash, batch, SigmaHashArgs{n, n_stride, cc, out_commit, kw, batch, e, x, x_prime, out_z1, kw + ZKP_Z1_EXTRA_LIMBS});
+  m.M.pow(256, r, e, 8, t1, w1, w2);               // r^e mod nn
+  m.M.mul(r_prime, w1, t1, w2, out_z, w2);
+  return m.st;
 }
 
 // Enc(z1, z) == c^e * commit mod n^2
@@ -921,18 +889,19 @@ template <int G>
 static int32_t sigma_verify_impl(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
                                  const uint32_t* z1, const uint32_t* z, const uint32_t* commit, uint8_t* verdict) {
   const uint32_t kw = n_bits / 32;
-  const uint64_t nkeys = n_stride ? batch : 1;
-  int32_t st;
-  if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, nkeys, c->consts))) return st;
-  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
-  for (int k : {S_TMP1, S_TMP2, S_TMP3}) if ((st = ensure(c, c->scratch[k], batch * 2 * kw * 4))) return st;
-  uint32_t *t1 = (uint32_t*)c->scratch[S_TMP1].p, *t2 = (uint32_t*)c->scratch[S_TMP2].p, *t3 = (uint32_t*)c->scratch[S_TMP3].p;
+  const int w2 = (int)(2 * kw);
+  Compose<G> m(c, batch, n_stride != 0, kw);
+  m.M.setup(n, n_stride, 1);
+  uint32_t* e = m.buf(S_E, batch * 8);
+  uint32_t *t1 = m.buf(S_TMP1, batch * 2 * kw), *t2 = m.buf(S_TMP2, batch * 2 * kw), *t3 = m.buf(S_TMP3, batch * 2 * kw);
+  if (m.st) return m.st;
   HIPCHK(c, hipMemsetAsync(t3, 0, batch * 2 * kw * 4, c->stream));
-  if ((st = sigma_hash(c, {n, n_stride, cc, commit, kw, batch, (uint32_t*)c->scratch[S_E].p, nullptr, nullptr, nullptr, 0}))) return st;
-  if ((st = enc_launch<G>(c, n_bits, batch, n, n_stride, z1, z1 ? (int)(kw + ZKP_Z1_EXTRA_LIMBS) : -1, z, (int)(2 * kw), t1))) return st;          // c_z
-  if ((st = modexp_core<G>(c, 256, batch, cc, (const uint32_t*)c->scratch[S_E].p, 8, n_stride != 0, t2, (int)(2 * kw)))) return st;          // c^e  (Paillier::mul)
-  if ((st = modmul_ctx<G>(c, c->consts, n_stride != 0, batch, t2, 0, commit, 0, t3, (int)(2 * kw)))) return st;                                // Paillier::add
-  return words_compare<G>(c, n_stride != 0, batch, t1, t3, 2 * kw, verdict);
+  m.rows(k_sigma_hash, batch, SigmaHashArgs{n, n_stride, cc, commit, kw, batch, e, nullptr, nullptr, nullptr, 0});
+  m.enc(n, n_stride, z1, z1 ? (int)(kw + ZKP_Z1_EXTRA_LIMBS) : -1, z, w2, t1);      // c_z
+  m.M.pow(256, cc, e, 8, t2, w2);                                                   // c^e  (Paillier::mul)
+  m.M.mul(t2, 0, commit, 0, t3, w2);                                                // Paillier::add
+  m.compare(t1, t3, 2 * kw, verdict);
+  return m.st;
 }
 
 static int32_t sigma_prove_entry(zkp_ctx* c, const char* name, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -957,8 +926,7 @@ static int32_t sigma_prove_entry(zkp_ctx* c, const char* name, uint32_t n_bits, 
   uint32_t* dcm = s.out(out_commit, batch * 2 * kw);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return sigma_prove_impl<G()>(c, n_bits, batch, dn, n_stride, dc, dx, dr, dxp, drp, dz1, dz, dcm); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 static int32_t sigma_verify_entry(zkp_ctx* c, const char* name, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -977,8 +945,7 @@ static int32_t sigma_verify_entry(zkp_ctx* c, const char* name, uint32_t n_bits,
   uint8_t* dv = s.out(verdict, batch);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return sigma_verify_impl<G()>(c, n_bits, batch, dn, n_stride, dc, dz1, dz, dcm, dv); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 extern "C" int32_t zkp_zero_proof_prove_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -1006,18 +973,15 @@ extern "C" int32_t zkp_ciphertext_proof_verify_batch(zkp_ctx* c, uint32_t n_bits
 // ---- VerlinProof (verlin_proof.rs:35-165): the same kernels once more ------------------------------------
 // out = c^y * c'^y' * Enc(y'', r_y) mod n^2   (gen_phi, verlin_proof.rs:138-165).  Uses scratch T1..T3.
 template <int G>
-static int32_t verlin_gen_phi(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc, const uint32_t* ccp,
-                              const uint32_t* y, const uint32_t* yp, const uint32_t* ypp, int y_words, const uint32_t* ry, int ry_words, uint32_t* out) {
-  const uint32_t kw = n_bits / 32;
-  uint32_t *t1 = (uint32_t*)c->scratch[S_TMP1].p, *t2 = (uint32_t*)c->scratch[S_TMP2].p, *t3 = (uint32_t*)c->scratch[S_TMP3].p;
-  int32_t st;
-  const bool per = n_stride != 0;
+static void verlin_gen_phi(Compose<G>& m, const uint32_t* n, uint64_t n_stride, const uint32_t* cc, const uint32_t* ccp, const uint32_t* y, const uint32_t* yp,
+                           const uint32_t* ypp, int y_words, const uint32_t* ry, int ry_words, uint32_t* out) {
+  const int w2 = (int)(2 * m.kw);
+  uint32_t *t1 = m.buf(S_TMP1, m.batch * w2), *t2 = m.buf(S_TMP2, m.batch * w2), *t3 = m.buf(S_TMP3, m.batch * w2);
   // Paillier::mul(c, y) and Paillier::mul(c', y'): one launch
-  if ((st = modexp_multi<G>(c, batch, per, {{(uint32_t)y_words * 32, cc, y, (uint64_t)y_words, t1, (int)(2 * kw), 0},
-                                            {(uint32_t)y_words * 32, ccp, yp, (uint64_t)y_words, t2, (int)(2 * kw), 0}}))) return st;
-  if ((st = enc_launch<G>(c, n_bits, batch, n, n_stride, ypp, y_words, ry, ry_words, t3))) return st;                              // Enc(y'', r_y)
-  if ((st = modmul_ctx<G>(c, c->consts, per, batch, t1, 0, t2, 0, t1, (int)(2 * kw)))) return st;                                                  // Paillier::add
-  return modmul_ctx<G>(c, c->consts, per, batch, t1, 0, t3, 0, out, (int)(2 * kw));
+  m.M.pow_multi({{(uint32_t)y_words * 32, cc, y, (uint64_t)y_words, t1, w2, 0}, {(uint32_t)y_words * 32, ccp, yp, (uint64_t)y_words, t2, w2, 0}});
+  m.enc(n, n_stride, ypp, y_words, ry, ry_words, t3);      // Enc(y'', r_y)
+  m.M.mul(t1, 0, t2, 0, t1, w2);                           // Paillier::add
+  m.M.mul(t1, 0, t3, 0, out, w2);
 }
 
 template <int G>
@@ -1025,29 +989,25 @@ static int32_t verlin_impl(zkp_ctx* c, bool prove, uint32_t n_bits, uint64_t bat
                            const uint32_t* phi_x, const uint32_t* const x[3], const uint32_t* r_x, const uint32_t* const a[3], const uint32_t* r_a,
                            uint32_t* phi_a, uint32_t* const z[3], uint32_t* r_z, uint8_t* verdict) {
   const uint32_t kw = n_bits / 32, zw = kw + ZKP_Z1_EXTRA_LIMBS;
-  const uint64_t nkeys = n_stride ? batch : 1;
-  const bool per = n_stride != 0;
-  int32_t st;
-  if ((st = run_setup<G>(c, n, n_stride, (int)kw, 1, nkeys, c->consts))) return st;
-  if ((st = ensure(c, c->scratch[S_E], batch * 32))) return st;
-  for (int k : {S_TMP1, S_TMP2, S_TMP3, S_TMP4, S_TMP5}) if ((st = ensure(c, c->scratch[k], batch * 2 * kw * 4))) return st;
-  uint32_t* e = (uint32_t*)c->scratch[S_E].p;
-  uint32_t *t4 = (uint32_t*)c->scratch[S_TMP4].p, *t5 = (uint32_t*)c->scratch[S_TMP5].p;
+  const int w1 = (int)kw, w2 = (int)(2 * kw);
+  Compose<G> m(c, batch, n_stride != 0, kw);
+  m.M.setup(n, n_stride, 1);
+  uint32_t* e = m.buf(S_E, batch * 8);
+  for (int k : {S_TMP1, S_TMP2, S_TMP3}) (void)m.buf(k, batch * 2 * kw);
+  uint32_t *t4 = m.buf(S_TMP4, batch * 2 * kw), *t5 = m.buf(S_TMP5, batch * 2 * kw);
   if (prove) {
-    if ((st = verlin_gen_phi<G>(c, n_bits, batch, n, n_stride, cc, ccp, a[0], a[1], a[2], (int)kw, r_a, (int)kw, phi_a))) return st;
-    VerlinHashArgs h{n, n_stride, {cc, ccp, phi_x, phi_a}, kw, batch, e, {x[0], x[1], x[2]}, {a[0], a[1], a[2]}, {z[0], z[1], z[2]}, zw};
-    hipLaunchKernelGGL(k_verlin_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
-    HIPCHK(c, hipGetLastError());
-    if ((st = modexp_core<G>(c, 256, batch, r_x, e, 8, per, t4, (int)kw, (int)(2 * kw)))) return st;     // r_x^e mod nn (:88)
-    return modmul_ctx<G>(c, c->consts, per, batch, t4, (int)(2 * kw), r_a, (int)kw, r_z, (int)(2 * kw));
+    verlin_gen_phi(m, n, n_stride, cc, ccp, a[0], a[1], a[2], w1, r_a, w1, phi_a);
+    m.rows(k_verlin_hash, batch, VerlinHashArgs{n, n_stride, {cc, ccp, phi_x, phi_a}, kw, batch, e, {x[0], x[1], x[2]}, {a[0], a[1], a[2]}, {z[0], z[1], z[2]}, zw});
+    m.M.pow(256, r_x, e, 8, t4, w1, w2);                   // r_x^e mod nn (:88)
+    m.M.mul(t4, w2, r_a, w1, r_z, w2);
+    return m.st;
   }
-  VerlinHashArgs h{n, n_stride, {cc, ccp, phi_x, phi_a}, kw, batch, e, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, 0};
-  hipLaunchKernelGGL(k_verlin_hash, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, h);
-  HIPCHK(c, hipGetLastError());
-  if ((st = verlin_gen_phi<G>(c, n_bits, batch, n, n_stride, cc, ccp, z[0], z[1], z[2], (int)zw, r_z, (int)(2 * kw), t4))) return st;    // phi_z
-  if ((st = modexp_core<G>(c, 256, batch, phi_x, e, 8, per, t5, (int)(2 * kw)))) return st;                                              // phi_x^e
-  if ((st = modmul_ctx<G>(c, c->consts, per, batch, t5, 0, phi_a, 0, t5, (int)(2 * kw)))) return st;                                                       // * phi_a
-  return words_compare<G>(c, per, batch, t4, t5, 2 * kw, verdict);
+  m.rows(k_verlin_hash, batch, VerlinHashArgs{n, n_stride, {cc, ccp, phi_x, phi_a}, kw, batch, e, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, 0});
+  verlin_gen_phi(m, n, n_stride, cc, ccp, z[0], z[1], z[2], (int)zw, r_z, w2, t4);      // phi_z
+  m.M.pow(256, phi_x, e, 8, t5, w2);                                                    // phi_x^e
+  m.M.mul(t5, 0, phi_a, 0, t5, w2);                                                     // * phi_a
+  m.compare(t4, t5, 2 * kw, verdict);
+  return m.st;
 }
 
 extern "C" int32_t zkp_verlin_proof_prove_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -1073,8 +1033,7 @@ extern "C" int32_t zkp_verlin_proof_prove_batch(zkp_ctx* c, uint32_t n_bits, uin
   uint32_t* drz = s.out(out_r_z, batch * 2 * kw);
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return verlin_impl<G()>(c, true, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, drx, da, dra, dpa, dz, drz, nullptr); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_verlin_proof_verify_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -1098,6 +1057,5 @@ extern "C" int32_t zkp_verlin_proof_verify_batch(zkp_ctx* c, uint32_t n_bits, ui
   const uint32_t* none[3] = {nullptr, nullptr, nullptr};
   int32_t st = s.st;
   if (!st) st = with_group<GA, GB, GC>(group_for_bits(2 * n_bits), [&](auto G) { return verlin_impl<G()>(c, false, n_bits, batch, dn, n_stride, dc, dcp, dphx, none, nullptr, none, nullptr, (uint32_t*)dpa, dz, (uint32_t*)drz, dv); });
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)

@@ -39,35 +39,26 @@ static int32_t nonce_sample_run(zkp_ctx* c, NonceSampleArgs& a, NonceDraw fourth
   a.meta = (uint32_t*)c->scratch[S_SAMPLE_META].p; a.max_attempts = RANGE_SAMPLE_MAX_ATTEMPTS;
   const uint64_t B = a.batch;
   const uint32_t kw = a.kw;
-  hipLaunchKernelGGL(k_nonce_prep, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
+  if ((st = launch_rows(c, k_nonce_prep, B, a))) return st;
   const uint64_t G = kw / 16;
   uint64_t tasks = 0, fix = 0;
   for (uint32_t k = 0; k < a.nbelow; k++) { tasks += B * a.below_per[k]; fix = std::max<uint64_t>(fix, B * a.below_per[k] * kw / 4); }
   if (tasks) {
-    const dim3 grid((unsigned)((tasks * G + 255) / 256));
     switch (G) {
-      case 2: hipLaunchKernelGGL(k_nonce_sample<2>, grid, dim3(256), 0, c->stream, a); break;
-      case 4: hipLaunchKernelGGL(k_nonce_sample<4>, grid, dim3(256), 0, c->stream, a); break;
-      default: hipLaunchKernelGGL(k_nonce_sample<8>, grid, dim3(256), 0, c->stream, a); break;
+      case 2: st = launch_rows(c, k_nonce_sample<2>, tasks * G, a); break;
+      case 4: st = launch_rows(c, k_nonce_sample<4>, tasks * G, a); break;
+      default: st = launch_rows(c, k_nonce_sample<8>, tasks * G, a); break;
     }
-    HIPCHK(c, hipGetLastError());
+    if (st) return st;
   }
   const uint64_t rows = B * a.raw_per;
-  if (fourth == ND_RAW && rows) hipLaunchKernelGGL(k_nonce_raw, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, a);
+  if (fourth == ND_RAW && rows && (st = launch_rows(c, k_nonce_raw, rows, a))) return st;
   if (fourth == ND_COPRIME) {
-    // As launch_modinv: latency-bound work with data-dependent trip counts, so small blocks — divergence stays among 16 lanes, several
-    // wavefronts share a compute unit, and two operands per lane are 16 KB of LDS per block at kw = 128.
-    const int lanes = 16;
     NonceCoprimeArgs q{a.key, a.n, a.n_stride, a.meta, a.raw, a.status, a.first_index, B, kw, a.kind, a.raw_field, RANGE_SAMPLE_MAX_ATTEMPTS};
-    hipLaunchKernelGGL(k_nonce_coprime, dim3((unsigned)((B + lanes - 1) / lanes)), dim3(lanes), lanes * coprime_lds_words_per_lane(kw) * 4, c->stream, q);
+    if ((st = launch_lanes(c, k_nonce_coprime, B, coprime_lds_words_per_lane(kw), q))) return st;
   }
-  HIPCHK(c, hipGetLastError());
   fix = std::max<uint64_t>(fix, rows * a.raw_words / 4);
-  if (a.n && fix) {                      // (a kind without a bound has no MALFORMED case)
-    hipLaunchKernelGGL(k_nonce_fixup, dim3((unsigned)((fix + 255) / 256)), dim3(256), 0, c->stream, a);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (a.n && fix) return launch_rows(c, k_nonce_fixup, fix, a);      // (a kind without a bound has no MALFORMED case)
   return ZKP_OK;
 }
 
@@ -125,8 +116,7 @@ static int32_t nonce_sample_entry(zkp_ctx* c, const char* name, bool coprime, ui
   int32_t st = s.st;
   if (!st && !ds) { st = ensure(c, c->scratch[S_SAMPLE_STATUS], batch); ds = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p; }
   if (!st) st = nonce_sample_launch(c, proof_kind, n_bits, batch, K, dn, n_stride, key, first_index, out, ds);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 extern "C" int32_t zkp_nonce_sample_batch(zkp_ctx* c, uint32_t proof_kind, uint32_t n_bits, uint64_t batch, uint32_t num_messages, const uint32_t* n,
@@ -185,8 +175,7 @@ static int32_t sigma_prove_seeded(zkp_ctx* c, const char* name, bool with_x, uin
   if (!st) st = with_x ? zkp_ciphertext_proof_prove_batch(c, n_bits, batch, dn, n_stride, dc, dx, dr, q.f[0], q.f[1], dz1, dz, dcm, ZKP_F_DEVICE_PTRS)
                        : zkp_zero_proof_prove_batch(c, n_bits, batch, dn, n_stride, dc, dr, q.f[0], dz, dcm, ZKP_F_DEVICE_PTRS);
   if (!st) st = seeded_status(c, ds, q.status, batch, false);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 extern "C" int32_t zkp_zero_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -225,8 +214,7 @@ extern "C" int32_t zkp_correct_message_prove_seeded_batch(zkp_ctx* c, uint32_t n
   int32_t st = q.st;      // (a null list, message or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
   if (!st) st = zkp_correct_message_prove_batch(c, n_bits, batch, K, dn, n_stride, dv, dm, q.f[0], q.f[2], q.f[3], q.f[1], dct, dev, dzv, dav, ds, ZKP_F_DEVICE_PTRS);
   if (!st) st = seeded_status(c, ds, q.status, batch, true);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_dlog_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint32_t y_bits, uint64_t batch, const uint32_t* N, const uint32_t* g,
@@ -247,8 +235,7 @@ extern "C" int32_t zkp_dlog_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint
   int32_t st = q.st;      // (a null statement, secret or output is refused by the nonce-input call: ZKP_EINVAL, after the sampler ran)
   if (!st) st = zkp_dlog_prove_batch(c, n_bits, y_bits, batch, dN, dg, dni, dsec, q.f[0], dx, dy, ZKP_F_DEVICE_PTRS);
   if (!st) st = seeded_status(c, ds, q.status, batch, false);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_verlin_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* cc,
@@ -275,8 +262,7 @@ extern "C" int32_t zkp_verlin_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bi
   if (!st) st = zkp_verlin_proof_prove_batch(c, n_bits, batch, dn, n_stride, dc, dcp, dphx, dx, dxp, dxpp, drx, q.f[0], q.f[1], q.f[2], q.f[3], dpa, dz, dzp,
                                              dzpp, drz, ZKP_F_DEVICE_PTRS);
   if (!st) st = seeded_status(c, ds, q.status, batch, false);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 extern "C" int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, const uint32_t* e_a,
@@ -302,8 +288,7 @@ extern "C" int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits,
   if (!st) st = zkp_mul_proof_prove_batch(c, n_bits, batch, dn, n_stride, dea, deb, dec, da, db, dra, drb, drc, q.f[0], q.f[1], df, dz1, dz2, ded, dedb, ds,
                                           ZKP_F_DEVICE_PTRS);
   if (!st) st = seeded_status(c, ds, q.status, batch, true);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 } ZKP_CATCH(c)
 
 // ---- the verifier's commitment of the interactive RangeProof: RangeProof::verifier_commit from a seed, the (r, e) it committed to for the
@@ -311,14 +296,12 @@ extern "C" int32_t zkp_mul_proof_prove_seeded_batch(zkp_ctx* c, uint32_t n_bits,
 // of every session, and the Enc runs as the device-pointer call it already is: zkp_paillier_enc_batch (store) or
 // zkp_paillier_enc_check_batch (compare with `expected`), with their routing, key cache and kernels.
 static int32_t range_commit_launch(zkp_ctx* c, uint32_t n_bits, const RangeCommitArgs& a) {
-  const dim3 grid((unsigned)((a.batch * (n_bits / 512) + 255) / 256));
+  const uint64_t rows = a.batch * (n_bits / 512);
   switch (n_bits / 512) {
-    case 2: hipLaunchKernelGGL(k_range_commit<2>, grid, dim3(256), 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL(k_range_commit<4>, grid, dim3(256), 0, c->stream, a); break;
-    default: hipLaunchKernelGGL(k_range_commit<8>, grid, dim3(256), 0, c->stream, a); break;
+    case 2: return launch_rows(c, k_range_commit<2>, rows, a);
+    case 4: return launch_rows(c, k_range_commit<4>, rows, a);
+    default: return launch_rows(c, k_range_commit<8>, rows, a);
   }
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
 }
 
 // commit (out_com) or reveal (out_r, out_e): the same stream, so the same (r, e).  `s` wipes the seed and every copy of r, e and m on every
@@ -353,8 +336,7 @@ static int32_t range_commit_seeded(zkp_ctx* c, const char* name, bool reveal, ui
   if (!st && !a.status) { st = ensure(c, c->scratch[S_SAMPLE_STATUS], batch); a.status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p; }
   if (!st) st = range_commit_launch(c, n_bits, a);
   if (!st && !reveal) st = zkp_paillier_enc_batch(c, n_bits, batch, a.n, n_stride, a.m, a.r, dcom, ZKP_F_DEVICE_PTRS);
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  return s.finish(st);
 }
 
 extern "C" int32_t zkp_range_verifier_commit_seeded_batch(zkp_ctx* c, uint32_t n_bits, uint64_t batch, const uint32_t* n, uint64_t n_stride, uint32_t e_len,
@@ -392,10 +374,6 @@ extern "C" int32_t zkp_range_verify_commit_batch(zkp_ctx* c, uint32_t n_bits, ui
   a.status = (uint8_t*)c->scratch[S_SAMPLE_STATUS].p;
   if (!st) st = range_commit_launch(c, n_bits, a);
   if (!st) st = zkp_paillier_enc_check_batch(c, n_bits, batch, a.n, n_stride, a.m, dr, nullptr, nullptr, dcom, dv, ZKP_F_DEVICE_PTRS);
-  if (!st) {
-    hipLaunchKernelGGL(k_range_commit_verdict, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c->stream, dv, (const uint8_t*)a.status, batch);
-    HIPCHK(c, hipGetLastError());
-  }
-  const int32_t fin = s.finish();
-  return st ? st : fin;
+  if (!st) st = launch_rows(c, k_range_commit_verdict, batch, dv, (const uint8_t*)a.status, batch);
+  return s.finish(st);
 } ZKP_CATCH(c)

@@ -232,9 +232,7 @@ template <class T> int32_t scan_merge(zkp_ctx* c, Stage& s, const std::vector<T>
   const T* src = s.host_in(host.data(), host.size());
   if (s.st) return s.st;
   const uint64_t total = docs * units_per_doc;
-  hipLaunchKernelGGL(k_scan_merge<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, src, dst, units_per_doc, didx, docs);
-  HIPCHK(c, hipGetLastError());
-  return ZKP_OK;
+  return launch_rows(c, k_scan_merge<T>, total, src, dst, units_per_doc, didx, docs);
 }
 
 // the text of a call as the scanner reads it, uploaded by the caller: byte `a` of the caller's text is d[a - lo], and 16 bytes '0' follow the span
@@ -334,9 +332,7 @@ int32_t json_scan(zkp_ctx* c, Stage& s, const char* name, uint32_t doc_kind, con
     const uint64_t count = head ? B : rows;
     const int32_t e = launch_dec2bin(c, dtext, J.items[t.arr], count, t.dst, item_status, t.words);
     if (e) return e;
-    hipLaunchKernelGGL(k_mark_docs, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, item_status, head ? J.head_doc : J.row_doc, count, dstat, 0);
-    HIPCHK(c, hipGetLastError());
-    return ZKP_OK;
+    return launch_rows(c, k_mark_docs, count, item_status, head ? J.head_doc : J.row_doc, count, dstat, 0);
   };
   for (const Target& t : targets) if (t.arr < W_ARR_C1 && !st) st = convert(t);
   if (st) return st;
